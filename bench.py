@@ -12,6 +12,13 @@ position are written to the device before each step as ggml's inputs are. The
 per-token MUL_MAT chain alone ("chain" workload, described below) is reported
 beside it in "matmul_chain".
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the headline line ("value", "ms_per_step", the per-step spread of the
+same steps). Every other figure described below is a run of its own after the timed
+steps and is measured only with --full. --dump-outputs DIR writes what the last timed
+step computed (the token's logits; the chain's stage outputs) as DIR/<name>.npy; the
+weights, token ids and activations are seeded, so two builds can be compared array by array.
+
 Metric (BASELINE.json): "tg128 tok/s + Q4_K GEMV achieved-HBM-GB/s, TinyLlama-1.1B
 Q4_K_M @1 GPU". One step = one decoded token of the whole graph; its matmuls carry
 629.8 MB of K-quant weights in the Q4_K_M type mix of llama-quant.cpp [U]
@@ -969,6 +976,14 @@ def main():
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--model", default="tinyllama-1.1b", choices=sorted(MODELS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the side figures (per-kernel timing and roofline, tg, "
+                         "large GEMVs, prefill, matmul chain, Llama-3-8B / 70B, row splits, collectives, CPU "
+                         "baseline); the --no-*, --tg and --cpu-seconds options select among them. Without it the "
+                         "run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): the token "
+                         "workload's logits, the chain workload's stage outputs")
     ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "rowsplit", "rowsplit-reduce"],
                     help="the headline at N GPUs: auto (default: N = 1 one token stream on one GPU; N > 1 "
                          "rowsplit-reduce, the north_star's row-split path), replicas (an independent token "
@@ -1119,7 +1134,88 @@ def main():
     head = headline_fields(mode if rowsplit else "replicas", world)  # (a failed communicator: replicas)
     tokens_total = args.steps * head["tokens_per_step"]
     value = tokens_total / t_max
+    if args.dump_outputs:
+        # before anything else runs on the decoder: what the last timed step left for its caller
+        dump_outputs(args.dump_outputs, chain, world, rank)
 
+    # the side figures run on every rank (the row split's steps are collective); rank 0 gets the fields
+    extra = full_figures(args, chain, be, dev, world, rank, local, barrier, rowsplit, split_mode) if args.full else {}
+    result = None
+    if rank == 0:
+        local_bytes = chain.bytes_per_token  # weight bytes one GPU streams per token
+        if isinstance(chain, Token):
+            executor = ("LlamaDecoder -> mi355x_backend_graph_compute: node fusion (norm/swiglu GEMV prologues, "
+                        "residual/swiglu epilogues), kq_rows + kq_attn_decode" +
+                        ((", RCCL ncclAllReduce per K-split stage (row split, reduce)" if split_mode == "reduce" else
+                          ", RCCL ncclAllGather per stage (row split)") if rowsplit else "") + ", " +
+                        ("hipGraph replay" if not args.no_graph else "eager"))
+        else:
+            executor = f"{'kq_gemv' if args.impl == 'tasks' else 'kq_rows'}: 1 launch per stage" + \
+                ("" if args.no_graph else ", hipGraph replay")
+        per_gpu_rate = value / (world if not rowsplit else 1)  # tokens/s each GPU streams its weights for
+        # launches per token of the decode graph are counted on an eager token of their own (--full)
+        stages = chain.launches() if args.full or not isinstance(chain, Token) else None
+        result = {
+            "metric": "tg128 tok/s + Q4_K GEMV achieved-HBM-GB/s, TinyLlama-1.1B Q4_K_M @1 GPU",
+            "value": round(value, 2), "unit": "tok/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(t_max / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": head["scaling"],
+            "vs_baseline": None, "dtype": "q4_K/q6_K x q8_K (u4/u6*i8 dot4 -> i32, f32 combine)",
+            "data": (f"GGUF weights {os.path.basename(args.gguf)}; random f32 first activation" if args.gguf else
+                     "synthetic (random valid K-quant blocks of the real shapes, f32 norms, random token ids)"
+                     if isinstance(chain, Token) else
+                     "synthetic (random valid K-quant blocks of the real shapes; random f32 activations)"),
+            "config": {"workload": (f"{chain.model} Q4_K_M tg{args.steps}: full decode graph, token i at "
+                                    f"position i of a fresh f16 KV cache" if isinstance(chain, Token) else
+                                    f"{chain.model} Q4_K_M decode matmul chain (tg, 1 token/step)"),
+                       "weights_MB_per_token": round(local_bytes * (world if rowsplit else 1) / 1e6, 1),
+                       "weights_MB_per_token_per_gpu": round(local_bytes / 1e6, 1),
+                       "stages_per_token": stages,
+                       "executor": executor,
+                       "parallelism": head["parallelism"],
+                       "hipgraph": not args.no_graph},
+            "gpu_ms_per_step": round(gpu_ms / args.steps, 4),
+            "step_ms": spread(step_ms),
+            "effective_GBps": round(per_gpu_rate * local_bytes / 1e9, 1),
+            # the whole token (every launch, gap and gather included) against the HBM roofline, per GPU
+            "token_hbm_frac": round(per_gpu_rate * local_bytes / 1e9 / HBM_PEAK_GBS, 4),
+            "full": args.full,
+            "rowsplit_error": comm_error,
+            "debug_knobs": knobs or None,
+            "rehearsal": ("BENCH_ONE_DEVICE: all ranks on one GPU, collectives emulated (loopback, no data "
+                          "exchanged): fields and control plane only, not a measurement"
+                          if os.environ.get("BENCH_ONE_DEVICE") and world > 1 else None),
+        }
+        result.update(extra)
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    return result
+
+
+def dump_outputs(out_dir, chain, world, rank):
+    """--dump-outputs: the arrays a caller of the timed path holds after the last timed step,
+    as <name>.npy (float32): the decode token's logits (LlamaDecoder.step's return value),
+    or every stage output of the matmul chain (the MUL_MAT nodes' dst tensors). Rank 0 writes
+    the plain names; an independent stream of another rank (replicas) goes to <name>.rankR."""
+    if isinstance(chain, Token):
+        if rank != 0 and chain.split is not None:
+            return  # the row split gathers the same logits on every rank
+        arrays = {"logits": chain.dec.logits}
+    else:
+        arrays = {name: y for stage, ys in zip(chain.stages, chain.y) for (name, _, _, _), y in zip(stage, ys)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
+def full_figures(args, chain, be, dev, world, rank, local, barrier, rowsplit, split_mode):
+    """--full: everything the line reports beside the headline, each a run of its own after
+    the timed steps. Collective at N > 1: every rank calls it; returns the line's extra fields
+    on rank 0 ({} elsewhere)."""
     # per-launch kernel timing (every rank: the row split's eager steps are collective)
     per = {}
     if isinstance(chain, Token):
@@ -1151,7 +1247,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - a side figure; reported in the line
             colls = {"error": f"{type(e).__name__}: {e}"}
 
-    result = None
+    fields = {}
     if rank == 0:
         # roofline of the dominant GEMV LAUNCH KIND (kernel + bytes per launch, so the q/k/v
         # and gate/up launches of one instantiation are not averaged), from per-launch
@@ -1211,41 +1307,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_token(chain, args.cpu_seconds) if isinstance(chain, Token) else \
                 cpu_baseline(chain, args.cpu_seconds)
-        local_bytes = chain.bytes_per_token  # weight bytes one GPU streams per token
-        if isinstance(chain, Token):
-            executor = ("LlamaDecoder -> mi355x_backend_graph_compute: node fusion (norm/swiglu GEMV prologues, "
-                        "residual/swiglu epilogues), kq_rows + kq_attn_decode" +
-                        ((", RCCL ncclAllReduce per K-split stage (row split, reduce)" if split_mode == "reduce" else
-                          ", RCCL ncclAllGather per stage (row split)") if rowsplit else "") + ", " +
-                        ("hipGraph replay" if not args.no_graph else "eager"))
-        else:
-            executor = f"{'kq_gemv' if args.impl == 'tasks' else 'kq_rows'}: 1 launch per stage" + \
-                ("" if args.no_graph else ", hipGraph replay")
-        per_gpu_rate = value / (world if not rowsplit else 1)  # tokens/s each GPU streams its weights for
-        result = {
-            "metric": "tg128 tok/s + Q4_K GEMV achieved-HBM-GB/s, TinyLlama-1.1B Q4_K_M @1 GPU",
-            "value": round(value, 2), "unit": "tok/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(t_max / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": head["scaling"],
-            "vs_baseline": None, "dtype": "q4_K/q6_K x q8_K (u4/u6*i8 dot4 -> i32, f32 combine)",
-            "data": (f"GGUF weights {os.path.basename(args.gguf)}; random f32 first activation" if args.gguf else
-                     "synthetic (random valid K-quant blocks of the real shapes, f32 norms, random token ids)"
-                     if isinstance(chain, Token) else
-                     "synthetic (random valid K-quant blocks of the real shapes; random f32 activations)"),
-            "config": {"workload": (f"{chain.model} Q4_K_M tg{args.steps}: full decode graph, token i at "
-                                    f"position i of a fresh f16 KV cache" if isinstance(chain, Token) else
-                                    f"{chain.model} Q4_K_M decode matmul chain (tg, 1 token/step)"),
-                       "weights_MB_per_token": round(local_bytes * (world if rowsplit else 1) / 1e6, 1),
-                       "weights_MB_per_token_per_gpu": round(local_bytes / 1e6, 1),
-                       "stages_per_token": chain.launches(),
-                       "executor": executor,
-                       "parallelism": head["parallelism"],
-                       "hipgraph": not args.no_graph},
-            "gpu_ms_per_step": round(gpu_ms / args.steps, 4),
-            "step_ms": spread(step_ms),
-            "effective_GBps": round(per_gpu_rate * local_bytes / 1e9, 1),
-            # the whole token (every launch, gap and gather included) against the HBM roofline, per GPU
-            "token_hbm_frac": round(per_gpu_rate * local_bytes / 1e9 / HBM_PEAK_GBS, 4),
+        fields = {
             "roofline": roof,
             "kernels": kernels, "launch_kinds": launch_kinds,
             "tg128": tg,
@@ -1261,19 +1323,9 @@ def main():
             "replicas": reps,
             "rowsplit": splits,
             "collectives_us": colls,
-            "rowsplit_error": comm_error,
-            "debug_knobs": knobs or None,
-            "rehearsal": ("BENCH_ONE_DEVICE: all ranks on one GPU, collectives emulated (loopback, no data "
-                          "exchanged): fields and control plane only, not a measurement"
-                          if os.environ.get("BENCH_ONE_DEVICE") and world > 1 else None),
             "cpu_baseline": cpu,
         }
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
-    return result
+    return fields
 
 
 if __name__ == "__main__":

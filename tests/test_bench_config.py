@@ -50,6 +50,25 @@ def test_tinyllama_model_size_matches_published():
     assert abs(mib - 636.18) <= 0.01, mib
 
 
+def test_dump_outputs_writes_every_stage_output(tmp_path):
+    """--dump-outputs on the chain workload: one float32 <name>.npy per MUL_MAT node, the values
+    the node's dst tensor holds; another rank's arrays go beside them as <name>.rankR.npy."""
+    import numpy as np
+    import torch
+    chain = bench.Chain.__new__(bench.Chain)
+    chain.stages = [[("blk.0.attn_q", g.TYPE_Q4_K, 256, 5), ("blk.0.attn_k", g.TYPE_Q4_K, 256, 3)],
+                    [("output", g.TYPE_Q6_K, 256, 7)]]
+    chain.y = [[torch.arange(5, dtype=torch.float32), torch.arange(3, dtype=torch.float32) - 1.5],
+               [torch.linspace(-1, 1, 7)]]
+    bench.dump_outputs(str(tmp_path / "d"), chain, 1, 0)
+    bench.dump_outputs(str(tmp_path / "d"), chain, 2, 1)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == sorted(
+        f"{n}{r}.npy" for n in ("blk.0.attn_q", "blk.0.attn_k", "output") for r in ("", ".rank1"))
+    for (name, _, _, _), y in zip(chain.stages[0] + chain.stages[1], chain.y[0] + chain.y[1]):
+        a = np.load(tmp_path / "d" / f"{name}.npy")
+        assert a.dtype == np.float32 and (a == y.numpy()).all()
+
+
 @pytest.mark.parametrize("world", [1, 2, 4, 8])
 def test_multi_gpu_headline_is_the_row_split(world):
     """at N > 1 the driver's scaling line measures the north_star's row-split

@@ -28,7 +28,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
         lib:*) export MI355X_LIB=$V/lib${p#lib:}.so ;;
       esac
     done
-    timeout -k 10 200 python bench.py --model $model --steps 64 --warmup 8 --no-cpu-baseline --no-large \
+    timeout -k 10 200 python bench.py --full --model $model --steps 64 --warmup 8 --no-cpu-baseline --no-large \
         --no-prefill --no-8b --no-70b --no-chain --tg 0 --no-collectives $EXTRA > gpurun_out/ab_one.json 2>gpurun_out/ab_one.err || exit $?
     python - "$C" >> $OUT <<'PY' || exit $?
 import json, sys

@@ -6,9 +6,10 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 OUT=gpurun_out/ab_env.log
 : > $OUT
+ONE=$(dirname $OUT)/ab_one.json  # the run's bench line, read back below
 for round in $(seq ${ROUNDS:-2}); do
   for E in "$@"; do
-    env $E timeout -k 10 200 python bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-large --no-prefill --no-8b --no-70b --no-chain --no-collectives --tg 0 ${BENCH_ARGS:-} > gpurun_out/ab_one.json 2>/dev/null || exit $?
+    env $E timeout -k 10 200 python bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-large --no-prefill --no-8b --no-70b --no-chain --no-collectives --tg 0 ${BENCH_ARGS:-} > $ONE 2>/dev/null || exit $?
     python - "$E" >> $OUT <<'PY' || exit $?
 import json, sys
 d = json.loads(open("gpurun_out/ab_one.json").read().strip().splitlines()[-1])

@@ -6,9 +6,10 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 OUT=gpurun_out/ab_mmq.log
 : > $OUT
+ONE=$(dirname $OUT)/ab_mmq_one.json  # the run's bench line, read back below
 for round in $(seq ${ROUNDS:-2}); do
   for E in "" "MI355X_MMQ_IMPL=tile64"; do
-    env $E timeout -k 10 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-large --no-chain --no-70b --tg 0 > gpurun_out/ab_mmq_one.json 2>/dev/null || exit $?
+    env $E timeout -k 10 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-large --no-chain --no-70b --tg 0 > $ONE 2>/dev/null || exit $?
     python - "$E" >> $OUT <<'PY' || exit $?
 import json, sys
 d = json.loads(open("gpurun_out/ab_mmq_one.json").read().strip().splitlines()[-1])

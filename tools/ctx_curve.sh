@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/ctx_curve.txt
 : > $OUT
 run() {  # model n
-  timeout -k 10 400 python -u bench.py --model $1 --steps 16 --warmup 4 --tg $2 --no-cpu-baseline --no-large \
+  timeout -k 10 400 python -u bench.py --full --model $1 --steps 16 --warmup 4 --tg $2 --no-cpu-baseline --no-large \
       --no-prefill --no-chain --no-8b --no-70b --no-collectives > gpurun_out/cc_tmp.json 2> gpurun_out/cc_tmp.err
   rc=$?; [ $rc -eq 0 ] || { echo "rc=$rc $1 $2"; tail -5 gpurun_out/cc_tmp.err; exit $rc; }
   tail -1 gpurun_out/cc_tmp.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); t=d['tg128']; print('$1', '$2', t['tok_s'], t.get('tok_s_sd'))" | tee -a $OUT

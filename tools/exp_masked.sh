@@ -16,7 +16,7 @@ for r in 1 2; do
   for L in default msk1 msk2; do
     for model in tinyllama-1.1b llama-3-8b; do
       if [ $L = default ]; then unset MI355X_LIB; else export MI355X_LIB=$V/lib$L.so; fi
-      timeout -k 10 200 python bench.py --model $model --steps 64 --warmup 8 --no-cpu-baseline --no-large \
+      timeout -k 10 200 python bench.py --full --model $model --steps 64 --warmup 8 --no-cpu-baseline --no-large \
           --no-prefill --no-8b --no-70b --no-chain --tg 0 --no-collectives > gpurun_out/ab_one.json 2>/dev/null || exit $?
       python - "$L $model" >> $OUT <<'PY' || exit $?
 import json, sys

@@ -11,7 +11,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-FLAGS="--steps 128 --warmup 16 --no-cpu-baseline --no-large --no-prefill --no-chain --no-8b --no-70b --no-collectives --tg 0"
+FLAGS="--full --steps 128 --warmup 16 --no-cpu-baseline --no-large --no-prefill --no-chain --no-8b --no-70b --no-collectives --tg 0"
 D=ggml-neon-opt_amd/lib/variants/libfdiag.so
 P=ggml-neon-opt_amd/lib/libggml_mi355x.so
 for model in ${MODELS:-tinyllama-1.1b llama-3-8b}; do
