@@ -22,9 +22,9 @@ template <int NCOL, bool FUSEDQ, bool DEBUG, int TMASK>
 __global__ void kq_gemv(const GemvArgs a);
 __global__ void kq_quantize_q8K(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
 template <int TMASK, bool FUSEDQ, int PRO>
-__global__ void kq_rows(const RowsArgs a);
+__global__ void kq_rows(KQ_ROWS_PARAMS);
 template <int TMASK, bool FUSEDQ, int PRO>
-__global__ void kq_rows_dyn(const RowsArgs a);
+__global__ void kq_rows_dyn(KQ_ROWS_PARAMS);
 template <bool AM>
 __global__ void kq_quantize_q8L(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
 template <int TYPE, int RT, int CW>
@@ -577,12 +577,25 @@ int launch_rows(const RowsPlan &pl, hipStream_t stream) {
     const RowsArgs &a = pl.a;
     if (a.waves_total == 0) return MI355X_OK;
     allow_lds((const void *)pl.fn, pl.lds);
+    // the leading parameters (KQ_ROWS_PARAMS): what a wave needs before its first memory
+    // request; the kernels read neither gridDim nor blockDim, and the prologue's pass count
+    // (passes of 4 superblocks per wave over the activation) is divided here
+    const void *x = pl.fusedq ? (const void *)a.x : (const void *)a.xq;
+    const int pass = 4 * pl.nwv;
+    const int qiters = pl.fusedq ? (a.nb + pass - 1) / pass : 0;
+    // cfg's fields are a few bits each: a plan outside them would run another launch silently
+    if (pl.nwv < 1 || pl.nwv > ROWS_WAVES || qiters > ROWS_QPASS || a.n_desc < 1 || a.n_desc > MI355X_MAX_FUSED)
+        return MI355X_E_INVAL;
+    const int cfg = rows_cfg(pl.nwv, qiters, a.n_desc, a.diag & 0x1ff);
+    const int grid = (int)pl.grid.x;
     hipEvent_t e0, e1;
     if (timing_slot(stream, e0, e1)) {
-        hipExtLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.nwv * 64), (uint32_t)pl.lds, stream, e0, e1, 0, a);
+        hipExtLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.nwv * 64), (uint32_t)pl.lds, stream, e0, e1, 0, x, a.x2, a.w[0],
+                              a.res[0], a.nb, a.waves_total, grid, cfg, a.rbase[0], a.rrem[0], a);
         timing_log(rows_name(pl), rows_bytes(a, pl.fusedq), e0, e1);
     } else {
-        hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.nwv * 64), pl.lds, stream, a);
+        hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.nwv * 64), pl.lds, stream, x, a.x2, a.w[0], a.res[0], a.nb,
+                           a.waves_total, grid, cfg, a.rbase[0], a.rrem[0], a);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MI355X_OK : (int)e;

@@ -84,7 +84,7 @@ __host__ __device__ inline LdsLayout lds_layout(int ncol, int nb, int out_per_wg
 #endif
 constexpr int ROWS_WAVES = KQ_ROWS_WAVES;  // the most waves per workgroup (LDS layout, launch bounds)
 // Small launches run ROWS_WAVES_SMALL waves per workgroup (the wave count is a launch
-// parameter: blockDim.x / 64): fewer waves to dispatch for a stream that is short anyway.
+// parameter, passed in `cfg`): fewer waves to dispatch for a stream that is short anyway.
 #ifndef KQ_ROWS_WAVES_SMALL
 #define KQ_ROWS_WAVES_SMALL 6
 #endif
@@ -99,42 +99,62 @@ constexpr int ROWS_QPASS = 3;  // fused-quantization passes of 4*ROWS_WAVES supe
 #endif
 constexpr int ROWS_PF = KQ_ROWS_PF;  // touches per wave when a.pf != 0
 
+// Kernel entry (kq_rows, kq_rows_dyn): what a wave needs before its first memory request comes
+// as leading plain parameters, 14 dwords, which the kernarg preload puts in SGPRs at wave start
+// (the activation loads then issue with no scalar-memory trip): x (the Q8L row when !FUSEDQ),
+// x2, the first matrix's w / res, nb, waves_total, the grid size, `cfg` (rows_cfg: waves per
+// workgroup, the prologue's pass count, n_desc, the diagnostic bits), the first matrix's
+// rbase / rrem. RowsArgs follows; the kernels read its first run (up to `stamps_cap`) in ONE
+// batch of scalar loads behind one wait (rows_resolve, kq_rows.hip) and pick per-matrix values
+// from the loaded arrays. The kernels read neither gridDim nor blockDim, and nothing of the
+// host's plan below that run except the experiment knobs of experiment builds.
+#define KQ_ROWS_PARAMS                                                                                        \
+    const void *x, const float *x2, const uint8_t *w0, const float *res0, int nb, int waves_total, int grid, \
+        int cfg, int rbase0, int rrem0, const RowsArgs a
+__host__ __device__ constexpr int rows_cfg(int nwv, int qiters, int n_desc, int diag) {
+    return nwv | (qiters << 8) | (n_desc << 12) | (diag << 16);
+}
+
 struct RowsArgs {
-    int n_desc;
-    int nb;           // K / 256
-    int rpw;          // max rows per wave (LDS sizing)
-    int waves_total;
-    int pre0;         // weight steps issued before the activation is quantized
-    int pf;           // L2 prefetch on/off (ROWS_PF 4-KB touches of the stream past the ring)
+    // ---- the run the kernels read at entry (one batch)
     int bR;           // rows per chain batch (bR*nb % 16 == 0 unless bR >= rpw)
-    int xmode;        // fused-quantization prologue: ROWS_X_* bits
-    int diag;         // diagnostics (timing only): bit3 stream weights only, 16/32 prologue, 64 no quantization, 128 no SWIGLU epilogue, 256 empty launch
+    int rpw;          // max rows per wave (LDS sizing)
     int wave_prefix[MI355X_MAX_FUSED + 1];
+    // SWIGLU epilogue (epi != 0): y[0] = gate, y[1] = up with equal rows and wave counts,
+    // up wave `wave` pairs with gate wave `wave - epi_wave_off` of the same workgroup
+    // (identical row ranges); epi_y[r] = swiglu(gate[r], up[r]) for r < epi_n
+    int epi;
     int rbase[MI355X_MAX_FUSED];
     int rrem[MI355X_MAX_FUSED];
     int type[MI355X_MAX_FUSED];
     const uint8_t *w[MI355X_MAX_FUSED];
-    float *y[MI355X_MAX_FUSED];
-    const float *x;       // f32 activation (FUSEDQ)
-    const uint8_t *xq;    // Q8L activation row (!FUSEDQ), written by kq_quantize_q8L
-    uint64_t *stamps;
-    int64_t stamps_cap;
     // fused neighbours of the MUL_MAT in the decode graph (FUSEDQ only):
-    int pro;              // ROWS_PRO_*: transform of x before its Q8_K quantization
-    float eps;            // ROWS_PRO_NORM: rms_norm epsilon
-    const float *x2;      // ROWS_PRO_NORM: norm weight (the MUL after RMS_NORM); ROWS_PRO_SWIGLU: up (x = gate)
     const float *res[MI355X_MAX_FUSED];  // y[m] = mul_mat + res[m] (the ADD after the MUL_MAT), or null
-    int n_rows[MI355X_MAX_FUSED];
-    // SWIGLU epilogue (epi != 0): y[0] = gate, y[1] = up with equal rows and wave counts,
-    // up wave `wave` pairs with gate wave `wave - epi_wave_off` of the same workgroup
-    // (identical row ranges); epi_y[r] = swiglu(gate[r], up[r]) for r < epi_n
-    int epi, epi_n, epi_wave_off;
+    float *y[MI355X_MAX_FUSED];
     float *epi_y;
-    int64_t prio_bytes;  // the most weight bytes any wave streams (KQ_ROWS_PRIO: remaining-work priority)
+    float eps;            // ROWS_PRO_NORM: rms_norm epsilon
+    int epi_n, epi_wave_off;
     // kq_rows_dyn (claimed rows): workgroup b owns rows [b*N/G, (b+1)*N/G) of every matrix
     // (rpw = the most such rows over the matrices, summed); its waves claim units of dyn_u
     // rows from an LDS counter, the first dyn_p units of each wave assigned statically
     int dyn_u, dyn_p, dyn_ush;  // (dyn_u = 1 << dyn_ush; rbase[0] / rrem[0]: the rows N / G split)
+    int n_rows[MI355X_MAX_FUSED];
+    uint64_t *stamps;     // diagnostic builds
+    int64_t stamps_cap;
+    // ---- the host's plan; what the kernels need of it travels as leading parameters
+    int n_desc;
+    int nb;           // K / 256
+    int waves_total;
+    const float *x;       // f32 activation (FUSEDQ)
+    const uint8_t *xq;    // Q8L activation row (!FUSEDQ), written by kq_quantize_q8L
+    const float *x2;      // ROWS_PRO_NORM: norm weight (the MUL after RMS_NORM); ROWS_PRO_SWIGLU: up (x = gate)
+    int pro;              // ROWS_PRO_*: transform of x before its Q8_K quantization
+    int diag;         // diagnostics (timing only): bit3 stream weights only, 16/32 prologue, 64 no quantization, 128 no SWIGLU epilogue, 256 empty launch
+    // ---- experiment builds only (compile-time constants in the product)
+    int pre0;         // weight steps issued before the activation is quantized
+    int pf;           // L2 prefetch on/off (ROWS_PF 4-KB touches of the stream past the ring)
+    int xmode;        // fused-quantization prologue: ROWS_X_* bits
+    int64_t prio_bytes;  // the most weight bytes any wave streams (KQ_ROWS_PRIO: remaining-work priority)
 };
 constexpr int ROWS_PRO_NONE = 0, ROWS_PRO_NORM = 1, ROWS_PRO_SWIGLU = 2;
 // Prologue of the fused quantization (a.xmode bits):

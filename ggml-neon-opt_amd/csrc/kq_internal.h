@@ -25,7 +25,7 @@ struct GemvPlan {
 int plan_gemv(const mi355x_gemv_desc *d, int n_desc, int64_t K, int64_t M, int ncol, bool fusedq, bool debug,
               GemvPlan &pl);
 int launch_gemv(const GemvPlan &pl, hipStream_t stream);
-typedef void (*rows_fn)(const RowsArgs);
+typedef void (*rows_fn)(KQ_ROWS_PARAMS);
 struct RowsPlan {
     RowsArgs a;
     dim3 grid;

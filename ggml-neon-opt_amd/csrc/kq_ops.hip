@@ -45,27 +45,50 @@ namespace kq {
 // One workgroup per (id, 2048-element chunk); thread t dequantizes 8 consecutive
 // elements. Q4_K / Q5_K: y = fmaf(d*sc, q, -(dmin*m)) (gcc contracts `d1*q - m1` [U]; Q5_K's
 // q is the nibble + 16 * its qh bit); Q6_K: y = (d*sc)*q; F32: copy.
+// Entry: the parameters are plain (14 dwords, preloaded), then the token id, then the
+// chunk's up to 8 superblocks in ONE round trip: each thread fetches one 16-B granule of
+// them (from the 16-B boundary below the first block, as kq_rows' streams) into LDS, and the
+// blocks are decoded from there, instead of byte loads with a wait each.
+constexpr int GETROWS_STAGE = ((15 + 8 * 210 + 15) / 16) * 16;  // 8 Q6_K blocks off a 16-B boundary
 __global__ void __launch_bounds__(256) kq_get_rows(int type, const uint8_t *__restrict__ table, int64_t k,
                                                    int64_t row_stride, int64_t n_rows,
                                                    const int32_t *__restrict__ ids, float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[GETROWS_STAGE];
     const int64_t r = blockIdx.y;
     const int64_t e0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    if (e0 >= k) return;
+    const bool live = e0 < k;
     const int64_t id = ids[r];
     float *y = out + r * k + e0;
     if (id < 0 || id >= n_rows) {  // ggml asserts 0 <= i01 < ne01: never read outside the table
+        if (live) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) y[i] = __builtin_nanf("");
+            for (int i = 0; i < 8; ++i) y[i] = __builtin_nanf("");
+        }
         return;
     }
-    const uint8_t *row = table + id * row_stride;
+    const uint8_t *grow = table + id * row_stride;
     if (type == MI355X_TYPE_F32) {
-        const float *s = (const float *)row + e0;
+        if (live) {
+            const float *s = (const float *)grow + e0;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) y[i] = s[i];
+            for (int i = 0; i < 8; ++i) y[i] = s[i];
+        }
         return;
     }
-    const int64_t b = e0 / QK;
+    // the workgroup's superblocks [b0, b0 + nblk) of the row -> LDS (uniform over the workgroup)
+    const int bsz = block_bytes(type);
+    const int64_t b0 = (int64_t)blockIdx.x * 8;
+    const int64_t left = k / QK - b0;
+    const int nblk = (int)(left < 8 ? left : 8);
+    const uint8_t *src = grow + b0 * bsz;
+    const uint32_t mis = (uint32_t)((uintptr_t)src & 15u);
+    const int ng = (int)((mis + (uint32_t)(nblk * bsz) + 15u) / 16u);  // <= GETROWS_STAGE / 16
+    if ((int)threadIdx.x < ng)
+        *(u32x4 *)(stage + 16 * threadIdx.x) = *(const u32x4 *)(src - mis + 16 * threadIdx.x);
+    __syncthreads();
+    if (!live) return;
+    const uint8_t *row = stage + mis;  // the chunk's block b at row + b * bsz
+    const int64_t b = e0 / QK - b0;
     const int e = (int)(e0 % QK);
     if (type == MI355X_TYPE_Q4_K || type == MI355X_TYPE_Q5_K) {
         const bool q5 = type == MI355X_TYPE_Q5_K;
@@ -213,9 +236,49 @@ __global__ void __launch_bounds__(256) kq_rope(const float *__restrict__ x, floa
 #ifndef KQ_ATTN_KDMA1  // 1: experiment build, caches of <= 256 cells on the LDS-DMA path (attn_head KD1)
 #define KQ_ATTN_KDMA1 0
 #endif
+// Entry (DESIGN.md §7 "Kernel entry"): the pointers a head needs first are leading plain
+// parameters, 14 dwords, in SGPRs at wave start with the kernarg preload (KQ_ATTN_PARAMS; the
+// AttnArgs that follows repeats them for the kernels that share it). The rest of AttnArgs
+// (out .. n_tok, 14 dwords) is fetched in one batch behind one wait, so no kernarg load is
+// left behind a later wait; *pos is the one dependent load.
+#define KQ_ATTN_PARAMS                                                                                      \
+    const float *q, const float *k, const float *v, const int32_t *pos, const float *rope_table, uint16_t *k_cache, \
+        uint16_t *v_cache, const AttnArgs a0
+constexpr int kAttnArgsOff = 14 * 4;  // AttnArgs in the kernarg segment: after the 14 leading dwords
+static_assert(offsetof(AttnArgs, out) == 56 && offsetof(AttnArgs, rope_row) == 88 && offsetof(AttnArgs, v_lds) == 104 &&
+                  sizeof(AttnArgs) == 112 && alignof(AttnArgs) == 8,
+              "attn_entry reads out .. n_tok as 8 + 4 + 2 dwords");
+typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x8s __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ AttnArgs attn_entry(const float *q, const float *k, const float *v, const int32_t *pos,
+                                               const float *rope_table, uint16_t *k_cache, uint16_t *v_cache) {
+    const auto *ka = __builtin_amdgcn_kernarg_segment_ptr();
+    u32x8s r0;
+    u32x4s r1;
+    u32x2s r2;
+    asm volatile("s_load_dwordx8 %0, %3, %4\n\t"
+                 "s_load_dwordx4 %1, %3, %5\n\t"
+                 "s_load_dwordx2 %2, %3, %6\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(r0), "=&s"(r1), "=&s"(r2)
+                 : "s"(ka), "i"(kAttnArgsOff + 56), "i"(kAttnArgsOff + 88), "i"(kAttnArgsOff + 104));
+    AttnArgs a;
+    a.q = q, a.k = k, a.v = v, a.pos = pos, a.rope_table = rope_table, a.k_cache = k_cache, a.v_cache = v_cache;
+    a.out = (float *)(uintptr_t)((uint64_t)r0[0] | ((uint64_t)r0[1] << 32));
+    a.n_ctx = (int)r0[2], a.n_head = (int)r0[3], a.n_head_kv = (int)r0[4], a.head_dim = (int)r0[5];
+    a.scale = __uint_as_float(r0[6]);
+    a.diag = (int)r0[7];
+    a.rope_row = (int)r1[0], a.no_store = (int)r1[1];
+    a.q8_out = (uint8_t *)(uintptr_t)((uint64_t)r1[2] | ((uint64_t)r1[3] << 32));
+    a.v_lds = (int)r2[0], a.n_tok = (int)r2[1];
+    return a;
+}
+
 template <int HD, bool BATCH, int DS = 1, int TPH = 256, bool KD1 = false>
-__global__ void __launch_bounds__(TPH) kq_attn_decode(const AttnArgs a) {
+__global__ void __launch_bounds__(TPH) kq_attn_decode(KQ_ATTN_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const AttnArgs a = attn_entry(q, k, v, pos, rope_table, k_cache, v_cache);
     // XCD-aware head order (speed only): workgroup b runs on XCD b % 8, so XCD x takes the
     // consecutive heads [x*n_head/8, (x+1)*n_head/8) (every slice of a head on one XCD) and a
     // KV group's cells are fetched into the L2 of 8*gsz/n_head XCDs (TinyLlama: 2, Llama-3: 1)
@@ -1154,6 +1217,7 @@ int launch_attn(const AttnArgs &a, hipStream_t s) {
     // is known (all of them in flight under KQ and soft_max) where they fit; shorter caches keep
     // the register prefetch, which issues V with the position itself.
     AttnArgs b = a;
+#define KQ_ATTN_LEAD(b) (b).q, (b).k, (b).v, (b).pos, (b).rope_table, (b).k_cache, (b).v_cache, (b)
     const int ds = attn_slices(a);
     if (path == MI355X_ATTN_PATH_SPLIT4 || path == MI355X_ATTN_PATH_SPLIT8) {
         const size_t lds = attn_lds_v(a.head_dim, a.n_ctx, ds);
@@ -1162,7 +1226,7 @@ int launch_attn(const AttnArgs &a, hipStream_t s) {
     if (a.head_dim == HD && ds == DS) {                                                                    \
         allow_lds((const void *)kq_attn_decode<HD, true, DS>, lds);                                        \
         return timed_launch("kq::kq_attn_decode<" #HD ", true, " #DS ">", bytes, kq_attn_decode<HD, true, DS>, \
-                            grid, dim3(256), lds, s, b);                                                   \
+                            grid, dim3(256), lds, s, KQ_ATTN_LEAD(b));                                                   \
     }
         KQ_ATTN_SPLIT_LAUNCH(64, 4)
         KQ_ATTN_SPLIT_LAUNCH(64, 8)
@@ -1183,11 +1247,11 @@ int launch_attn(const AttnArgs &a, hipStream_t s) {
         if (a.head_dim == 64) {
             allow_lds((const void *)kq_attn_decode<64, true, 1, 256, true>, lds);
             return timed_launch("kq::kq_attn_decode<64, true, 1, kd1>", bytes, kq_attn_decode<64, true, 1, 256, true>,
-                                dim3(a.n_head), dim3(256), lds, s, b);
+                                dim3(a.n_head), dim3(256), lds, s, KQ_ATTN_LEAD(b));
         }
         allow_lds((const void *)kq_attn_decode<128, true, 1, 256, true>, lds);
         return timed_launch("kq::kq_attn_decode<128, true, 1, kd1>", bytes, kq_attn_decode<128, true, 1, 256, true>,
-                            dim3(a.n_head), dim3(256), lds, s, b);
+                            dim3(a.n_head), dim3(256), lds, s, KQ_ATTN_LEAD(b));
     }
     b.v_lds = a.n_ctx > KQ_ATTN_BATCH_CTX && a.n_ctx % 8 == 0 && attn_lds_v(a.head_dim, a.n_ctx) <= 160 * 1024 &&
               ((uintptr_t)a.v_cache & 15u) == 0 && KQ_ATTN_VLDS;
@@ -1196,14 +1260,16 @@ int launch_attn(const AttnArgs &a, hipStream_t s) {
     if (a.head_dim == 64) {
         if (!batch)
             return timed_launch("kq::kq_attn_decode<64, false>", bytes, kq_attn_decode<64, false, 1, KQ_ATTN_TPH64>,
-                                dim3(a.n_head), dim3(KQ_ATTN_TPH64), lds, s, b);
+                                dim3(a.n_head), dim3(KQ_ATTN_TPH64), lds, s, KQ_ATTN_LEAD(b));
         if (b.v_lds) allow_lds((const void *)kq_attn_decode<64, true>, lds);
-        return timed_launch("kq::kq_attn_decode<64, true>", bytes, kq_attn_decode<64, true>, dim3(a.n_head), dim3(256), lds, s, b);
+        return timed_launch("kq::kq_attn_decode<64, true>", bytes, kq_attn_decode<64, true>, dim3(a.n_head), dim3(256), lds, s, KQ_ATTN_LEAD(b));
     }
-    if (!batch) return timed_launch("kq::kq_attn_decode<128, false>", bytes, kq_attn_decode<128, false>, dim3(a.n_head), dim3(256), lds, s, b);
+    if (!batch) return timed_launch("kq::kq_attn_decode<128, false>", bytes, kq_attn_decode<128, false>, dim3(a.n_head), dim3(256), lds, s, KQ_ATTN_LEAD(b));
     if (b.v_lds) allow_lds((const void *)kq_attn_decode<128, true>, lds);
-    return timed_launch("kq::kq_attn_decode<128, true>", bytes, kq_attn_decode<128, true>, dim3(a.n_head), dim3(256), lds, s, b);
+    return timed_launch("kq::kq_attn_decode<128, true>", bytes, kq_attn_decode<128, true>, dim3(a.n_head), dim3(256), lds, s, KQ_ATTN_LEAD(b));
 }
+
+#undef KQ_ATTN_LEAD
 
 // mi355x_attn_prompt_impl: MI355X_ATTN_GROUP (default: one workgroup per kv group and token
 // where the group fits) or MI355X_ATTN_HEAD (one per query head and token)

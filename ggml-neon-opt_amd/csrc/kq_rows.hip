@@ -34,12 +34,17 @@
 #ifndef KQ_ROWS_DIAG
 #define KQ_ROWS_DIAG 0
 #endif
+// The diagnostic bits travel in the leading `cfg` parameter and the stamp buffer in the entry
+// batch (RowsHot), so a diagnostic build enters as the product does; it takes its stamps
+// whether or not a buffer is set (RSTAMP) and writes them only where one is.
 #if KQ_ROWS_DIAG
-#define RDIAG(a) ((a).diag)
-#define RSTAMPS(a) ((a).stamps)
+#define RDIAG(ld) ((ld).diag)
+#define RSTAMPS(h) ((h).stamps)
+#define RSTAMP() __builtin_amdgcn_s_memrealtime()
 #else
-#define RDIAG(a) 0
-#define RSTAMPS(a) ((uint64_t *)nullptr)
+#define RDIAG(ld) 0
+#define RSTAMPS(h) ((uint64_t *)nullptr)
+#define RSTAMP() ((uint64_t)0)
 #endif
 
 #ifndef KQ_ROWS_XMODE
@@ -219,18 +224,204 @@ int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64
     return e == hipSuccess ? MI355X_OK : (int)e;
 }
 
-template <int TYPE, bool FUSEDQ, int PRO>
-__device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww, uint8_t *smem, const RowsLayout &L,
-                                          int wave, int lane, uint64_t st0) {
+// ---------------------------------------------------------------- kernel entry
+// The leading parameters (KQ_ROWS_PARAMS, kq_common.h), in SGPRs at wave start with the
+// kernarg preload: the activation loads need nothing else.
+struct RowsLead {
+    const void *x;  // f32 activation; the Q8L row when !FUSEDQ
+    const float *x2;
+    const uint8_t *w0;
+    const float *res0;
+    int nb, waves_total, grid, nwv, qiters, n_desc, diag, rbase0, rrem0;
+};
+__device__ __forceinline__ RowsLead rows_lead(const void *x, const float *x2, const uint8_t *w0, const float *res0,
+                                              int nb, int waves_total, int grid, int cfg, int rbase0, int rrem0) {
+    RowsLead ld;
+    ld.x = x, ld.x2 = x2, ld.w0 = w0, ld.res0 = res0;
+    ld.nb = nb, ld.waves_total = waves_total, ld.grid = grid;
+    ld.nwv = cfg & 0xff, ld.qiters = (cfg >> 8) & 0xf, ld.n_desc = (cfg >> 12) & 0xf, ld.diag = (cfg >> 16) & 0x1ff;
+    ld.rbase0 = rbase0, ld.rrem0 = rrem0;
+    return ld;
+}
+
+// RowsArgs' entry run (kq_common.h: bR .. stamps_cap), fetched by hand: four wide scalar
+// loads behind ONE wait, issued where the call stands (after the activation loads). Left to
+// the compiler, kernarg loads are sunk to their first uses, one trip each behind later waits,
+// or hoisted above the activation loads with a wait of their own. The product build reads
+// 56 dwords; a diagnostic build 64 (the stamp buffer).
+typedef uint32_t u32x8s __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x16s __attribute__((ext_vector_type(16)));
+constexpr int kRowsArgsOff = 14 * 4;  // RowsArgs in the kernarg segment: after the 14 leading dwords
+static_assert(alignof(RowsArgs) == 8 && kRowsArgsOff % 8 == 0, "RowsArgs follows the leading parameters unpadded");
+#define RA_DW(f) ((int)(offsetof(RowsArgs, f) / 4))
+#if KQ_ROWS_DIAG
+typedef u32x16s rows_run_tail;
+#define KQ_ROWS_RUN_TAIL "s_load_dwordx16"
+static_assert(offsetof(RowsArgs, stamps_cap) + 8 <= 64 * 4 && sizeof(RowsArgs) >= 64 * 4, "entry run: 64 dwords");
+#else
+typedef u32x8s rows_run_tail;
+#define KQ_ROWS_RUN_TAIL "s_load_dwordx8"
+static_assert(offsetof(RowsArgs, n_rows) + 16 <= 56 * 4 && sizeof(RowsArgs) >= 56 * 4, "entry run: 56 dwords");
+#endif
+struct RowsRun {
+    u32x16s a, b, c;
+    rows_run_tail d;
+    template <int I>
+    __device__ __forceinline__ uint32_t dw() const {
+        if constexpr (I < 16) return a[I];
+        else if constexpr (I < 32) return b[I - 16];
+        else if constexpr (I < 48) return c[I - 32];
+        else return d[I - 48];
+    }
+    template <int I>
+    __device__ __forceinline__ int i32() const {
+        return (int)dw<I>();
+    }
+    template <class T, int I>
+    __device__ __forceinline__ T *ptr() const {
+        return (T *)(uintptr_t)((uint64_t)dw<I>() | ((uint64_t)dw<I + 1>() << 32));
+    }
+};
+__device__ __forceinline__ RowsRun rows_fetch() {
+    const auto *ka = __builtin_amdgcn_kernarg_segment_ptr();
+    RowsRun r;
+    asm volatile("s_load_dwordx16 %0, %4, %5\n\t"
+                 "s_load_dwordx16 %1, %4, %6\n\t"
+                 "s_load_dwordx16 %2, %4, %7\n\t" KQ_ROWS_RUN_TAIL " %3, %4, %8\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(r.a), "=&s"(r.b), "=&s"(r.c), "=&s"(r.d)
+                 : "s"(ka), "i"(kRowsArgsOff), "i"(kRowsArgsOff + 64), "i"(kRowsArgsOff + 128), "i"(kRowsArgsOff + 192));
+    return r;
+}
+
+// A value of the run in scalar registers of its own from here on: picking among elements of
+// one loaded vector by a run-time index would otherwise become an indexed read of the vector
+// (through scratch).
+template <class T>
+__device__ __forceinline__ T sreg(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+// Everything else a wave of kq_rows needs, resolved for its matrix m.
+struct RowsHot {
+    int m, r0, nrows;  // this wave's matrix and rows [r0, r0 + nrows)
+    int type, bR, rpw;
+    const uint8_t *w;
+    const float *res;
+    float *y;
+    float eps;
+    int epi, epi_n, epi_wave_off;
+    float *epi_y;
+    uint64_t *stamps;
+    int64_t stamps_cap;
+};
+
+// The entry run, then this wave's matrix, picked from the loaded arrays with scalar selects:
+// with one matrix (o-proj, down, the head) the leading parameters hold its values and nothing
+// is searched or picked.
+template <int TMASK>
+__device__ __forceinline__ RowsHot rows_resolve(const RowsLead &ld, int gw) {
+    const RowsRun r = rows_fetch();
+    RowsHot h;
+    h.bR = r.i32<RA_DW(bR)>(), h.rpw = r.i32<RA_DW(rpw)>();
+    h.epi = r.i32<RA_DW(epi)>(), h.epi_n = r.i32<RA_DW(epi_n)>(), h.epi_wave_off = r.i32<RA_DW(epi_wave_off)>();
+    h.eps = __uint_as_float(r.dw<RA_DW(eps)>());
+    h.epi_y = r.ptr<float, RA_DW(epi_y)>();
+#if KQ_ROWS_DIAG
+    h.stamps = r.ptr<uint64_t, RA_DW(stamps)>();
+    h.stamps_cap = (int64_t)(uintptr_t)r.ptr<uint8_t, RA_DW(stamps_cap)>();
+#else
+    h.stamps = nullptr, h.stamps_cap = 0;
+#endif
+    h.m = 0, h.w = ld.w0, h.res = ld.res0;
+    h.type = TMASK == 7 ? sreg(r.i32<RA_DW(type)>()) : 0;
+    h.y = sreg(r.ptr<float, RA_DW(y)>());
+    int j = gw, base = ld.rbase0, rem = ld.rrem0;
+    if (ld.n_desc > 1) {  // uniform over the launch
+        const int p1 = sreg(r.i32<RA_DW(wave_prefix) + 1>()), p2 = sreg(r.i32<RA_DW(wave_prefix) + 2>()),
+                  p3 = sreg(r.i32<RA_DW(wave_prefix) + 3>());
+        const int b1 = sreg(r.i32<RA_DW(rbase) + 1>()), b2 = sreg(r.i32<RA_DW(rbase) + 2>()), b3 = sreg(r.i32<RA_DW(rbase) + 3>());
+        const int e1 = sreg(r.i32<RA_DW(rrem) + 1>()), e2 = sreg(r.i32<RA_DW(rrem) + 2>()), e3 = sreg(r.i32<RA_DW(rrem) + 3>());
+        const uint8_t *w1 = sreg(r.ptr<const uint8_t, RA_DW(w) + 2>()), *w2 = sreg(r.ptr<const uint8_t, RA_DW(w) + 4>()),
+                      *w3 = sreg(r.ptr<const uint8_t, RA_DW(w) + 6>());
+        const float *s1 = sreg(r.ptr<const float, RA_DW(res) + 2>()), *s2 = sreg(r.ptr<const float, RA_DW(res) + 4>()),
+                    *s3 = sreg(r.ptr<const float, RA_DW(res) + 6>());
+        float *y1 = sreg(r.ptr<float, RA_DW(y) + 2>()), *y2 = sreg(r.ptr<float, RA_DW(y) + 4>()), *y3 = sreg(r.ptr<float, RA_DW(y) + 6>());
+        int m = gw >= p1 ? 1 : 0;
+        if (ld.n_desc > 2 && gw >= p2) m = 2;
+        if (ld.n_desc > 3 && gw >= p3) m = 3;
+        h.m = m;
+        j = gw - (m == 0 ? 0 : m == 1 ? p1 : m == 2 ? p2 : p3);
+        base = m == 0 ? base : m == 1 ? b1 : m == 2 ? b2 : b3;
+        rem = m == 0 ? rem : m == 1 ? e1 : m == 2 ? e2 : e3;
+        if (TMASK == 7) {
+            const int t1 = sreg(r.i32<RA_DW(type) + 1>()), t2 = sreg(r.i32<RA_DW(type) + 2>()), t3 = sreg(r.i32<RA_DW(type) + 3>());
+            h.type = m == 0 ? h.type : m == 1 ? t1 : m == 2 ? t2 : t3;
+        }
+        h.w = m == 0 ? h.w : m == 1 ? w1 : m == 2 ? w2 : w3;
+        h.res = m == 0 ? h.res : m == 1 ? s1 : m == 2 ? s2 : s3;
+        h.y = m == 0 ? h.y : m == 1 ? y1 : m == 2 ? y2 : y3;
+    }
+    h.r0 = j * base + (j < rem ? j : rem);
+    h.nrows = gw < ld.waves_total ? base + (j < rem ? 1 : 0) : 0;
+    return h;
+}
+
+// `resolve` returns the wave's RowsHot: called after the activation loads are issued (they
+// need the leading parameters only), or before the call where the type depends on the matrix.
+template <int TYPE, bool FUSEDQ, int PRO, int TMASK, class Resolve>
+__device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
+                                          uint64_t st0, Resolve resolve) {
     constexpr int BSZ = block_bytes(TYPE);
     constexpr int GRAN = rows_gran(TYPE);
     constexpr int NI = rows_ni(TYPE);
     constexpr int SLOT = rows_slot(TYPE);
     constexpr int D = rows_depth(TYPE);
     static_assert(D >= 2 && D <= 4, "vm_wait_k covers 3 steps in flight");
-    const int nb = a.nb, bR = a.bR;
-    const int nwv = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));  // waves in this workgroup
+    const int nb = ld.nb;
+    const int nwv = ld.nwv;  // waves in this workgroup
     const int q = lane >> 2, s = lane & 3;
+
+    // ---- activation loads first: every wave's requests leave before any argument fetch
+    const int PASS = 4 * nwv;  // superblocks per workgroup pass
+    // KQ_ROWS_XMODE >= 0: the prologue fixed at compile time (experiment builds)
+    const int xm = !FUSEDQ ? 0 : KQ_ROWS_XMODE >= 0 ? KQ_ROWS_XMODE : a.xmode;
+    u32x4 xv[ROWS_QPASS][4] = {};
+    u32x4 x2v[ROWS_QPASS][4] = {};  // norm weight / up, same elements as xv
+    // passes this wave loads (wave-uniform): pass i while slot 4*wave of it lies in the row
+    int qw = 0;
+    // slot j of the passes -> superblock: rotated by the workgroup (ROWS_X_ROT) so the
+    // grid does not read the activation's lines in one order; slots past the row read
+    // superblock nb-1's place and store nothing
+    const int rot = (xm & ROWS_X_ROT) ? (int)(blockIdx.x % (unsigned)nb) : 0;
+    auto sbk = [&](int j) {
+        int b = (j < nb ? j : nb - 1) + rot;
+        return b >= nb ? b - nb : b;
+    };
+    if (FUSEDQ) {
+        const float *const x = (const float *)ld.x;
+#pragma unroll
+        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < ld.qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < ROWS_QPASS; ++i) {
+            if (i < qw) {  // waves past the row load nothing
+                const int b = sbk(PASS * i + 4 * wave + (lane >> 4));
+                const float *xp = x + (int64_t)b * QK + 16 * (lane & 15);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
+                if (PRO != ROWS_PRO_NONE) {  // (diag bit 4: read x again instead of x2, timing only)
+                    const float *x2p = ((RDIAG(ld) & 16) ? x : ld.x2) + (int64_t)b * QK + 16 * (lane & 15);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
+                }
+            }
+        }
+    }
+    const RowsHot h = resolve();
+    const uint64_t sa = RSTAMP();  // diagnostics: arguments fetched
+    const int bR = h.bR;
+    const RowsLayout L = rows_layout(nb, TMASK, bR, h.rpw, nwv);
     uint8_t *const ring = smem + L.ring + wave * L.ring_stride;
     uint8_t *const ring_end = ring + D * SLOT;
     Rec *const recs = (Rec *)(smem + L.recs + wave * L.recs_stride);
@@ -238,9 +429,9 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
     const uint8_t *const actq = smem + L.act;
 
     // weight stream of this wave
-    const int G = ww.nrows * nb;               // superblocks
+    const int G = h.nrows * nb;               // superblocks
     const int T = (G + ROWS_SB - 1) / ROWS_SB;  // steps
-    const uint8_t *src = a.w[ww.m] + (int64_t)ww.r0 * nb * BSZ;
+    const uint8_t *src = h.w + (int64_t)h.r0 * nb * BSZ;
     const uint32_t mis = (uint32_t)((uintptr_t)src & 15u);
     const uint8_t *s16 = src - mis;
     const uint8_t *last16 =
@@ -269,7 +460,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
         ++it_;
     };
 
-    const float *const res_p = a.res[ww.m];
+    const float *const res_p = h.res;
     uint32_t rv = 0;  // residual of the fused ADD for row r0 + lane (first 64 rows)
 
     // ---- prologue: activation loads, pre0 weight steps, quantize, then the rest of the ring
@@ -279,47 +470,16 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
     const int pre0 = T >= pre_cap ? pre_cap : (T > 0 ? T : 0);
     uint64_t sx = 0, sq = 0, sf = 0;  // diagnostics: x landed, quantized, first step computed
     if (FUSEDQ) {
-        const int PASS = 4 * nwv;  // superblocks per workgroup pass
-        // KQ_ROWS_XMODE >= 0: the prologue fixed at compile time (experiment builds)
-        const int xm = KQ_ROWS_XMODE >= 0 ? KQ_ROWS_XMODE : a.xmode;
-        u32x4 xv[ROWS_QPASS][4] = {};
-        u32x4 x2v[ROWS_QPASS][4] = {};  // norm weight / up, same elements as xv
-        const int qiters = (nb + PASS - 1) / PASS;
-        // passes this wave loads (wave-uniform): pass i while slot 4*wave of it lies in the row
-        int qw = 0;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
-        // slot j of the passes -> superblock: rotated by the workgroup (ROWS_X_ROT) so the
-        // grid does not read the activation's lines in one order; slots past the row read
-        // superblock nb-1's place and store nothing
-        const int rot = (xm & ROWS_X_ROT) ? (int)(blockIdx.x % (unsigned)nb) : 0;
-        auto sbk = [&](int j) {
-            int b = (j < nb ? j : nb - 1) + rot;
-            return b >= nb ? b - nb : b;
-        };
+        const float *const x = (const float *)ld.x;
         constexpr int pro = PRO;
         constexpr int PL = PRO != ROWS_PRO_NONE ? 8 : 4;  // loads per pass
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) {
-            if (i < qw) {  // waves past the row load nothing
-                const int b = sbk(PASS * i + 4 * wave + (lane >> 4));
-                const float *xp = a.x + (int64_t)b * QK + 16 * (lane & 15);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
-                if (PRO != ROWS_PRO_NONE) {  // (diag bit 4: read x again instead of x2, timing only)
-                    const float *x2p = ((RDIAG(a) & 16) ? a.x : a.x2) + (int64_t)b * QK + 16 * (lane & 15);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
-                }
-            }
-        }
         // residual of the fused ADD: one row per lane, fetched with the activation. Issued
         // on every path (a dummy read of x without a residual) so that no branch joins a
         // register whose asm load is still in flight; rv stays live until the flush waits
         // for it (the res_p branch is a run-time condition). An asm load whose register the
         // compiler sees dead is reused while the load is in flight: a build with that branch
         // compiled out faulted (profiles/r02_attn_epilogue_rejected.md).
-        rv = gload4_asm(res_p && ww.nrows > 0 ? res_p + ww.r0 + (lane < ww.nrows ? lane : 0) : a.x);
+        rv = gload4_asm(res_p && h.nrows > 0 ? res_p + h.r0 + (lane < h.nrows ? lane : 0) : x);
         // ROWS_X_BAR: every wave's activation requests are queued before any weight DMA of
         // the workgroup (uniform: every wave of the workgroup runs the prologue)
         if (xm & ROWS_X_BAR) asm volatile("s_barrier" ::: "memory");
@@ -329,7 +489,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
         // wait below covers the activation loads on every path (tools/vmem_lint.py).
         constexpr bool kConstPre = KQ_ROWS_PRE0 == 1 && KQ_ROWS_L2PF == 0;
         if (kConstPre && T == 0) {
-            const uint8_t *xb = (const uint8_t *)a.x + 16 * lane;
+            const uint8_t *xb = (const uint8_t *)x + 16 * lane;
 #pragma unroll
             for (int i = 0; i < NI; ++i)
                 if (KQ_ROWS_MASKED && i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, GRAN - 64 * (NI - 1));
@@ -375,15 +535,15 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
                 if (i < qw) {
                     vm_wait_dyn((qw - 1 - i) * PL + tail);
                     pin();
-                    if (pro == ROWS_PRO_SWIGLU && !(RDIAG(a) & 32)) {  // ggml_vec_swiglu_f32: silu(gate) * up
+                    if (pro == ROWS_PRO_SWIGLU && !(RDIAG(ld) & 32)) {  // ggml_vec_swiglu_f32: silu(gate) * up
 #pragma unroll
                         for (int k = 0; k < 4; ++k) xv[i][k] = swiglu4(xv[i][k], x2v[i][k]);
                     }
                     const int j = PASS * i + 4 * wave + (lane >> 4);
-                    if (j < nb && !(RDIAG(a) & 64)) quant16_store(xv[i], lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));
+                    if (j < nb && !(RDIAG(ld) & 64)) quant16_store(xv[i], lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));
                 }
             }
-            if (RSTAMPS(a)) sx = sq = __builtin_amdgcn_s_memrealtime();
+            if (RSTAMPS(h)) sx = sq = __builtin_amdgcn_s_memrealtime();
         } else {
             // every pass landed: all but the pre0 weight steps (and prefetch touches); with
             // compile-time pre0 / prefetch a constant per path
@@ -399,7 +559,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
                 vm_wait_dyn(tail);
             }
             pin();
-            if (RDIAG(a) & 32) {  // diagnostics (timing only): skip the transform
+            if (RDIAG(ld) & 32) {  // diagnostics (timing only): skip the transform
             } else if (pro == ROWS_PRO_SWIGLU) {  // ggml_vec_swiglu_f32: silu(gate) * up
 #pragma unroll
                 for (int i = 0; i < ROWS_QPASS; ++i)
@@ -431,25 +591,25 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
                 // workgroup-uniform (every wave sums the same LDS values): the rare rows whose
                 // float mean could depend on the order are summed in ggml's order (each wave)
                 if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
-                    tot = seq_sumsq_wave(a.x, (int64_t)nb * QK, lane);
+                    tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
                 const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
-                const float scale = 1.0f / sqrtf(mean + a.eps);
+                const float scale = 1.0f / sqrtf(mean + h.eps);
 #pragma unroll
                 for (int i = 0; i < ROWS_QPASS; ++i)
                     if (i < qw)
 #pragma unroll
                         for (int k = 0; k < 4; ++k) xv[i][k] = normmul4(xv[i][k], x2v[i][k], scale);
             }
-            if (RSTAMPS(a)) sx = __builtin_amdgcn_s_memrealtime();
+            if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
 #pragma unroll 1
             for (int i = 0; i < qw; ++i) {  // one copy of the quantizer; pick the pass's registers
                 u32x4 cur[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) cur[k] = i == 0 ? xv[0][k] : i == 1 ? xv[1][k] : xv[2][k];
                 const int j = PASS * i + 4 * wave + (lane >> 4);
-                if (j < nb && !(RDIAG(a) & 64)) quant16_store(cur, lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));  // (diag 64: timing only)
+                if (j < nb && !(RDIAG(ld) & 64)) quant16_store(cur, lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));  // (diag 64: timing only)
             }
-            if (RSTAMPS(a)) {
+            if (RSTAMPS(h)) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 sq = __builtin_amdgcn_s_memrealtime();
             }
@@ -458,14 +618,14 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
         const int ng = nb * (Q8L_STRIDE / 16);
         for (int j = wave; 64 * j < ng; j += nwv) {
             const int k = 64 * j + lane;
-            if (k < ng) dma16(a.xq + 16 * k, (LDS void *)(smem + L.act + 1024 * j));
+            if (k < ng) dma16((const uint8_t *)ld.x + 16 * k, (LDS void *)(smem + L.act + 1024 * j));
         }
         for (int j = 0; j < pre0; ++j) issue();
         vm_wait_k<NI>(pre0);
     }
     while (it_ < D && it_ < T) issue();
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // Q8_K row complete (no vmcnt drain)
-    const uint64_t st1 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const uint64_t st1 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
 
     // ---- main loop
     int io = q, rr = 0;  // quad's (block, row-in-batch) of superblock 16t+q
@@ -499,7 +659,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
         } else {
             vm_wait_k<NI>(T - t - 1);
         }
-        if (!(RDIAG(a) & 8) && ROWS_SB * t + q < G) {
+        if (!(RDIAG(ld) & 8) && ROWS_SB * t + q < G) {
             const uint8_t *blk = cslot + mis + q * BSZ;
             const uint8_t *ab = actq + io * Q8L_STRIDE;
             QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
@@ -536,10 +696,10 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
             }
         }
         if (it_ < T) issue();
-        if (RSTAMPS(a) && t == 0) sf = __builtin_amdgcn_s_memrealtime();
+        if (RSTAMPS(h) && t == 0) sf = __builtin_amdgcn_s_memrealtime();
         if (ROWS_SB * (t + 1) >= bend) {  // batch complete: replay its rows' chains, lane r <-> row r
             wave_lds_fence();
-            const int nr = bR < ww.nrows - brow ? bR : ww.nrows - brow;
+            const int nr = bR < h.nrows - brow ? bR : h.nrows - brow;
             if (lane < nr) {
                 float v = 0.f;
                 const Rec *rc = recs + lane;
@@ -554,92 +714,84 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const WaveWork &ww,
         }
     }
     if (KQ_ROWS_PRIO) __builtin_amdgcn_s_setprio(0);
-    const uint64_t st2 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const uint64_t st2 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
     if (pf_on) {  // every touch has landed (they are older than step pre0): release the register
         asm volatile("" ::"v"(pf_sink));
     }
 
     // ---- flush staged results (coalesced)
-    if (ww.nrows > 0) {
+    if (h.nrows > 0) {
         wave_lds_fence();
-        float *y = a.y[ww.m] + ww.r0;
+        float *y = h.y + h.r0;
         if (res_p) {  // ggml_add(mul_mat, residual): the same single f32 add per element
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("" : "+v"(rv));
-            for (int k = 0; k < ww.nrows; k += 64)
-                if (k + lane < ww.nrows)
-                    store_y(y + k + lane, outs[k + lane] + (k == 0 ? __uint_as_float(rv) : res_p[ww.r0 + k + lane]));
+            for (int k = 0; k < h.nrows; k += 64)
+                if (k + lane < h.nrows)
+                    store_y(y + k + lane, outs[k + lane] + (k == 0 ? __uint_as_float(rv) : res_p[h.r0 + k + lane]));
         } else {
-            for (int k = 0; k < ww.nrows; k += 64)
-                if (k + lane < ww.nrows) store_y(y + k + lane, outs[k + lane]);
+            for (int k = 0; k < h.nrows; k += 64)
+                if (k + lane < h.nrows) store_y(y + k + lane, outs[k + lane]);
         }
     }
     // ---- SWIGLU epilogue (the GLU node after the gate/up MUL_MATs): up wave and its
     // gate partner own the same rows in this workgroup; both results are staged in LDS.
     // Same arithmetic as kq_swiglu (ggml_vec_swiglu_f32: NEON body, libm tail).
-    if (a.epi && !(RDIAG(a) & 128)) {  // uniform over the grid: every wave of the workgroup reaches the barrier (diag 128: timing only)
+    if (h.epi && !(RDIAG(ld) & 128)) {  // uniform over the grid: every wave of the workgroup reaches the barrier (diag 128: timing only)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (ww.m == 1 && ww.nrows > 0) {
-            const float *gouts = (const float *)(smem + L.outs + (wave - a.epi_wave_off) * L.outs_stride);
-            const int n4 = a.epi_n & ~3;
-            for (int k = 0; k < ww.nrows; k += 64)
-                if (k + lane < ww.nrows) {
-                    const int r = ww.r0 + k + lane;
+        if (h.m == 1 && h.nrows > 0) {
+            const float *gouts = (const float *)(smem + L.outs + (wave - h.epi_wave_off) * L.outs_stride);
+            const int n4 = h.epi_n & ~3;
+            for (int k = 0; k < h.nrows; k += 64)
+                if (k + lane < h.nrows) {
+                    const int r = h.r0 + k + lane;
                     const float gv = gouts[k + lane], uv = outs[k + lane];
-                    store_y(a.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+                    store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
                 }
         }
     }
-    if (RSTAMPS(a)) {
+    if (RSTAMPS(h)) {
         const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * 8;  // stamp slots sized for the most waves
-        if (lane == 0 && o + 7 < a.stamps_cap) {
-            RSTAMPS(a)[o] = st0;
-            RSTAMPS(a)[o + 1] = st1;
-            RSTAMPS(a)[o + 2] = st2;
-            RSTAMPS(a)[o + 3] = __builtin_amdgcn_s_memrealtime();
-            RSTAMPS(a)[o + 4] = sx;
-            RSTAMPS(a)[o + 5] = sq;
-            RSTAMPS(a)[o + 6] = sf;
+        if (lane == 0 && o + 7 < h.stamps_cap) {
+            RSTAMPS(h)[o] = st0;
+            RSTAMPS(h)[o + 1] = st1;
+            RSTAMPS(h)[o + 2] = st2;
+            RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
+            RSTAMPS(h)[o + 4] = sx;
+            RSTAMPS(h)[o + 5] = sq;
+            RSTAMPS(h)[o + 6] = sf;
+            RSTAMPS(h)[o + 7] = sa;
         }
     }
 }
 
 template <int TMASK, bool FUSEDQ, int PRO>
-__global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(const RowsArgs a) {
+__global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (RDIAG(a) & 256) return;  // diagnostics (timing only): empty launch
-    const uint64_t st0 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const RowsLead ld = rows_lead(x, x2, w0, res0, nb, waves_total, grid, cfg, rbase0, rrem0);
+    if (RDIAG(ld) & 256) return;  // diagnostics (timing only): empty launch
+    const uint64_t st0 = RSTAMP();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const RowsLayout L = rows_layout(a.nb, TMASK, a.bR, a.rpw, __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)));
-
-    const int gw = wave * gridDim.x + blockIdx.x;  // active waves spread over every CU
-    WaveWork ww;
-    int m = 0;
-#pragma unroll
-    for (int i = 1; i < MI355X_MAX_FUSED; ++i)
-        if (i < a.n_desc && gw >= a.wave_prefix[i]) m = i;
-    ww.m = m;
-    const int j = gw - a.wave_prefix[m];
-    const int base = a.rbase[m], rem = a.rrem[m];
-    ww.r0 = j * base + (j < rem ? j : rem);
-    ww.nrows = gw < a.waves_total ? base + (j < rem ? 1 : 0) : 0;
+    const int gw = wave * ld.grid + blockIdx.x;  // active waves spread over every CU
+    auto resolve = [&]() { return rows_resolve<TMASK>(ld, gw); };
 
     if (TMASK == 1) {
-        rows_body<Q4_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
+        rows_body<Q4_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 2) {
-        rows_body<Q5_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
+        rows_body<Q5_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 4) {
-        rows_body<Q6_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
-    } else {
-        const int type = a.type[m];
-        if (type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
-        else if (type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
-        else rows_body<Q4_K, FUSEDQ, PRO>(a, ww, smem, L, wave, lane, st0);
+        rows_body<Q6_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
+    } else {  // the type is the matrix's: the entry batch first
+        const RowsHot h = resolve();
+        auto resolved = [&]() { return h; };
+        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
+        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
+        else rows_body<Q4_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
     }
 }
 
-#define KQ_ROWS_INST(TM, FQ, PR) template __global__ void kq_rows<TM, FQ, PR>(const RowsArgs a);
+#define KQ_ROWS_INST(TM, FQ, PR) template __global__ void kq_rows<TM, FQ, PR>(KQ_ROWS_PARAMS);
 #define KQ_ROWS_INST_T(TM)        \
     KQ_ROWS_INST(TM, true, 0)     \
     KQ_ROWS_INST(TM, true, 1)     \
@@ -678,9 +830,42 @@ struct DynUnit {
 // workgroup row range [r0, r0 + nr) serves them all: unit u is matrix u / nu's rows
 // [r0 + (u % nu) U, ...), flat output index m * nr + local row. Records of consecutive
 // units go into one batch of bR rows, replayed together (lane r <-> batch row r).
-template <int TYPE, bool FUSEDQ, int PRO>
-__device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, const RowsDynLayout &L, int wave,
-                                              int lane, uint64_t st0) {
+// kq_rows_dyn's entry batch: every matrix's pointers stay (a wave takes units of all of them).
+struct RowsDynHot {
+    int bR, rpw, U, P, ush, N, epi, epi_n;
+    const uint8_t *w1, *w2, *w3;
+    const float *s1, *s2, *s3;
+    float *y0, *y1, *y2, *y3, *epi_y;
+    float eps;
+    uint64_t *stamps;
+    int64_t stamps_cap;
+};
+__device__ __forceinline__ RowsDynHot rows_dyn_resolve() {
+    const RowsRun r = rows_fetch();
+    RowsDynHot h;
+    h.bR = r.i32<RA_DW(bR)>(), h.rpw = r.i32<RA_DW(rpw)>();
+    h.U = r.i32<RA_DW(dyn_u)>(), h.P = r.i32<RA_DW(dyn_p)>(), h.ush = r.i32<RA_DW(dyn_ush)>(), h.N = r.i32<RA_DW(n_rows)>();
+    h.epi = r.i32<RA_DW(epi)>(), h.epi_n = r.i32<RA_DW(epi_n)>();
+    h.epi_y = r.ptr<float, RA_DW(epi_y)>();
+    h.eps = __uint_as_float(r.dw<RA_DW(eps)>());
+    h.w1 = sreg(r.ptr<const uint8_t, RA_DW(w) + 2>()), h.w2 = sreg(r.ptr<const uint8_t, RA_DW(w) + 4>());
+    h.w3 = sreg(r.ptr<const uint8_t, RA_DW(w) + 6>());
+    h.s1 = sreg(r.ptr<const float, RA_DW(res) + 2>()), h.s2 = sreg(r.ptr<const float, RA_DW(res) + 4>());
+    h.s3 = sreg(r.ptr<const float, RA_DW(res) + 6>());
+    h.y0 = sreg(r.ptr<float, RA_DW(y)>()), h.y1 = sreg(r.ptr<float, RA_DW(y) + 2>());
+    h.y2 = sreg(r.ptr<float, RA_DW(y) + 4>()), h.y3 = sreg(r.ptr<float, RA_DW(y) + 6>());
+#if KQ_ROWS_DIAG
+    h.stamps = r.ptr<uint64_t, RA_DW(stamps)>();
+    h.stamps_cap = (int64_t)(uintptr_t)r.ptr<uint8_t, RA_DW(stamps_cap)>();
+#else
+    h.stamps = nullptr, h.stamps_cap = 0;
+#endif
+    return h;
+}
+
+template <int TYPE, bool FUSEDQ, int PRO, int TMASK>
+__device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
+                                              uint64_t st0) {
     uint64_t sx = 0, sq = 0, sf = 0;  // diagnostics (KQ_ROWS_DIAG builds): x landed, quantized, first step
     constexpr int BSZ = block_bytes(TYPE);
     constexpr int GRAN = rows_gran(TYPE);
@@ -688,10 +873,43 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
     constexpr int SLOT = rows_slot(TYPE);
     constexpr int D = rows_depth(TYPE);
     static_assert(D >= 2 && D <= 4, "vm_wait_k covers 3 steps in flight");
-    const int nb = a.nb, U = a.dyn_u, P = a.dyn_p, bR = a.bR;
-    const int nwv = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));
+    const int nb = ld.nb;
+    const int nwv = ld.nwv;
     const int b = (int)blockIdx.x;
     const int q = lane >> 2, s = lane & 3;
+
+    // ---- activation loads first (the leading parameters only), then the entry batch
+    const float *const x = (const float *)ld.x;
+    const int PASS = 4 * nwv;
+    u32x4 xv[ROWS_QPASS][4] = {};
+    u32x4 x2v[ROWS_QPASS][4] = {};
+    int qw = 0;
+    if (FUSEDQ) {
+#pragma unroll
+        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < ld.qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < ROWS_QPASS; ++i) {
+            if (i < qw) {
+                const int j = PASS * i + 4 * wave + (lane >> 4);
+                const int bb = j < nb ? j : nb - 1;
+                const float *xp = x + (int64_t)bb * QK + 16 * (lane & 15);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
+                if (PRO != ROWS_PRO_NONE) {
+                    const float *x2p = ld.x2 + (int64_t)bb * QK + 16 * (lane & 15);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
+                }
+            }
+        }
+    }
+    const RowsDynHot h = rows_dyn_resolve();
+    // (scalars of their own: a pick among struct members becomes a pick of addresses, in scratch)
+    const uint8_t *const w0 = ld.w0, *const w1 = h.w1, *const w2 = h.w2, *const w3 = h.w3;
+    const float *const s0 = ld.res0, *const s1 = h.s1, *const s2 = h.s2, *const s3 = h.s3;
+    float *const y0 = h.y0, *const y1 = h.y1, *const y2 = h.y2, *const y3 = h.y3;
+    const int U = h.U, P = h.P, bR = h.bR;
+    const RowsDynLayout L = rows_dyn_layout(nb, TMASK, bR, h.rpw, nwv);
     uint8_t *const ring = smem + L.ring + wave * L.ring_stride;
     uint8_t *const ring_end = ring + D * SLOT;
     Rec *const recs = (Rec *)(smem + L.recs + wave * L.recs_stride);
@@ -700,14 +918,14 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
     const uint8_t *const actq = smem + L.act;
 
     // ---- the workgroup's rows and units: rows [r0, r0 + nr) of every matrix (the host's
-    // N / G split, a.rbase[0] / a.rrem[0]); unit u = matrix u / nu, rows r0 + (u % nu) U ..
-    const int N = a.n_rows[0];
-    const int ush = a.dyn_ush;  // U = 1 << ush
-    const int rbase = a.rbase[0], rrem = a.rrem[0];
+    // N / G split, rbase[0] / rrem[0]); unit u = matrix u / nu, rows r0 + (u % nu) U ..
+    const int N = h.N;
+    const int ush = h.ush;  // U = 1 << ush
+    const int rbase = ld.rbase0, rrem = ld.rrem0;
     const int r0 = b * rbase + (b < rrem ? b : rrem);
     const int nr = rbase + (b < rrem ? 1 : 0);
     const int nu = (nr + U - 1) >> ush;
-    const int units = a.n_desc * nu, nflat = a.n_desc * nr;
+    const int units = ld.n_desc * nu, nflat = ld.n_desc * nr;
     const int64_t rowb = (int64_t)nb * BSZ;
     auto row_of = [&](int f) { return r0 + f; };
     // unit u's stream (its first byte), rows and flat output index: computed once, when the
@@ -718,7 +936,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
         const int lr = (u - m * nu) << ush;
         d.rows = nr - lr < U ? nr - lr : U;
         d.flat = m * nr + lr;
-        const uint8_t *w = m == 0 ? a.w[0] : m == 1 ? a.w[1] : m == 2 ? a.w[2] : a.w[3];
+        const uint8_t *w = m == 0 ? w0 : m == 1 ? w1 : m == 2 ? w2 : w3;
         d.src = w + (int64_t)(r0 + lr) * rowb;
         d.G = d.rows * nb;
         d.T = (d.G + ROWS_SB - 1) / ROWS_SB;
@@ -794,38 +1012,16 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
     // (issued on every path: a dummy read of x without one; kept live until the flush waits)
     const int f0 = 64 * wave + lane;
     const int fm = (f0 >= nr ? 1 : 0) + (f0 >= 2 * nr ? 1 : 0) + (f0 >= 3 * nr ? 1 : 0);
-    const float *fres = fm == 0 ? a.res[0] : fm == 1 ? a.res[1] : fm == 2 ? a.res[2] : a.res[3];
+    const float *fres = fm == 0 ? s0 : fm == 1 ? s1 : fm == 2 ? s2 : s3;
     const int frow = row_of(f0 - fm * nr);
     uint32_t rv = 0;
 
     // ---- prologue (the product kq_rows prologue: one step before the activation wait)
     if (FUSEDQ) {
-        const int PASS = 4 * nwv;
-        u32x4 xv[ROWS_QPASS][4] = {};
-        u32x4 x2v[ROWS_QPASS][4] = {};
-        const int qiters = (nb + PASS - 1) / PASS;
-        int qw = 0;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) {
-            if (i < qw) {
-                const int j = PASS * i + 4 * wave + (lane >> 4);
-                const int bb = j < nb ? j : nb - 1;
-                const float *xp = a.x + (int64_t)bb * QK + 16 * (lane & 15);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
-                if (PRO != ROWS_PRO_NONE) {
-                    const float *x2p = a.x2 + (int64_t)bb * QK + 16 * (lane & 15);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
-                }
-            }
-        }
-        rv = gload4_asm(fres && f0 < nflat && frow < N ? fres + frow : a.x);
+        rv = gload4_asm(fres && f0 < nflat && frow < N ? fres + frow : x);
         // exactly one step's NI DMA instructions on every path (the constant wait below)
         if (ki < 0) {  // no unit: from the activation, into a slot never read
-            const uint8_t *xb = (const uint8_t *)a.x + 16 * lane;
+            const uint8_t *xb = (const uint8_t *)x + 16 * lane;
 #pragma unroll
             for (int i = 0; i < NI; ++i)
                 if (i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, GRAN - 64 * (NI - 1));
@@ -845,7 +1041,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
             if (is == iT) next_unit(false);
         }
         vm_wait<NI + 1>();  // x landed; the residual load and the step's DMAs may be in flight
-        if (RSTAMPS(a)) sx = __builtin_amdgcn_s_memrealtime();
+        if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
         asm volatile("" : "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[1][0]),
                      "+v"(xv[1][1]), "+v"(xv[1][2]), "+v"(xv[1][3]), "+v"(xv[2][0]), "+v"(xv[2][1]),
                      "+v"(xv[2][2]), "+v"(xv[2][3]));
@@ -884,9 +1080,9 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             double tot = seq_sum_lanes(sums, nb, lane);
             if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
-                tot = seq_sumsq_wave(a.x, (int64_t)nb * QK, lane);
+                tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
             const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
-            const float scale = 1.0f / sqrtf(mean + a.eps);
+            const float scale = 1.0f / sqrtf(mean + h.eps);
 #pragma unroll
             for (int i = 0; i < ROWS_QPASS; ++i)
                 if (i < qw)
@@ -901,7 +1097,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
             const int j = PASS * i + 4 * wave + (lane >> 4);
             if (j < nb) quant16_store(cur, lane & 15, smem + L.act + Q8L_STRIDE * j);
         }
-        if (RSTAMPS(a)) {
+        if (RSTAMPS(h)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             sq = __builtin_amdgcn_s_memrealtime();
         }
@@ -909,9 +1105,9 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
         const int ng = nb * (Q8L_STRIDE / 16);
         for (int j = wave; 64 * j < ng; j += nwv) {
             const int k = 64 * j + lane;
-            if (k < ng) dma16(a.xq + 16 * k, (LDS void *)(smem + L.act + 1024 * j));
+            if (k < ng) dma16((const uint8_t *)ld.x + 16 * k, (LDS void *)(smem + L.act + 1024 * j));
         }
-        rv = gload4_asm(fres && f0 < nflat && frow < N ? fres + frow : (const float *)a.xq);
+        rv = gload4_asm(fres && f0 < nflat && frow < N ? fres + frow : (const float *)ld.x);
         if (!idone && !iwait && ki >= 0) issue(false);
         vm_wait_k<NI>(issued);
     }
@@ -920,7 +1116,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // Q8_K row complete, counter set
     if (iwait) next_unit(true);
     while (!idone && ki >= 0 && issued < D) issue(true);
-    const uint64_t st1 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const uint64_t st1 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
 
     // ---- main loop: the oldest step in flight, then one more issued
     int kc = 0, cs = 0, cT = 0, cG = 0, cmis = 0, crows = 0, io = 0, rr = 0;
@@ -987,7 +1183,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
         ++consumed;
         ++cs;
         if (!idone) issue(true);
-        if (RSTAMPS(a) && consumed == 1) sf = __builtin_amdgcn_s_memrealtime();
+        if (RSTAMPS(h) && consumed == 1) sf = __builtin_amdgcn_s_memrealtime();
         if (cs == cT) {  // the unit's last step: into the batch; replay when the next unit may not fit
             bro += crows;
             if (bro + U > bR || consumed == issued) replay();
@@ -1002,7 +1198,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
         }
     }
 
-    const uint64_t st2 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const uint64_t st2 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
     // ---- flush: the workgroup's rows, coalesced, with the residual ADD / SWIGLU epilogue
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" : "+v"(rv));
@@ -1011,48 +1207,47 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, uint8_t *smem, 
         const int m = (f >= nr ? 1 : 0) + (f >= 2 * nr ? 1 : 0) + (f >= 3 * nr ? 1 : 0);
         const int row = f == f0 ? frow : row_of(f - m * nr);
         if (row >= N) continue;  // the short last unit's unused slots
-        const float *res = m == 0 ? a.res[0] : m == 1 ? a.res[1] : m == 2 ? a.res[2] : a.res[3];
-        float *y = m == 0 ? a.y[0] : m == 1 ? a.y[1] : m == 2 ? a.y[2] : a.y[3];
+        const float *res = m == 0 ? s0 : m == 1 ? s1 : m == 2 ? s2 : s3;
+        float *y = m == 0 ? y0 : m == 1 ? y1 : m == 2 ? y2 : y3;
         float v = outs[f];
         if (res) v = v + (f == f0 ? __uint_as_float(rv) : res[row]);  // ggml_add(mul_mat, residual)
         store_y(y + row, v);
     }
-    if (a.epi) {  // y[0] = gate, y[1] = up: the same rows of both in this workgroup
-        const int n4 = a.epi_n & ~3;
+    if (h.epi) {  // y[0] = gate, y[1] = up: the same rows of both in this workgroup
+        const int n4 = h.epi_n & ~3;
         for (int f = f0; f < nr; f += 64 * nwv) {
             const int r = row_of(f);
             if (r >= N) continue;
             const float gv = outs[f], uv = outs[nr + f];
-            store_y(a.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+            store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
         }
     }
-    if (RSTAMPS(a)) {  // the kq_rows stamp layout (tools/stamps.py); slot 7: units this wave took
+    if (RSTAMPS(h)) {  // the kq_rows stamp layout (tools/stamps.py); slot 7: units this wave took
         const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * 8;
-        if (lane == 0 && o + 7 < a.stamps_cap) {
-            RSTAMPS(a)[o] = st0;
-            RSTAMPS(a)[o + 1] = st1;
-            RSTAMPS(a)[o + 2] = st2;
-            RSTAMPS(a)[o + 3] = __builtin_amdgcn_s_memrealtime();
-            RSTAMPS(a)[o + 4] = sx;
-            RSTAMPS(a)[o + 5] = sq;
-            RSTAMPS(a)[o + 6] = sf;
-            RSTAMPS(a)[o + 7] = (uint64_t)(ki + 1);
+        if (lane == 0 && o + 7 < h.stamps_cap) {
+            RSTAMPS(h)[o] = st0;
+            RSTAMPS(h)[o + 1] = st1;
+            RSTAMPS(h)[o + 2] = st2;
+            RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
+            RSTAMPS(h)[o + 4] = sx;
+            RSTAMPS(h)[o + 5] = sq;
+            RSTAMPS(h)[o + 6] = sf;
+            RSTAMPS(h)[o + 7] = (uint64_t)(ki + 1);
         }
     }
 }
 template <int TMASK, bool FUSEDQ, int PRO>
-__global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_dyn(const RowsArgs a) {
+__global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_dyn(KQ_ROWS_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint64_t st0 = RSTAMPS(a) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const RowsLead ld = rows_lead(x, x2, w0, res0, nb, waves_total, grid, cfg, rbase0, rrem0);
+    const uint64_t st0 = RSTAMP();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const RowsDynLayout L =
-        rows_dyn_layout(a.nb, TMASK, a.bR, a.rpw, __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)));
     constexpr int TYPE = TMASK == 1 ? Q4_K : TMASK == 2 ? Q5_K : Q6_K;
-    rows_dyn_body<TYPE, FUSEDQ, PRO>(a, smem, L, wave, lane, st0);
+    rows_dyn_body<TYPE, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0);
 }
 
-#define KQ_ROWS_DYN_INST(TM, FQ, PR) template __global__ void kq_rows_dyn<TM, FQ, PR>(const RowsArgs a);
+#define KQ_ROWS_DYN_INST(TM, FQ, PR) template __global__ void kq_rows_dyn<TM, FQ, PR>(KQ_ROWS_PARAMS);
 #define KQ_ROWS_DYN_INST_T(TM)        \
     KQ_ROWS_DYN_INST(TM, true, 0)     \
     KQ_ROWS_DYN_INST(TM, true, 1)     \

@@ -72,12 +72,17 @@ def main(impl):
             t0 = st[:, 0].min()
             rel = (st - t0) * 10 / 1000.0  # 100 MHz ticks -> us
             med = lambda v: float(np.median(v))  # noqa: E731
-            if impl == 0:  # kq_rows: [entry, ring filled, loop end, exit, x landed, x quantized, first step]
+            if impl == 0:  # kq_rows: [entry, ring filled, loop end, exit, x landed, x quantized, first step, arguments fetched]
                 ok = rel[:, 4] > 0
+                # slot 7: the stamp after the entry's one scalar wait (kq_rows; builds before it
+                # leave 0, kq_rows_dyn keeps its unit count there): x-wait = argument fetch +
+                # the rest of the activation fetch
+                ha = ok & (st[:, 7] >= t0)
+                args = med(rel[ha, 7] - rel[ha, 0]) if ha.any() else float("nan")
                 res.append((len(st), rel[:, 0].max(), med(rel[ok, 4] - rel[ok, 0]), med(rel[ok, 5] - rel[ok, 4]),
                             med(rel[:, 1] - rel[:, 5]), med(rel[ok, 6] - rel[ok, 1]),
                             med(rel[:, 1] - rel[:, 0]), med(rel[:, 2] - rel[:, 1]), np.max(rel[:, 2] - rel[:, 1]),
-                            rel[:, 3].max(), rel[:, 2].max(), med(rel[:, 2])))
+                            rel[:, 3].max(), rel[:, 2].max(), med(rel[:, 2]), args))
                 continue
             res.append((len(st), rel[:, 0].max(), med(rel[:, 4] - rel[:, 0]), med(rel[:, 5] - rel[:, 4]),
                         med(rel[:, 6] - rel[:, 5]), med(rel[:, 1] - rel[:, 6]),
@@ -85,7 +90,7 @@ def main(impl):
                         rel[:, 3].max()))
         a = np.array(res)[1:].mean(0)
         if impl == 0:
-            print(f"{tag} {label:12s} waves={int(a[0]):5d} start_spread={a[1]:5.2f}us | x-wait {a[2]:4.2f} quant {a[3]:4.2f} "
+            print(f"{tag} {label:12s} waves={int(a[0]):5d} start_spread={a[1]:5.2f}us | x-wait {a[2]:4.2f} (args {a[12]:4.2f}) quant {a[3]:4.2f} "
                   f"barrier+fill {a[4]:4.2f} = prologue {a[6]:4.2f} | first step {a[5]:4.2f} loop med/max={a[7]:5.2f}/{a[8]:5.2f} "
                   f"loop end med/max={a[11]:6.2f}/{a[10]:6.2f} end={a[9]:6.2f}us")
             continue
