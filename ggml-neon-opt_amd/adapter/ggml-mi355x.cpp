@@ -24,6 +24,10 @@
 //    hipGraph replay); async set / get on the backend stream; synchronize.
 // A graph the lowering cannot take (flash attention, a mask that is not causal over
 // [0, pos], an op outside the list) returns GGML_STATUS_FAILED rather than a wrong result.
+// With ggml_backend_mi355x_set_multi_seq on, a graph whose cells are not its positions
+// (several sequences in the cache, moved cells) is lowered with cells_from_graph instead:
+// the attention reads cells and mask from the graph's inputs (ATTN_BATCH), once the K and V
+// stores are checked to name the same cells.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -172,6 +176,7 @@ struct Backend : mi355x_adapter::Context {
     size_t rope_bytes = 0;
     int rope_dims = 0;
     std::vector<uint8_t> host_in;  // read-back of the inputs when no fresh shadow holds them
+    bool multi_seq = false;        // ggml_backend_mi355x_set_multi_seq: cells and mask from the graph
 };
 
 const char *be_name(ggml_backend_t backend) { return ((Backend *)backend->context)->dev->name.c_str(); }
@@ -267,6 +272,53 @@ bool cells_checked(Backend *ctx, const std::vector<ggml_tensor *> &nodes) {
                                           T);
 }
 
+// Index operand `t` (I32 / I64, n entries) on the host as int64.
+bool read_indices(Backend *ctx, const ggml_tensor *t, int64_t n, std::vector<int64_t> &out) {
+    const size_t eb = t->type == GGML_TYPE_I64 ? 8 : 4;
+    ctx->host_in.resize((size_t)n * eb + 64);
+    const uint8_t *h = read_input(ctx, t, (size_t)n * eb, 0);
+    if (!h) return false;
+    out.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (eb == 8) {
+            std::memcpy(&out[(size_t)i], h + 8 * i, 8);
+        } else {
+            int32_t v;
+            std::memcpy(&v, h + 4 * i, 4);
+            out[(size_t)i] = v;
+        }
+    }
+    return true;
+}
+
+// The lowering's cells_from_graph promise (mi355x_lower_opts), from the graph's inputs: the
+// K-cache and V-cache stores (every layer's SET_ROWS pair shares the two index tensors) name
+// the same cell per token, inside the cache (cells_match, mi355x_ggml_mirror.hpp).
+bool cells_match_checked(Backend *ctx, const std::vector<ggml_tensor *> &nodes) {
+    const ggml_tensor *ks = nullptr, *vs = nullptr;
+    for (const ggml_tensor *t : nodes) {
+        if (!is_op(t, "SET_ROWS") || !t->src[1] || !t->src[1]->data) continue;
+        if (!ks) {
+            ks = t;
+        } else if (!vs && t->src[1]->data != ks->src[1]->data) {
+            vs = t;
+        } else if (t->src[1]->data != ks->src[1]->data && (!vs || t->src[1]->data != vs->src[1]->data)) {
+            return false;  // a third index tensor: not llm_build_llama's pair
+        }
+    }
+    if (!ks || !vs) return false;
+    const ggml_tensor *k_idxs = ks->src[1], *v_idxs = vs->src[1];
+    for (const ggml_tensor *t : {k_idxs, v_idxs})
+        if (t->type != GGML_TYPE_I64 && t->type != GGML_TYPE_I32) return false;
+    const ggml_tensor *kc = ks;  // the K cache [kvw, kv_size] the store writes into
+    while (kc->view_src) kc = kc->view_src;
+    const int64_t T = ggml_nelements(k_idxs), kvw = kc->ne[0], kv_size = kc->ne[1];
+    if (T <= 0 || kvw <= 0 || kv_size <= 0 || ggml_nelements(v_idxs) != T * kvw) return false;
+    std::vector<int64_t> kid, vid;
+    if (!read_indices(ctx, k_idxs, T, kid) || !read_indices(ctx, v_idxs, T * kvw, vid)) return false;
+    return mi355x_adapter::cells_match(kid.data(), vid.data(), T, kvw, kv_size);
+}
+
 // The rope table the lowering's ROPE nodes are checked against: created on the backend
 // for the graph's (n_dims, freq_base, freq_scale) and at least as many positions as the
 // K cache has cells (every SET_ROWS destination's storage), kept while those hold.
@@ -313,6 +365,9 @@ enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph *cg
     for (int i = 0; i < n; ++i) nodes[(size_t)i] = ggml_graph_node(cgraph, i);
     if (!rope_table_for(ctx, nodes)) return GGML_STATUS_FAILED;
     const bool cells_ok = cells_checked(ctx, nodes);
+    // several sequences in the cache, or cells that are not positions: with the multi-sequence
+    // option the attention reads cells and mask from the graph's inputs, else refused as before
+    const bool from_graph = !cells_ok && ctx->multi_seq && cells_match_checked(ctx, nodes);
     {
         std::lock_guard<std::mutex> lk(ctx->dev->mu);
         ++ctx->dev->epoch;  // inputs set after this point are fresh for the next graph
@@ -321,7 +376,7 @@ enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph *cg
     mir.op_name = op_name;
     mir.output_flag = GGML_TENSOR_FLAG_OUTPUT;
     mir.max_src = GGML_MAX_SRC;
-    const int rc = mi355x_adapter::graph_compute(*ctx, mir, nodes.data(), n, cells_ok);
+    const int rc = mi355x_adapter::graph_compute(*ctx, mir, nodes.data(), n, cells_ok, from_graph);
     return rc == 0 ? GGML_STATUS_SUCCESS : GGML_STATUS_FAILED;
 }
 
@@ -532,7 +587,11 @@ ggml_backend_dev_t reg_device(ggml_backend_reg_t reg, size_t i) {
     auto *r = (Registry *)reg->context;
     return i < r->devices.size() ? &r->devices[i]->dev : nullptr;
 }
-void *reg_proc(ggml_backend_reg_t, const char *) { return nullptr; }
+void *reg_proc(ggml_backend_reg_t, const char *name) {
+    if (name && std::strcmp(name, "ggml_backend_mi355x_set_multi_seq") == 0)
+        return (void *)ggml_backend_mi355x_set_multi_seq;
+    return nullptr;
+}
 
 const struct ggml_backend_reg_i kRegIface = {
     /* .get_name         = */ reg_name,
@@ -582,6 +641,10 @@ ggml_backend_buffer_type_t ggml_backend_mi355x_buffer_type(int device) {
 }
 
 int ggml_backend_mi355x_get_device_count(void) { return (int)registry()->devices.size(); }
+
+void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable) {
+    if (ggml_backend_is_mi355x(backend)) ((Backend *)backend->context)->multi_seq = enable;
+}
 
 GGML_BACKEND_DL_IMPL(ggml_backend_mi355x_reg)
 GGML_BACKEND_DL_SCORE_IMPL(mi355x_score)

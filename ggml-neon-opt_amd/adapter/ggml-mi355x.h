@@ -23,6 +23,15 @@ GGML_BACKEND_API bool ggml_backend_is_mi355x(ggml_backend_t backend);
 // unchanged: no repack)
 GGML_BACKEND_API ggml_backend_buffer_type_t ggml_backend_mi355x_buffer_type(int device);
 GGML_BACKEND_API int ggml_backend_mi355x_get_device_count(void);
+// Several sequences in the unified KV cache, or one whose cells are not its positions (a
+// removed cell, a context shift, a reused prefix). Off (the default): such a graph is refused
+// (GGML_STATUS_FAILED), as a graph the backend cannot compute always is. On: its attention
+// blocks run as ATTN_BATCH nodes that take each token's cell from the K store's indices and
+// the mask from the graph's KQ mask, when the V store's indices name the same cells
+// (mi355x_adapter::cells_match). Graphs whose cells equal their positions under a causal mask
+// keep the single-sequence path either way. Also returned by the registry's get_proc_address
+// under this name.
+GGML_BACKEND_API void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,22 @@ inline bool kq_mask_causal(const void *mask, int mask_type, int64_t n_kv, size_t
     return true;
 }
 
+// The cells_from_graph promise of mi355x_lower_opts (ATTN_BATCH takes each token's cell
+// from the K store's indices and writes the transposed V at the same cell), on the host
+// copies of the two SET_ROWS index operands: for every token i and channel ch the V store's
+// entry v_idxs[i*kvw + ch] is ch*kv_size + k_idxs[i] (llama-kv-cache's transposed-V
+// indices), and every cell lies inside the cache. An empty batch promises nothing.
+inline bool cells_match(const int64_t *k_idxs, const int64_t *v_idxs, int64_t n_tokens, int64_t kvw,
+                        int64_t kv_size) {
+    if (n_tokens <= 0 || kvw <= 0 || kv_size <= 0 || !k_idxs || !v_idxs) return false;
+    for (int64_t i = 0; i < n_tokens; ++i) {
+        if (k_idxs[i] < 0 || k_idxs[i] >= kv_size) return false;
+        for (int64_t ch = 0; ch < kvw; ++ch)
+            if (v_idxs[i * kvw + ch] != ch * kv_size + k_idxs[i]) return false;
+    }
+    return true;
+}
+
 // Rope table parameters the lowering checks a ROPE node against (ggml rope op_params:
 // [1] n_dims, [2] mode, [5] freq_base, [6] freq_scale as float bits).
 struct RopeParams {
@@ -146,9 +162,12 @@ inline bool rope_params_of(const Tensor *rope, RopeParams &p) {
     return p.n_dims > 0 && (p.n_dims % 2) == 0;
 }
 
-// Lower `n` graph nodes; 0 and the backend node list, or the lowering's status.
+// Lower `n` graph nodes; 0 and the backend node list, or the lowering's status. cells_ok:
+// the cells == positions promise holds (ATTN_DECODE); cells_from_graph: it does not, but
+// cells_match does and the backend's multi-sequence option is on (ATTN_BATCH).
 template <typename Tensor>
-int lower(Context &ctx, Mirror<Tensor> &mir, Tensor *const *graph_nodes, int n, bool cells_ok, int *n_out) {
+int lower(Context &ctx, Mirror<Tensor> &mir, Tensor *const *graph_nodes, int n, bool cells_ok, int *n_out,
+          bool cells_from_graph = false) {
     std::vector<mi355x_gtensor *> g((size_t)n);
     for (int i = 0; i < n; ++i) g[(size_t)i] = mir.of(graph_nodes[i]);
     ctx.arena.resize(4 * (size_t)n + 64);
@@ -160,15 +179,17 @@ int lower(Context &ctx, Mirror<Tensor> &mir, Tensor *const *graph_nodes, int n, 
     opts.rope_freq_base = ctx.freq_base;
     opts.rope_freq_scale = ctx.freq_scale;
     opts.cells_eq_pos = cells_ok ? 1 : 0;
+    opts.cells_from_graph = !cells_ok && cells_from_graph ? 1 : 0;
     return mi355x_lower_ggml_graph(g.data(), n, &opts, ctx.arena.data(), (int)ctx.arena.size(), ctx.nodes.data(),
                                    (int)ctx.nodes.size(), n_out);
 }
 
 // graph_compute: lower, then run with hipGraph replay (decode steps repeat the graph).
 template <typename Tensor>
-int graph_compute(Context &ctx, Mirror<Tensor> &mir, Tensor *const *graph_nodes, int n, bool cells_ok) {
+int graph_compute(Context &ctx, Mirror<Tensor> &mir, Tensor *const *graph_nodes, int n, bool cells_ok,
+                  bool cells_from_graph = false) {
     int nn = 0;
-    const int rc = lower(ctx, mir, graph_nodes, n, cells_ok, &nn);
+    const int rc = lower(ctx, mir, graph_nodes, n, cells_ok, &nn, cells_from_graph);
     if (rc) return rc;
     return mi355x_backend_graph_compute(ctx.be, ctx.nodes.data(), nn, /*use_graph=*/1);
 }

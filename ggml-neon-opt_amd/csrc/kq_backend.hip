@@ -334,6 +334,19 @@ void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a) {
     a.n_ctx = (int)t->src[4]->ne[1];
 }
 
+// ATTN_BATCH: the ATTN_DECODE operands, the cells (src7), the mask (src8) and n_kv
+void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d) {
+    attn_desc_of(t, d.a);
+    d.a.rope_row = 0;
+    d.cells = t->src[7]->data;
+    d.cells_type = t->src[7]->type;
+    d.mask = t->src[8]->data;
+    d.mask_type = t->src[8]->type;
+    d.mask_row_bytes = t->src[8]->nb[1];
+    d.n_kv = t->op_params[4];
+    d.n_tokens = (int)t->src[0]->ne[1];
+}
+
 // A batched MUL_MAT that runs on the int8 GEMM (kq_mmq, Q8L activation blocks): always in
 // the exact precision, and in the f16 one where kq_mmf is not the faster kernel
 bool mm_exact(const mi355x_tensor *t) {
@@ -755,6 +768,15 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             }
             a.rope_row = t->src[6]->ne[1] == 1 ? 1 : 0;  // the position's row, staged with pos
             return mi355x_attn_decode(&a, st);
+        }
+        case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
+            mi355x_attn_batch_desc d;
+            attn_batch_desc_of(t, d);
+            kq::AttnBatchArgs ba;
+            const int rc = kq::attn_batch_args_from(&d, (int)t->src[6]->ne[1], ba);
+            if (rc) return rc;
+            if (!kq::device_ok()) return MI355X_E_NODEVICE;
+            return kq::launch_attn_batch(ba, st);
         }
         default:
             return MI355X_E_UNSUPPORTED;
@@ -1265,6 +1287,47 @@ int mi355x_backend_supports_op(const mi355x_tensor *op) {
                 return 0;  // packed rows; the whole rope table (one position per token)
             if (op->src[6]->ne[1] != 1 && op->src[6]->ne[1] < op->src[4]->ne[1]) return 0;  // row or table
             if (op->src[6]->ne[0] != hd) return 0;
+            return contig_f32(op) && op->ne[0] == (int64_t)nh * hd && op->ne[1] == T &&
+                   (T == 1 || op->nb[1] == (size_t)nh * hd * 4);
+        }
+        case MI355X_OP_ATTN_BATCH: {
+            for (int s = 0; s < 9; ++s)
+                if (!op->src[s] || !op->src[s]->data) return 0;
+            const int nh = op->op_params[0], nkv = op->op_params[1], hd = op->op_params[2], n_kv = op->op_params[4];
+            if ((hd != 64 && hd != 128) || nkv <= 0 || nh <= 0 || nh % nkv) return 0;
+            const mi355x_tensor *kc = op->src[4], *vc = op->src[5], *tab = op->src[6], *cells = op->src[7],
+                                *mask = op->src[8];
+            if (kc->type != MI355X_TYPE_F16 || vc->type != MI355X_TYPE_F16) return 0;
+            if (kc->ne[0] != (int64_t)nkv * hd || op->src[3]->type != MI355X_TYPE_I32) return 0;
+            if (vc->ne[0] != kc->ne[1] || vc->ne[1] != kc->ne[0]) return 0;
+            // caches exactly [n_ctx][kvw] and [kvw][n_ctx] f16, 16-B aligned (the kernels' addressing)
+            if (kc->nb[0] != 2 || kc->nb[1] != (size_t)kc->ne[0] * 2) return 0;
+            if (vc->nb[0] != 2 || vc->nb[1] != (size_t)vc->ne[0] * 2) return 0;
+            if (((uintptr_t)kc->data & 15u) || ((uintptr_t)vc->data & 15u)) return 0;
+            const int64_t n_ctx = kc->ne[1];
+            if (n_ctx < 32 || n_ctx % 32 || n_ctx > 8192) return 0;
+            if (n_kv < 32 || n_kv % 32 || n_kv > n_ctx) return 0;
+            // T tokens, rows packed: q [nh*hd, T], k, v [kvw, T], pos [T], cells [T]
+            const int64_t T = op->src[0]->ne[1];
+            if (T < 1 || T > 65535 || op->src[0]->ne[0] != (int64_t)nh * hd) return 0;
+            for (int s = 0; s < 3; ++s)
+                if (!contig_f32(op->src[s])) return 0;
+            if (nelem(op->src[0]) != (int64_t)nh * hd * T || nelem(op->src[1]) != (int64_t)nkv * hd * T ||
+                nelem(op->src[2]) != (int64_t)nkv * hd * T || op->src[3]->ne[0] != T)
+                return 0;
+            if (T > 1 && (op->src[0]->nb[1] != (size_t)nh * hd * 4 || op->src[1]->nb[1] != (size_t)nkv * hd * 4 ||
+                          op->src[2]->nb[1] != (size_t)nkv * hd * 4))
+                return 0;
+            if (!contig_f32(tab) || tab->ne[0] != hd || tab->ne[1] < 1 || tab->ne[1] > 0x7fffffff) return 0;
+            if ((cells->type != MI355X_TYPE_I32 && cells->type != MI355X_TYPE_I64) || nelem(cells) != T) return 0;
+            if (cells->nb[0] != (cells->type == MI355X_TYPE_I64 ? 8u : 4u)) return 0;
+            if (mask->type != MI355X_TYPE_F16 && mask->type != MI355X_TYPE_F32) return 0;
+            const size_t me = mask->type == MI355X_TYPE_F16 ? 2 : 4;
+            if (mask->nb[0] != me || mask->ne[0] < n_kv || mask->ne[1] < T || mask->nb[1] < (size_t)n_kv * me) return 0;
+            mi355x_attn_batch_desc d;
+            attn_batch_desc_of(op, d);
+            kq::AttnBatchArgs ba;
+            if (kq::attn_batch_args_from(&d, (int)tab->ne[1], ba) != MI355X_OK) return 0;  // the LDS of either form
             return contig_f32(op) && op->ne[0] == (int64_t)nh * hd && op->ne[1] == T &&
                    (T == 1 || op->nb[1] == (size_t)nh * hd * 4);
         }

@@ -287,6 +287,20 @@ struct AttnArgs {
     int n_tok;        // prompt batch (kq_attn_prompt_group), set by launch_attn_prompt: its tokens
 };
 
+// Batched attention with the KV cells and the mask read from the graph's inputs
+// (kq_attn_batch.hip): `a` as for a prompt batch (rows per token, rope_row 0).
+struct AttnBatchArgs {
+    AttnArgs a;
+    const void *cells;        // device int32 / int64 [n_tok]: token i's cache cell
+    const void *mask;         // device f16 / f32: token i's row at mask + i * mask_row_bytes, >= n_kv entries
+    int64_t mask_row_bytes;
+    int cells_i64, mask_f16;
+    int n_kv;                 // the row: cells [0, n_kv), n_kv % 32 == 0, <= a.n_ctx
+    int n_tok;
+    int n_pos;                // rows of the rope table: a position outside [0, n_pos) has no cell
+    int per_head;             // set by launch_attn_batch: one workgroup per query head, not per kv group
+};
+
 // Decode attention fused with the o-proj GEMV (kq_attn_oproj.hip): workgroup (s, rb) runs the
 // attention of the heads of superblock s of the o-proj's K, quantizes them (one Q8_K
 // superblock) and writes the exact per-superblock records of rows [rb*R, rb*R + R); the

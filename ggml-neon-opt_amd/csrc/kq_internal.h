@@ -106,6 +106,12 @@ constexpr int kAttnOprojMaxCtx = 256;  // kq_attn_oproj fuses caches of at most 
 size_t attn_oproj_buffer(int hd, int n_head, int n_head_kv, int n_ctx, int type, int64_t K, int64_t n_rows, int *nsb);
 int launch_attn_oproj(const AttnArgs &a, int type, const void *w, int64_t n_rows, size_t row_stride, const float *res,
                       float *y, uint8_t *buf, size_t buf_size, hipStream_t stream);
+// kq_attn_batch.hip: the attention block with cells and mask from the graph. attn_batch_args_from
+// checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /
+// MI355X_ATTN_HEAD, or MI355X_E_UNSUPPORTED where neither form's LDS fits.
+int attn_batch_args_from(const mi355x_attn_batch_desc *d, int n_pos, AttnBatchArgs &b);
+int attn_batch_form(const AttnBatchArgs &b);
+int launch_attn_batch(const AttnBatchArgs &b, hipStream_t s);
 int attn_impl();  // mi355x_attn_impl (kq_ops.hip)
 size_t attn_lds16(int hd, int n_ctx);  // attn_head's LDS per head, 16-B multiple (kq_attn_oproj.hip)
 // kq_layer.hip: one decode layer as one persistent launch. The caller fills E, F, nq, nkv,

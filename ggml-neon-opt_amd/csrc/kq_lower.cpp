@@ -12,7 +12,10 @@
 //  * the attention block of llama-graph.cpp's build_attn (non-flash: ROPE(Q), ROPE(K),
 //    SET_ROWS into the K and V caches, MUL_MAT(K cache, Q), SOFT_MAX_EXT(kq, mask,
 //    scale), MUL_MAT(V cache, kq), PERMUTE, CONT [U]) becomes one ATTN_DECODE node with
-//    the pre-rope q/k/v, the position, both caches and the caller's rope table;
+//    the pre-rope q/k/v, the position, both caches and the caller's rope table (the
+//    adapter's cells_eq_pos promise), or one ATTN_BATCH node that also takes the K store's
+//    cell indices and the soft_max mask from the graph (cells_from_graph: several
+//    sequences in the cache, or cells that are not positions);
 //  * the [up, gate] MUL_MAT pair build_ffn emits before SWIGLU(gate, up) [U] is put in
 //    [gate, up] order (the two nodes are independent) so the gate/up launch fuses.
 // Anything else returns MI355X_E_UNSUPPORTED: the caller hands the graph to another
@@ -152,8 +155,13 @@ struct Lower {
     // is the block's meaning only under the adapter's cells_eq_pos promise (one sequence,
     // k_idxs == v_idxs cells == inp_pos, causal mask, views from cell 0), so without it
     // the block is not lowered.
+    // Under cells_from_graph instead (the adapter's other promise: v_idxs[i*kvw + ch] ==
+    // ch*kv_size + k_idxs[i], every k_idxs[i] in [0, kv_size)), the same pattern becomes one
+    // ATTN_BATCH, which reads the cells (the K store's index leaf) and the mask leaf on the
+    // device over the n_kv cells the KQ / KQV views span.
     bool attention(const mi355x_gtensor *c) {
-        if (!opts->cells_eq_pos) return false;
+        const bool batch = !opts->cells_eq_pos && opts->cells_from_graph;
+        if (!opts->cells_eq_pos && !batch) return false;
         const mi355x_gtensor *p = c->src[0];
         if (!p || p->op != MI355X_GOP_PERMUTE) return false;
         const mi355x_gtensor *kqv = root(p->src[0]);
@@ -210,8 +218,23 @@ struct Lower {
         tab->nb[1] = (size_t)hd * 4;
         tab->nb[2] = tab->nb[3] = tab->nb[1] * (size_t)opts->rope_n_pos;
         tab->data = opts->rope_table;
-        mi355x_tensor *a = emit(c, MI355X_OP_ATTN_DECODE,
-                                {value(qmm), value(kmm), value(vmm), leaf(root(pos)), leaf(kcache), leaf(vcache), tab});
+        mi355x_tensor *a;
+        if (batch) {
+            // the mask: an F16 / F32 leaf with a row of >= n_kv entries per token; n_kv: the
+            // cells both views span, whole 32-cell blocks inside the cache
+            const mi355x_gtensor *mask = sm->src[1];
+            const int64_t n_kv = kq->src[0]->ne[1];
+            if (root(mask)->op != MI355X_GOP_NONE || (mask->type != kTypeF16 && mask->type != kTypeF32)) return false;
+            if (n_kv != kqv->src[0]->ne[0] || n_kv < 32 || n_kv % 32 || n_kv > kcache->ne[1]) return false;
+            if (mask->ne[0] < n_kv || mask->ne[1] < T || mask->ne[2] != 1 || mask->ne[3] != 1) return false;
+            a = emit(c, MI355X_OP_ATTN_BATCH,
+                     {value(qmm), value(kmm), value(vmm), leaf(root(pos)), leaf(kcache), leaf(vcache), tab,
+                      leaf(sk->src[1]), leaf(mask)});
+            if (a) a->op_params[4] = (int32_t)n_kv;
+        } else {
+            a = emit(c, MI355X_OP_ATTN_DECODE,
+                     {value(qmm), value(kmm), value(vmm), leaf(root(pos)), leaf(kcache), leaf(vcache), tab});
+        }
         if (!a) return false;
         a->ne[0] = (int64_t)nh * hd;
         a->ne[1] = T;

@@ -18,13 +18,15 @@ PKG_ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("MI355X_LIB") or os.path.join(PKG_ROOT, "lib", "libggml_mi355x.so")
 
 TYPE_F32, TYPE_F16, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K, TYPE_Q8_K, TYPE_I32 = 0, 1, 12, 13, 14, 15, 26
+TYPE_I64 = 27  # cell indices of attn_batch / OP_ATTN_BATCH
 QK_K = 256
 BLOCK_BYTES = {TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210, TYPE_Q8_K: 292}
 TYPE_NAMES = {TYPE_Q4_K: "q4_K", TYPE_Q5_K: "q5_K", TYPE_Q6_K: "q6_K", TYPE_Q8_K: "q8_K", TYPE_F32: "f32"}
 MAX_FUSED = 4
 OP_NONE, OP_MUL_MAT, OP_GET_ROWS, OP_RMS_NORM, OP_MUL, OP_ADD, OP_SWIGLU, OP_ROPE, OP_ATTN_DECODE, OP_ALL_GATHER, \
     OP_ALL_REDUCE = range(11)
-MAX_SRC = 8
+OP_ATTN_BATCH = 11
+MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
 PRO_NONE, PRO_RMS_NORM, PRO_SWIGLU = 0, 1, 2
@@ -64,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_backend_set_layer_engine", "mi355x_backend_layer_error",
     "mi355x_attn_prompt",
     "mi355x_attn_prompt_impl",
+    "mi355x_attn_batch", "mi355x_attn_batch_path",
 )
 
 
@@ -102,7 +105,8 @@ GTensor._fields_ = [("type", ctypes.c_int), ("op", ctypes.c_int), ("ne", ctypes.
 
 class LowerOpts(ctypes.Structure):
     _fields_ = [("rope_table", ctypes.c_void_p), ("rope_n_pos", ctypes.c_int), ("rope_freq_base", ctypes.c_float),
-                ("rope_freq_scale", ctypes.c_float), ("cells_eq_pos", ctypes.c_int)]
+                ("rope_freq_scale", ctypes.c_float), ("cells_eq_pos", ctypes.c_int),
+                ("cells_from_graph", ctypes.c_int)]
 
 
 (GOP_NONE, GOP_GET_ROWS, GOP_RMS_NORM, GOP_MUL, GOP_ADD, GOP_MUL_MAT, GOP_ROPE, GOP_SET_ROWS, GOP_SOFT_MAX, GOP_GLU,
@@ -116,6 +120,13 @@ class AttnDesc(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("n_ctx", ctypes.c_int), ("n_head", ctypes.c_int),
                 ("n_head_kv", ctypes.c_int), ("head_dim", ctypes.c_int), ("scale", ctypes.c_float),
                 ("rope_row", ctypes.c_int)]
+
+
+class AttnBatchDesc(ctypes.Structure):
+    """mi355x_attn_batch_desc"""
+    _fields_ = [("a", AttnDesc), ("cells", ctypes.c_void_p), ("cells_type", ctypes.c_int), ("mask", ctypes.c_void_p),
+                ("mask_type", ctypes.c_int), ("mask_row_bytes", ctypes.c_size_t), ("n_kv", ctypes.c_int),
+                ("n_tokens", ctypes.c_int)]
 
 
 class GemvExt(ctypes.Structure):
@@ -218,6 +229,10 @@ def lib():
     L.mi355x_attn_path.argtypes = [ctypes.POINTER(AttnDesc)]
     L.mi355x_attn_path.restype = i32
     L.mi355x_attn_prompt.argtypes = [ctypes.POINTER(AttnDesc), i32, vp]
+    L.mi355x_attn_batch.argtypes = [ctypes.POINTER(AttnBatchDesc), vp]
+    L.mi355x_attn_batch.restype = i32
+    L.mi355x_attn_batch_path.argtypes = [ctypes.POINTER(AttnBatchDesc)]
+    L.mi355x_attn_batch_path.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -433,7 +448,8 @@ def debug_knob(name, value=float("nan")):
 
 
 def attn_prompt_impl(impl):
-    """Prompt attention: ATTN_GROUP (per kv group and token, default) / ATTN_HEAD; returns the previous."""
+    """Prompt attention, and attn_batch / OP_ATTN_BATCH: ATTN_GROUP (per kv group and token where it
+    fits, default) / ATTN_HEAD (per query head and token); returns the previous."""
     return int(lib().mi355x_attn_prompt_impl(impl))
 
 
@@ -564,6 +580,48 @@ def attn_prompt(q, k, v, pos, table, k_cache, v_cache, n_head, n_head_kv, head_d
     return out
 
 
+def _attn_batch_desc(q, k, v, pos, cells, mask, table, k_cache, v_cache, out, n_head, n_head_kv, head_dim, scale,
+                     n_kv):
+    torch = _torch()
+    T = pos.numel()
+    a = AttnDesc(q.data_ptr(), k.data_ptr(), v.data_ptr(), pos.data_ptr(), table.data_ptr(), k_cache.data_ptr(),
+                 v_cache.data_ptr(), out.data_ptr(), k_cache.shape[0], n_head, n_head_kv, head_dim, scale, 0)
+    if cells.dtype not in (torch.int32, torch.int64) or cells.numel() != T or not cells.is_contiguous():
+        raise Mi355xError("attn_batch: cells must be a contiguous int32 / int64 tensor of one entry per token")
+    if mask.dtype not in (torch.float16, torch.float32) or mask.dim() != 2 or mask.stride(1) != 1 or \
+            mask.shape[0] < T:
+        raise Mi355xError("attn_batch: mask must be float16 / float32 (rows >= T, >= n_kv) with unit column stride")
+    return AttnBatchDesc(a, cells.data_ptr(), TYPE_I64 if cells.dtype == torch.int64 else TYPE_I32, mask.data_ptr(),
+                         TYPE_F16 if mask.dtype == torch.float16 else TYPE_F32,
+                         mask.stride(0) * mask.element_size(), n_kv, T)
+
+
+def attn_batch(q, k, v, pos, cells, mask, table, k_cache, v_cache, n_head, n_head_kv, head_dim, scale, n_kv,
+               out=None, stream=None):
+    """The attention block of T tokens with the KV cells and the mask given (mi355x_attn_batch):
+    q (T, n_head*hd), k, v (T, n_head_kv*hd) f32 before rope; pos int32 cuda (T,), only the rope
+    row; cells int32 / int64 cuda (T,): token i is stored at cell cells[i]; mask (>= T, >= n_kv)
+    float16 / float32, additive (0 visible, -inf hidden), row stride free; table the whole rope
+    table. Every query attends over cells [0, n_kv). Returns out (T, n_head*hd)."""
+    _require_device()
+    T = pos.numel()
+    out = _torch().empty((T, n_head * head_dim), dtype=_torch().float32, device=q.device) if out is None else out
+    d = _attn_batch_desc(q, k, v, pos, cells, mask, table, k_cache, v_cache, out, n_head, n_head_kv, head_dim, scale,
+                         n_kv)
+    _check(lib().mi355x_attn_batch(ctypes.byref(d), _stream(stream)), "mi355x_attn_batch")
+    return out
+
+
+def attn_batch_path(n_ctx, n_head, n_head_kv, head_dim, n_kv):
+    """ATTN_GROUP / ATTN_HEAD: the form mi355x_attn_batch takes for this shape (negative: the
+    status it would return). No launch, no device access (synthetic, aligned addresses)."""
+    base = 1 << 20
+    a = AttnDesc(base, base + 4096, base + 8192, base + 64, base + 12288, base + (1 << 12), base + (1 << 13),
+                 base + (1 << 14), n_ctx, n_head, n_head_kv, head_dim, 1.0 / float(head_dim) ** 0.5, 0)
+    d = AttnBatchDesc(a, base + 128, TYPE_I32, base + 256, TYPE_F32, 4 * n_kv, n_kv, 1)
+    return int(lib().mi355x_attn_batch_path(ctypes.byref(d)))
+
+
 def block_partials(type_, w, K, q8_row, stream=None):
     """Per-superblock integer partials -> (N, nb, 2) int32 cuda tensor."""
     torch = _torch()
@@ -679,18 +737,22 @@ class Backend:
 
 
 def lower_ggml_graph(gnodes, rope_table_ptr, rope_n_pos, freq_base, freq_scale=1.0, arena_cap=None,
-                     cells_eq_pos=True):
+                     cells_eq_pos=True, cells_from_graph=False):
     """mi355x_lower_ggml_graph over a list of GTensor nodes (graph order). Returns
     (status, [Tensor node list], arena) — the arena keeps the nodes alive.
     cells_eq_pos: the adapter's promise (mi355x_lower_opts) that the batch is one
-    sequence whose KV cells equal its positions under a causal mask."""
+    sequence whose KV cells equal its positions under a causal mask. cells_from_graph (with
+    cells_eq_pos False): attention blocks become ATTN_BATCH nodes that read the K store's cell
+    indices and the soft_max mask on the device; the promise is that the V store's indices
+    match the K store's (v_idxs[i*kvw + ch] == ch*kv_size + k_idxs[i], cells inside the cache)."""
     n = len(gnodes)
     arr = (ctypes.POINTER(GTensor) * max(1, n))(*[ctypes.pointer(t) for t in gnodes])
     cap = arena_cap or (4 * n + 64)
     arena = (Tensor * cap)()
     out = (ctypes.POINTER(Tensor) * cap)()
     nn = ctypes.c_int(0)
-    opts = LowerOpts(rope_table_ptr, rope_n_pos, freq_base, freq_scale, 1 if cells_eq_pos else 0)
+    opts = LowerOpts(rope_table_ptr, rope_n_pos, freq_base, freq_scale, 1 if cells_eq_pos else 0,
+                     1 if cells_from_graph else 0)
     rc = int(lib().mi355x_lower_ggml_graph(arr, n, ctypes.byref(opts), arena, cap, out, cap, ctypes.byref(nn)))
     return rc, [out[i].contents for i in range(nn.value)], (arena, out)
 
@@ -714,7 +776,7 @@ def make_tensor(type_, ne0, ne1, data, row_stride=None, op=OP_NONE, src0=None, s
     t = Tensor()
     t.type = type_
     t.op = op
-    nb0 = BLOCK_BYTES.get(type_, 2 if type_ == TYPE_F16 else 4)
+    nb0 = BLOCK_BYTES.get(type_, 2 if type_ == TYPE_F16 else 8 if type_ == TYPE_I64 else 4)
     nb1 = row_stride if row_stride is not None else (ne0 // QK_K * nb0 if type_ in BLOCK_BYTES else ne0 * nb0)
     t.ne[0], t.ne[1], t.ne[2], t.ne[3] = ne0, ne1, 1, 1
     t.nb[0], t.nb[1], t.nb[2], t.nb[3] = nb0, nb1, nb1 * ne1, nb1 * ne1

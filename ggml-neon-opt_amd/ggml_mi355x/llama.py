@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL, OP_MUL_MAT,
+from . import (FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
+               OP_MUL_MAT,
                OP_RMS_NORM,
                OP_SWIGLU, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table)
 
@@ -56,6 +57,7 @@ class LlamaDecoder:
     """
 
     HOST_SLOTS = 1024
+    BATCH_SLOTS = 64  # pinned staging rows of a step_batch graph (tokens | pos | cells | mask)
 
     def __init__(self, backend: Backend, hp: dict, weights: dict, n_ctx: int, fuse: bool = True, split=None,
                  rope_src: str = "row"):
@@ -333,6 +335,128 @@ class LlamaDecoder:
         if rc:
             raise Mi355xError(f"graph_compute failed ({rc})")
         self.prompt_hidden = g["hidden"]
+        return g["logits"]
+
+    # ------------------------------------------------------------ several sequences per step
+    def _batch_graph(self, n_tok: int, n_kv: int):
+        """Node list of one batch of n_tok tokens that may belong to different sequences
+        (llm_build_llama over a ubatch with a unified KV cache): like _prompt_graph, but each
+        attention block is an ATTN_BATCH node that takes every token's cache cell and mask row
+        from the inputs, and the output norm and head run over all n_tok rows (every sequence
+        needs its logits). Inputs, one device buffer: token ids | positions | cells (int32
+        [n_tok] each) | the mask, f32 [n_tok, n_kv]."""
+        import torch
+        key = (n_tok, n_kv)
+        cached = getattr(self, "_batches", {}).get(key)
+        if cached is not None:
+            return cached
+        if self.split is not None:
+            raise Mi355xError("batched decoding runs on one GPU (no row split)")
+        hp, weights, n_ctx = self.hp, self.w, self.n_ctx
+        dev = weights["output_norm"].device
+        E, V = hp["n_embd"], hp["n_vocab"]
+        hd, nh, nkv = hp["head_dim"], hp["n_head"], hp["n_head_kv"]
+        kvw = nkv * hd
+        T, bufs, nodes = [], [], []
+        inp = torch.zeros(3 * n_tok + n_tok * n_kv, dtype=torch.int32, device=dev)
+
+        def leaf(t, type_, ne0, ne1=1, row_stride=None):
+            x = make_tensor(type_, ne0, ne1, t.data_ptr(), row_stride=row_stride)
+            T.append(x)
+            return x
+
+        def node(op, n, srcs, params=None, flags=0):
+            b = torch.zeros(n * n_tok, dtype=torch.float32, device=dev)
+            bufs.append(b)
+            x = make_tensor(TYPE_F32, n, n_tok, b.data_ptr(), op=op, srcs=srcs, op_params=params, flags=flags)
+            T.append(x)
+            nodes.append(x)
+            return x, b
+
+        def mm(name, x, flags=0):
+            t, w = weights[name]
+            wt = leaf(w, t, w.shape[1] * 256 // {12: 144, 13: 176, 14: 210}[t], w.shape[0], row_stride=w.stride(0))
+            return node(OP_MUL_MAT, wt.ne[1], [wt, x], flags=flags)
+
+        eps_bits = [f32_bits(hp["eps"])]
+        tok = leaf(inp[:n_tok], TYPE_I32, n_tok)
+        pos = leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
+        cells = leaf(inp[2 * n_tok:3 * n_tok], TYPE_I32, n_tok)
+        mask = leaf(inp[3 * n_tok:], TYPE_F32, n_kv, n_tok)
+        tab = leaf(self.table, TYPE_F32, hd, n_ctx)
+        et, ew = weights["token_embd"]
+        emb_t = leaf(ew, et, E, ew.shape[0], row_stride=ew.stride(0) * ew.element_size())
+        x, _ = node(OP_GET_ROWS, E, [emb_t, tok])
+        scale = f32_bits(float(torch.tensor(1.0) / torch.sqrt(torch.tensor(float(hd)))))
+        for i in range(hp["n_layer"]):
+            p = f"blk.{i}."
+            n1, _ = node(OP_RMS_NORM, E, [x], eps_bits)
+            m1, _ = node(OP_MUL, E, [n1, leaf(weights[p + "attn_norm"], TYPE_F32, E)])
+            q, k, v = mm(p + "attn_q", m1)[0], mm(p + "attn_k", m1)[0], mm(p + "attn_v", m1)[0]
+            kc = leaf(self.k_cache[i], TYPE_F16, kvw, n_ctx)
+            vc = leaf(self.v_cache[i], TYPE_F16, n_ctx, kvw)
+            att, _ = node(OP_ATTN_BATCH, nh * hd, [q, k, v, pos, kc, vc, tab, cells, mask],
+                          [nh, nkv, hd, scale, n_kv])
+            o = mm(p + "attn_output", att)[0]
+            ffn_inp, _ = node(OP_ADD, E, [o, x])
+            n2, _ = node(OP_RMS_NORM, E, [ffn_inp], eps_bits)
+            m2, _ = node(OP_MUL, E, [n2, leaf(weights[p + "ffn_norm"], TYPE_F32, E)])
+            gt, up = mm(p + "ffn_gate", m2)[0], mm(p + "ffn_up", m2)[0]
+            glu, _ = node(OP_SWIGLU, gt.ne[0], [gt, up])
+            dn = mm(p + "ffn_down", glu)[0]
+            x, _ = node(OP_ADD, E, [dn, ffn_inp])
+        n3, _ = node(OP_RMS_NORM, E, [x], eps_bits)
+        m3, _ = node(OP_MUL, E, [n3, leaf(weights["output_norm"], TYPE_F32, E)])
+        _, logits = mm("output", m3, flags=FLAG_OUTPUT)
+        g = dict(inp=inp, nodes=nodes, tensors=T, bufs=bufs, logits=logits.view(n_tok, V),
+                 arr=(ctypes.POINTER(type(T[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes]),
+                 host=torch.zeros((self.BATCH_SLOTS, inp.numel()), dtype=torch.int32).pin_memory()
+                 if self.b is not None else None, slot=0)
+        if not hasattr(self, "_batches"):
+            self._batches = {}
+        self._batches[key] = g
+        if self.b is not None:
+            torch.cuda.synchronize()  # zeroed buffers (torch's stream) before the backend stream runs
+        return g
+
+    def step_batch(self, tokens, pos, cells, mask, n_kv: int, use_graph: bool = True):
+        """Enqueue one batch of T tokens of any sequences (no synchronization): token i has
+        position pos[i] (its rope row), is stored at cache cell cells[i] and attends over cells
+        [0, n_kv) under mask[i] (additive: 0 visible, -inf hidden; [T, >= n_kv] floats, numpy or
+        torch on the host). Returns the device logits [T, n_vocab]. The graph of a (T, n_kv)
+        pair is built once and replayed with new input contents."""
+        import numpy as np
+        import torch
+        n_tok = len(tokens)
+        if n_tok < 1 or len(pos) != n_tok or len(cells) != n_tok:
+            raise Mi355xError("step_batch: tokens, pos and cells need one entry per token")
+        if n_kv < 32 or n_kv % 32 or n_kv > self.n_ctx:
+            raise Mi355xError(f"step_batch: n_kv {n_kv} must be a multiple of 32 in [32, n_ctx {self.n_ctx}]")
+        if any(not 0 <= t < self.hp["n_vocab"] for t in tokens):
+            raise Mi355xError("step_batch: token outside the vocabulary")
+        if any(not 0 <= c < self.n_ctx for c in cells) or any(not 0 <= p < self.n_ctx for p in pos):
+            raise Mi355xError(f"step_batch: cell or position outside the KV cache (n_ctx {self.n_ctx})")
+        m = torch.as_tensor(np.asarray(mask, dtype=np.float32) if not torch.is_tensor(mask) else mask).to(torch.float32)
+        if m.dim() != 2 or m.shape[0] != n_tok or m.shape[1] < n_kv:
+            raise Mi355xError(f"step_batch: mask must be [{n_tok}, >= {n_kv}]")
+        from . import lib
+        g = self._batch_graph(n_tok, n_kv)
+        if g["slot"] == self.BATCH_SLOTS:  # a pinned staging row is reused only after its copy is done
+            self.b.synchronize()
+            g["slot"] = 0
+        host = g["host"][g["slot"]]
+        g["slot"] += 1
+        host[:n_tok] = torch_tensor(tokens)
+        host[n_tok:2 * n_tok] = torch_tensor(pos)
+        host[2 * n_tok:3 * n_tok] = torch_tensor(cells)
+        host[3 * n_tok:].view(torch.float32).view(n_tok, n_kv).copy_(m[:, :n_kv])
+        L = lib()
+        rc = L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel())
+        if rc:
+            raise Mi355xError(f"set_tensor failed ({rc})")
+        rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
+        if rc:
+            raise Mi355xError(f"graph_compute failed ({rc})")
         return g["logits"]
 
     def step(self, token: int, pos: int, use_graph: bool = True):

@@ -81,6 +81,7 @@ enum mi355x_type {
     MI355X_TYPE_Q6_K = 14,
     MI355X_TYPE_Q8_K = 15,
     MI355X_TYPE_I32  = 26,
+    MI355X_TYPE_I64  = 27,   /* cell indices of mi355x_attn_batch / ATTN_BATCH only */
 };
 
 enum mi355x_status {
@@ -386,8 +387,38 @@ int mi355x_attn_impl(int impl);
 /* Prompt attention selector (A/B runs, parity of both): MI355X_ATTN_GROUP (default: one
  * workgroup per kv group and token, the group's query heads sharing every K/V load, where
  * n_head/n_head_kv <= 8 and its LDS fits) or MI355X_ATTN_HEAD (one per query head and
- * token). Returns the previous value, or MI355X_E_INVAL. */
+ * token). mi355x_attn_batch follows the same selector. Returns the previous value, or
+ * MI355X_E_INVAL. */
 int mi355x_attn_prompt_impl(int impl);
+/* The same block for a batch whose KV cells and mask are the graph's own inputs (ggml's
+ * SET_ROWS + MUL_MAT + SOFT_MAX(mask) + MUL_MAT): several sequences in one unified cache, or
+ * one sequence whose cells are not its positions (a removed cell, a context shift, a reused
+ * prefix). `a` as for mi355x_attn_prompt (rows per token, pos int32 [n_tokens], rope_row 0;
+ * rope_table has at least n_ctx rows and a position selects only its rope row). Token i's
+ * roped K row and V column are written at cell cells[i]; then every query attends over cells
+ * [0, n_kv) with the score dot * scale + mask[i][c] (additive, as ggml_compute_forward_soft_max
+ * applies it: -INF hides a cell, a finite entry is added; an f16 mask is widened to f32
+ * first). Nothing derives visibility from pos. A cell outside [0, n_ctx) or a position outside
+ * [0, n_ctx) writes nothing and gives that token a NaN output row. Two tokens of one batch on
+ * the same cell is undefined, as in ggml. Cells inside [0, n_kv) must hold finite values
+ * (zero-initialised caches do); nothing at or past n_kv is read. The K rows of hidden cells and
+ * the V chunks of 32-cell blocks without a visible cell are not loaded (exactly the same bits:
+ * csrc/kq_attn_batch.hip). Returns MI355X_E_INVAL for a null pointer, a type outside the list,
+ * n_kv % 32 != 0, n_kv < 32, n_kv > n_ctx, mask_row_bytes below n_kv entries, rope_row != 0 or
+ * n_tokens <= 0 (before any device access), MI355X_E_UNSUPPORTED for a shape the kernels do
+ * not take. */
+typedef struct {
+    mi355x_attn_desc a;          /* q/k/v/out rows per token, pos int32[n_tokens], rope_row 0 */
+    const void *cells; int cells_type;             /* MI355X_TYPE_I32 or I64 (27), [n_tokens] */
+    const void *mask;  int mask_type; size_t mask_row_bytes; /* F16 / F32 */
+    int n_kv, n_tokens;
+} mi355x_attn_batch_desc;
+int mi355x_attn_batch(const mi355x_attn_batch_desc *d, void *stream);
+/* The form mi355x_attn_batch runs for this descriptor: MI355X_ATTN_GROUP (one workgroup per
+ * KV group and token: the group's query heads share every K row, V chunk and mask row; groups
+ * of at most 8 heads whose rows fit 160 KB of LDS) or MI355X_ATTN_HEAD (one per query head and
+ * token), or the MI355X_E_* mi355x_attn_batch would return. No launch, no device access. */
+int mi355x_attn_batch_path(const mi355x_attn_batch_desc *d);
 
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
@@ -408,6 +439,15 @@ int mi355x_attn_prompt_impl(int impl);
  *                token's position, staged with pos; op_params = {n_head, n_head_kv, head_dim, scale bits}
  *                -> f32 [head_dim*n_head]: the non-flash attention block
  *                (set_rows, mul_mat f16, soft_max_ext, mul_mat f16, permute, cont).
+ *   ATTN_BATCH   src0..src6 as ATTN_DECODE for T tokens (q [n_head*head_dim, T], k, v [kvw, T]
+ *                packed rows, pos I32 [T], both caches, the whole rope table [head_dim, n_pos]:
+ *                a position >= n_pos has no rope row), src7 cells I32 or I64 [T], src8 mask F16
+ *                or F32 [>= n_kv, >= T] (nb[1] the row stride); op_params = {n_head, n_head_kv,
+ *                head_dim, scale bits, n_kv} -> f32 [head_dim*n_head, T]: mi355x_attn_batch —
+ *                token i stored at cell cells[i], every query over cells [0, n_kv) under its
+ *                mask row. One launch unit (store + attention), captured and replayed like any
+ *                node: cells, mask and pos are read on the device at run time. It joins none
+ *                of the ATTN_DECODE fusions.
  *   ALL_GATHER   src0 f32 [n] (this rank's contiguous row slice of a row-split MUL_MAT
  *                chain stage) -> f32 [n * world]: the slices of every rank in rank order,
  *                one RCCL ncclAllGather over xGMI on the backend stream (captured in the
@@ -425,8 +465,9 @@ enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
+    MI355X_OP_ATTN_BATCH = 11,
 };
-#define MI355X_MAX_SRC 8
+#define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */
 
 typedef struct mi355x_tensor {
@@ -522,7 +563,8 @@ int mi355x_backend_graph_compute(mi355x_backend_t backend, mi355x_tensor *const 
  *   RESHAPE / VIEW / PERMUTE / TRANSPOSE are aliases (no node);
  *   the non-flash attention block — ROPE(Q), ROPE(K), SET_ROWS(K cache), SET_ROWS
  *   (V cache), MUL_MAT(K cache, Q), SOFT_MAX(kq, mask, scale), MUL_MAT(V cache, kq),
- *   PERMUTE, CONT — becomes ONE ATTN_DECODE node (rope table from the caller);
+ *   PERMUTE, CONT — becomes ONE ATTN_DECODE node (rope table from the caller), or ONE
+ *   ATTN_BATCH node under mi355x_lower_opts.cells_from_graph;
  *   [up, gate] MUL_MAT pairs read by SWIGLU(gate, up) are emitted as [gate, up]
  *   (independent nodes; the order the fused gate/up launch takes).
  * The op numbering is this library's (the adapter maps GGML_OP_* by name). */
@@ -557,7 +599,19 @@ typedef struct {
                                      * [0, pos] and the KQ / KQV views start at cell 0.
                                      * ATTN_DECODE writes cell == pos and attends over
                                      * [0, pos]; with 0 here attention blocks are not
-                                     * lowered (MI355X_E_UNSUPPORTED). */
+                                     * lowered (MI355X_E_UNSUPPORTED) unless
+                                     * cells_from_graph is set. Takes precedence. */
+    int cells_from_graph;           /* (with cells_eq_pos 0) lower an attention block to ONE
+                                     * ATTN_BATCH node that reads the cells (the K SET_ROWS
+                                     * index leaf) and the mask (the SOFT_MAX mask leaf, F16 or
+                                     * F32) on the device; n_kv is the KQ K-view's ne[1]. The
+                                     * lowering cannot read device memory, so the adapter
+                                     * promises, checked on its host copies (cells_match,
+                                     * adapter/mi355x_ggml_mirror.hpp): for every token i and
+                                     * channel ch the transposed-V store's index entry
+                                     * v_idxs[i*kvw + ch] equals ch*kv_size + k_idxs[i], and
+                                     * every k_idxs[i] lies in [0, kv_size). A zero-initialised
+                                     * struct keeps the meaning it had before this field. */
 } mi355x_lower_opts;
 /* Lowers `n` ggml nodes (graph order) into backend nodes. Tensors are written into
  * `arena` (cap entries: nodes and the leaf mirrors they reference); `nodes_out`
