@@ -21,9 +21,9 @@ namespace kq {
 template <int NCOL, bool FUSEDQ, bool DEBUG, int TMASK>
 __global__ void kq_gemv(const GemvArgs a);
 __global__ void kq_quantize_q8K(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
-template <int TMASK, bool FUSEDQ, int PRO>
+template <int TMASK, bool FUSEDQ, int PRO, int LSH>
 __global__ void kq_rows(KQ_ROWS_PARAMS);
-template <int TMASK, bool FUSEDQ, int PRO>
+template <int TMASK, bool FUSEDQ, int PRO, int LSH>
 __global__ void kq_rows_dyn(KQ_ROWS_PARAMS);
 template <bool AM>
 __global__ void kq_quantize_q8L(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
@@ -357,28 +357,34 @@ bool rows_enabled() {
 }
 
 
-template <int TM, bool FQ, int PR>
+template <int TM, bool FQ, int PR, int LS>
 rows_fn rows_inst(bool dyn) {
     if constexpr (TM == 7) {
-        return kq_rows<TM, FQ, PR>;
+        return kq_rows<TM, FQ, PR, LS>;
     } else {
-        return dyn ? kq_rows_dyn<TM, FQ, PR> : kq_rows<TM, FQ, PR>;
+        return dyn ? kq_rows_dyn<TM, FQ, PR, LS> : kq_rows<TM, FQ, PR, LS>;
     }
 }
 
-template <int TM>
-rows_fn rows_pick_pro(bool fusedq, int pro, bool dyn) {
-    if (!fusedq) return rows_inst<TM, false, 0>(dyn);
-    return pro == ROWS_PRO_NORM ? rows_inst<TM, true, 1>(dyn) : pro == ROWS_PRO_SWIGLU ? rows_inst<TM, true, 2>(dyn)
-                                                                                       : rows_inst<TM, true, 0>(dyn);
+template <int TM, int PR>
+rows_fn rows_pick_form(int lsh, bool dyn) {
+    return lsh == 2 ? rows_inst<TM, true, PR, 2>(dyn) : lsh == 1 ? rows_inst<TM, true, PR, 1>(dyn) : rows_inst<TM, true, PR, 0>(dyn);
 }
 
-rows_fn pick_rows(int tmask, bool fusedq, int pro, bool dyn = false) {
+template <int TM>
+rows_fn rows_pick_pro(bool fusedq, int pro, bool dyn, int lsh) {
+    if (!fusedq) return rows_inst<TM, false, 0, 0>(dyn);
+    return pro == ROWS_PRO_NORM ? rows_pick_form<TM, 1>(lsh, dyn) : pro == ROWS_PRO_SWIGLU ? rows_pick_form<TM, 2>(lsh, dyn)
+                                                                                         : rows_pick_form<TM, 0>(lsh, dyn);
+}
+
+// lsh: the fused prologue's form (RowsPlan::lsh), a template parameter of the kernels
+rows_fn pick_rows(int tmask, bool fusedq, int pro, bool dyn, int lsh) {
     switch (tmask) {
-        case 1: return rows_pick_pro<1>(fusedq, pro, dyn);
-        case 2: return rows_pick_pro<2>(fusedq, pro, dyn);
-        case 4: return rows_pick_pro<4>(fusedq, pro, dyn);
-        default: return rows_pick_pro<7>(fusedq, pro, false);
+        case 1: return rows_pick_pro<1>(fusedq, pro, dyn, lsh);
+        case 2: return rows_pick_pro<2>(fusedq, pro, dyn, lsh);
+        case 4: return rows_pick_pro<4>(fusedq, pro, dyn, lsh);
+        default: return rows_pick_pro<7>(fusedq, pro, false, lsh);
     }
 }
 
@@ -409,7 +415,6 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
     if (tmask != 1 && tmask != 2 && tmask != 4) tmask = 7;
     pl.tmask = tmask;
     pl.fusedq = fusedq;
-    pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE);
     a.n_desc = n_desc;
     a.nb = (int)nb;
     for (int i = 0; i < n_desc; ++i) {
@@ -495,6 +500,9 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
         }
     if (rpw > 0x7fffffff / 64) return MI355X_E_UNSUPPORTED;
     a.rpw = (int)(rpw > 0 ? rpw : 1);
+    // the prologue's form, by the row, the waves and the longest stream of the launch
+    pl.lsh = fusedq ? rows_pro_form((int)nb, pl.nwv, (rpw * nb + ROWS_SB - 1) / ROWS_SB).lsh : 0;
+    pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, false, pl.lsh);
     // rows per chain batch: ~ROWS_RECS records, batch ends on a step boundary (bR*nb % 16 == 0)
     int g16 = ROWS_SB;
     while (nb % g16) g16 >>= 1;
@@ -552,7 +560,7 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
             a.rpw = (int)flat;
             pl.lds = (size_t)DL.total;
             pl.grid = dim3((unsigned)n_wg, 1, 1);
-            pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, true);
+            pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, true, pl.lsh);
         }
     }
     return MI355X_OK;
@@ -581,8 +589,9 @@ int launch_rows(const RowsPlan &pl, hipStream_t stream) {
     // request; the kernels read neither gridDim nor blockDim, and the prologue's pass count
     // (passes of 4 superblocks per wave over the activation) is divided here
     const void *x = pl.fusedq ? (const void *)a.x : (const void *)a.xq;
-    const int pass = 4 * pl.nwv;
-    const int qiters = pl.fusedq ? (a.nb + pass - 1) / pass : 0;
+    // (the prologue's form, rows_pro_form at plan time: its lanes per superblock are the kernel's LSH)
+    const int qiters = !pl.fusedq ? 0 : pl.lsh ? 1 : (a.nb + 4 * pl.nwv - 1) / (4 * pl.nwv);
+    if (pl.lsh < 0 || pl.lsh > 2 || (pl.lsh && (!pl.fusedq || a.nb * (16 << pl.lsh) > 64 * pl.nwv))) return MI355X_E_INVAL;
     // cfg's fields are a few bits each: a plan outside them would run another launch silently
     if (pl.nwv < 1 || pl.nwv > ROWS_WAVES || qiters > ROWS_QPASS || a.n_desc < 1 || a.n_desc > MI355X_MAX_FUSED)
         return MI355X_E_INVAL;
@@ -1061,7 +1070,7 @@ int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *w
                                                                 : ROWS_PRO_NONE;
                 rp.a.x2 = ext->x2;
                 rp.a.eps = ext->eps;
-                rp.fn = pick_rows(rp.tmask, true, rp.a.pro, rp.dyn);
+                rp.fn = pick_rows(rp.tmask, true, rp.a.pro, rp.dyn, rp.lsh);
                 for (int i = 0; i < n; ++i) {
                     rp.a.res[i] = ext->residual[i];
                     rp.a.n_rows[i] = (int)d[i].n_rows;
@@ -1397,6 +1406,32 @@ int mi355x_debug_stream(const void *buf, size_t bytes, void *sink, void *stream)
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MI355X_OK : (int)e;
+}
+
+int mi355x_rows_prologue_plan(int64_t k, int waves, int64_t steps, int *lanes, int *passes) {
+    if (k <= 0 || k % QK || waves < 1 || waves > ROWS_WAVES || steps < 0) return MI355X_E_INVAL;
+    const int64_t nb = k / QK;
+    if (nb > kRowsFusedMaxNb) return MI355X_E_UNSUPPORTED;
+    const RowsProForm f = rows_pro_form((int)nb, waves, steps);
+    if (f.passes > ROWS_QPASS) return MI355X_E_UNSUPPORTED;  // (plan_rows runs such a row on ROWS_WAVES waves)
+    if (lanes) *lanes = 16 << f.lsh;
+    if (passes) *passes = f.passes;
+    return MI355X_OK;
+}
+
+int mi355x_debug_rows_prologue(int prologue, const float *x, const float *x2, float eps, int64_t k, int waves, void *out,
+                               size_t out_bytes, void *stream) {
+    if (!x || !out || ((uintptr_t)x & 15u) || ((uintptr_t)out & 15u)) return MI355X_E_INVAL;
+    if (prologue < MI355X_PRO_NONE || prologue > MI355X_PRO_SWIGLU) return MI355X_E_INVAL;
+    if (prologue != MI355X_PRO_NONE && (!x2 || ((uintptr_t)x2 & 15u))) return MI355X_E_INVAL;
+    if (prologue == MI355X_PRO_RMS_NORM && !(eps >= 0.0f)) return MI355X_E_INVAL;
+    const int rc = mi355x_rows_prologue_plan(k, waves, 0, nullptr, nullptr);
+    if (rc) return rc;
+    const int64_t nb = k / QK;
+    if (out_bytes < (size_t)nb * Q8L_STRIDE) return MI355X_E_INVAL;
+    if (!device_ok()) return MI355X_E_NODEVICE;
+    const int pro = prologue == MI355X_PRO_RMS_NORM ? ROWS_PRO_NORM : prologue == MI355X_PRO_SWIGLU ? ROWS_PRO_SWIGLU : ROWS_PRO_NONE;
+    return launch_rows_prologue_dbg(pro, x, x2, eps, (int)nb, waves, (uint8_t *)out, (hipStream_t)stream);
 }
 
 int mi355x_debug_block_partials(int src0_type, const void *src0, int64_t ne00, int64_t ne01, size_t nb01,

@@ -114,6 +114,28 @@ constexpr int ROWS_PF = KQ_ROWS_PF;  // touches per wave when a.pf != 0
 __host__ __device__ constexpr int rows_cfg(int nwv, int qiters, int n_desc, int diag) {
     return nwv | (qiters << 8) | (n_desc << 12) | (diag << 16);
 }
+// The fused prologue's mapping of the activation row to the workgroup: 16 << lsh lanes
+// quantize one superblock (16, 8 or 4 consecutive values per lane), the widest form with
+// nb * lanes <= 64 * nwv, so that one pass covers the row with as many of the workgroup's
+// waves as it has; rows that fill the workgroup anyway keep 16 lanes per superblock and as
+// many passes of 4 * nwv superblocks as they need (up to ROWS_QPASS). `steps`: the most
+// 16-superblock steps any wave of the launch streams. The wide forms pay in the short,
+// latency-bound launches (K = 2048 at 6 waves -0.13 to -0.2 us, K = 5632 at 12 waves -0.27 us);
+// a launch whose waves stream many steps loses with them (Llama-3-8B gate + up, 10 steps per
+// wave: 9.88 -> 10.94 us, profiles/r08_prologue_ab.txt) and keeps 16 lanes.
+constexpr int ROWS_PRO_WIDE_STEPS = 2;  // wide forms up to this many steps per wave
+struct RowsProForm {
+    int lsh, passes;
+};
+#ifndef KQ_ROWS_PRO_WIDE
+#define KQ_ROWS_PRO_WIDE 1  // 0: 16 lanes per superblock for every row (experiment builds: the A/B baseline)
+#endif
+__host__ __device__ constexpr RowsProForm rows_pro_form(int nb, int nwv, int64_t steps = 0) {
+    const bool wide = KQ_ROWS_PRO_WIDE && steps <= ROWS_PRO_WIDE_STEPS;
+    return wide && nb * 64 <= 64 * nwv   ? RowsProForm{2, 1}
+           : wide && nb * 32 <= 64 * nwv ? RowsProForm{1, 1}
+                                         : RowsProForm{0, (nb + 4 * nwv - 1) / (4 * nwv)};
+}
 
 struct RowsArgs {
     // ---- the run the kernels read at entry (one batch)

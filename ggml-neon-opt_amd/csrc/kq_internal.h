@@ -34,6 +34,7 @@ struct RowsPlan {
     int tmask;
     bool fusedq;
     int nwv;  // waves per workgroup (one workgroup per CU): ROWS_WAVES, or ROWS_WAVES_SMALL
+    int lsh = 0;  // fused prologue: 16 << lsh lanes per superblock (rows_pro_form; the kernel's LSH)
     bool dyn = false;  // kq_rows_dyn: rows claimed from a per-workgroup counter
 };
 // Row-stream decode GEMV (kq_rows): returns MI355X_E_UNSUPPORTED when the rows are
@@ -43,6 +44,8 @@ struct RowsPlan {
 int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, RowsPlan &pl,
               int waves_per_cu = 0);
 int launch_rows(const RowsPlan &pl, hipStream_t stream);
+int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps, int nb, int waves, uint8_t *out,
+                             hipStream_t s);
 bool rows_enabled();
 int launch_quantize(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
                     hipStream_t stream);

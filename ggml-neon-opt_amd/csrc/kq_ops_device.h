@@ -5,15 +5,19 @@
 //   * ggml_v_silu: x / (1 + v_expf(0 - x)) with a correctly rounded divide;
 //   * binary16 FMA / add (vfmaq_f16 / vaddq_f16) on the f16 ALU (v_fma_f16, v_add_f16:
 //     IEEE, one rounding, f16 denormals kept);
-//   * the RMS-norm sum of squares: a fast FIXED order shared by every kernel that
-//     computes it (kq_rms_norm and the kq_rows norm prologue): per 16 consecutive
-//     elements a sequential double sum, a balanced tree over the 16 groups of a
-//     256-element superblock, then superblocks in order. ggml sums sequentially in
-//     double (ggml_compute_forward_rms_norm_f32); the two orders can differ only in
-//     the last bits of the double, which reach the float mean only when it lies
-//     within ~2^-40 (relative) of a rounding boundary — detected exactly
-//     (rms_mean_ambiguous), and then the sum is redone in ggml's sequential order,
-//     so the float mean is the reference's in every case.
+//   * the RMS-norm sum of squares: a fast tree order, then a guard. Each kernel has its own
+//     fast order, every one a sum of the n non-negative squares with one rounding per add:
+//     kq_rms_norm, the prompt's batched norm and kq_layer sum 16 consecutive elements in
+//     order, a balanced tree over the 16 groups of a 256-element superblock, then
+//     superblocks in order; the kq_rows norm prologue sums the 16, 8 or 4 consecutive
+//     elements a lane holds (its form, kq_rows.hip RowsPrologue), a xor tree over the
+//     superblock's 16, 32 or 64 lanes, then superblocks in order (every aligned group of 16
+//     elements is a subtree of each). ggml sums sequentially in double
+//     (ggml_compute_forward_rms_norm_f32); any two such orders can differ only in the last
+//     bits of the double, which reach the float mean only when it lies within ~2^-40
+//     (relative) of a rounding boundary — detected exactly (rms_mean_ambiguous, whose bound
+//     holds for any order of at most n + 32 adds per value), and then the sum is redone in
+//     ggml's sequential order, so the float mean is the reference's in every case.
 #pragma once
 
 #include <hip/hip_runtime.h>

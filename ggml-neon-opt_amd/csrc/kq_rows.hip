@@ -18,9 +18,10 @@
 //  * when a batch of bR rows is complete, lane r replays row r's records in
 //    superblock order (the serial fp32 chain, 64 rows per instruction);
 //  * the activation is quantized to Q8_K once per workgroup into LDS (aligned
-//    304-B "Q8L" blocks: d @0, qs @16, bsums @272): 16 lanes per superblock, x
-//    loaded by inline-asm global loads issued before the weight DMAs (K <= 8192);
-//    above that kq_quantize_q8L writes Q8L blocks to a workspace, copied by DMA.
+//    304-B "Q8L" blocks: d @0, qs @16, bsums @272): 16, 32 or 64 lanes per superblock
+//    by the row and the workgroup's waves (RowsPrologue below), x loaded by inline-asm
+//    global loads issued before the weight DMAs; rows past the fused limit are written
+//    as Q8L blocks to a workspace by kq_quantize_q8L and copied by DMA.
 #include <hip/hip_ext.h>
 
 #include "kq_internal.h"
@@ -368,9 +369,245 @@ __device__ __forceinline__ RowsHot rows_resolve(const RowsLead &ld, int gw) {
     return h;
 }
 
+// ---------------------------------------------------------------- the FUSEDQ prologue
+// The activation of a fused-quantization launch, shared by kq_rows, kq_rows_dyn and
+// kq_rows_prologue_dbg: load() issues the wave's inline-asm loads of x (and of x2: the norm
+// weight / up) from the leading parameters alone; the caller issues what it wants in flight
+// behind them and waits for them (ONE constant s_waitcnt vmcnt per path, tools/vmem_lint.py);
+// finish() pins the registers, applies the transform (PRO) and quantizes into the
+// workgroup's Q8L row in LDS. The caller's workgroup barrier completes the row.
+//
+// Mapping (rows_pro_form, chosen by the host per launch; LSH is a template parameter of the
+// kernels: one form's code per kernel, a form picked at run time cost the token 3.5 %,
+// profiles/r08_prologue_ab.txt): 16 << LSH lanes hold one superblock, 16 >> LSH consecutive
+// values per lane (4 >> LSH 16-B loads of x). LSH = 0: 4 superblocks per wave and pass, up to
+// ROWS_QPASS passes of 4 * nwv superblocks; LSH = 1, 2: one pass of 2 or 1 superblocks per
+// wave over as many waves as the row has superblocks for.
+template <int LSH>
+struct RowsPrologue {
+    static constexpr int NP = LSH ? 1 : ROWS_QPASS;  // passes held in registers
+    static constexpr int NL = 4 >> LSH;              // 16-B loads per pass and vector
+    static constexpr int LP = 16 << LSH;             // lanes per superblock
+    static constexpr int SPW = 4 >> LSH;             // superblocks per wave and pass
+    // The registers of the asm loads: claimed by an empty asm (no instruction, no value: a pass
+    // the wave does not load is never read) and loaded in place (gload16_into), so a register
+    // is the same one on the path that loads it and on the path that skips the load.
+    u32x4 xv[NP][NL];
+    u32x4 x2v[NP][NL];  // norm weight / up, same elements as xv
+    int qw = 0;  // passes this wave loads (wave-uniform): pass i while its first slot lies in the row
+    int nb, pass, rot, wave, lane;
+
+    // slot of pass i held by this lane, its lane index within the superblock, slot -> superblock:
+    // rotated by the workgroup (ROWS_X_ROT) so the grid does not read the activation's lines in
+    // one order; slots past the row read superblock nb-1's place and store nothing
+    __device__ __forceinline__ int slot(int i) const { return pass * i + SPW * wave + (lane >> (4 + LSH)); }
+    __device__ __forceinline__ int sl() const { return lane & (LP - 1); }
+    __device__ __forceinline__ int sbk(int j) const {
+        const int b = (j < nb ? j : nb - 1) + rot;
+        return b >= nb ? b - nb : b;
+    }
+
+    // ASM: the kernels' inline-asm loads, which the caller waits for; false (the debug kernel):
+    // ordinary loads that the compiler waits for itself
+    template <int PRO, bool ASM = true>
+    __device__ __forceinline__ void load(const RowsLead &ld, int wave_, int lane_, int rot_, int diag) {
+        nb = ld.nb, pass = SPW * ld.nwv, rot = rot_, wave = wave_, lane = lane_;
+        const float *const x = (const float *)ld.x;
+        // (diag bit 4: read x again instead of x2, timing only)
+        const float *const x2 = (diag & 16) ? x : ld.x2;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) qw += (i < ld.qiters && pass * i + SPW * wave < nb) ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+                asm volatile("" : "=v"(xv[i][k]));
+                if (PRO != ROWS_PRO_NONE) asm volatile("" : "=v"(x2v[i][k]));
+            }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            if (i < qw) {  // waves past the row load nothing
+                const int64_t e = (int64_t)sbk(slot(i)) * QK + (16 >> LSH) * sl();
+#pragma unroll
+                for (int k = 0; k < NL; ++k) {
+                    if (ASM) gload16_into(xv[i][k], x + e + 4 * k);
+                    else xv[i][k] = *(const u32x4 *)(x + e + 4 * k);
+                }
+                if (PRO != ROWS_PRO_NONE) {
+#pragma unroll
+                    for (int k = 0; k < NL; ++k) {
+                        if (ASM) gload16_into(x2v[i][k], x2 + e + 4 * k);
+                        else x2v[i][k] = *(const u32x4 *)(x2 + e + 4 * k);
+                    }
+                }
+            }
+        }
+    }
+
+    // the asm loads are invisible to the compiler: pin their registers past each wait
+    template <int PRO>
+    __device__ __forceinline__ void pin() {
+        if constexpr (LSH == 0) {
+            asm volatile("" : "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[1][0]),
+                         "+v"(xv[1][1]), "+v"(xv[1][2]), "+v"(xv[1][3]), "+v"(xv[2][0]), "+v"(xv[2][1]),
+                         "+v"(xv[2][2]), "+v"(xv[2][3]));
+        } else {
+#pragma unroll
+            for (int k = 0; k < NL; ++k) asm volatile("" : "+v"(xv[0][k]));
+        }
+        if (PRO != ROWS_PRO_NONE) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+#pragma unroll
+                for (int k = 0; k < NL; ++k) asm volatile("" : "+v"(x2v[i][k]));
+        }
+    }
+
+    // ggml_vec_swiglu_f32 on pass i: silu(gate) * up
+    __device__ __forceinline__ void swiglu_pass(int i) {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) xv[i][k] = swiglu4(xv[i][k], x2v[i][k]);
+    }
+
+    // this lane's 16 >> LSH values of pass i, in order
+    __device__ __forceinline__ void values(int i, float v[4 * NL]) const {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            v[4 * k] = __uint_as_float(xv[i][k].x), v[4 * k + 1] = __uint_as_float(xv[i][k].y);
+            v[4 * k + 2] = __uint_as_float(xv[i][k].z), v[4 * k + 3] = __uint_as_float(xv[i][k].w);
+        }
+    }
+
+    // rms_norm then MUL by the norm weight: this wave's superblock sums of squares to `sums`
+    // (LDS), a workgroup barrier, the row's total in superblock order; the rare rows whose
+    // float mean could depend on the order are summed in ggml's order (each wave; the test is
+    // workgroup-uniform: every wave sums the same LDS values). The fast order: the lane's
+    // 16 >> LSH squares in order, then the xor tree over the superblock's lanes, so every
+    // aligned group of 16 elements is a subtree for every LSH.
+    __device__ __forceinline__ void norm(double *sums, const float *x, float eps) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            if (i < qw) {  // wave-uniform: this wave holds x of the pass
+                const int j = slot(i);
+                double sq = 0.0;
+                if (j < nb) {
+                    float v[4 * NL];
+#pragma unroll
+                    for (int k = 0; k < NL; ++k) {
+                        v[4 * k] = __uint_as_float(xv[i][k].x), v[4 * k + 1] = __uint_as_float(xv[i][k].y);
+                        v[4 * k + 2] = __uint_as_float(xv[i][k].z), v[4 * k + 3] = __uint_as_float(xv[i][k].w);
+                    }
+                    if constexpr (LSH == 0) {
+                        sq = sumsq16(v);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4 * NL; ++k) sq += (double)(v[k] * v[k]);
+                    }
+                }
+                // DPP / lane swaps, every lane of the wave active
+                if constexpr (LSH == 0) sq = row16_sum(sq);
+                else sq = sblk_sum<LP>(sq);
+                if (j < nb && sl() == 0) sums[sbk(j)] = sq;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        double tot = seq_sum_lanes(sums, nb, lane);  // superblocks in order
+        if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
+            tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
+        const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
+        const float scale = 1.0f / sqrtf(mean + eps);
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            if (i < qw)
+#pragma unroll
+                for (int k = 0; k < NL; ++k) xv[i][k] = normmul4(xv[i][k], x2v[i][k], scale);
+    }
+
+    // pass i (wave-uniform, i < qw) into the Q8L row at `act`
+    __device__ __forceinline__ void quantize_pass(int i, uint8_t *act) {
+        const int j = slot(i);
+        uint8_t *const qb = act + Q8L_STRIDE * sbk(j);
+        if constexpr (LSH == 0) {
+            u32x4 cur[4];  // one copy of the quantizer; pick the pass's registers
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                // values, not lvalues: a pick among members would become a pick of addresses (scratch)
+                const u32x4 p0 = xv[0][k], p1 = xv[1][k], p2 = xv[2][k];
+                cur[k] = i == 0 ? p0 : i == 1 ? p1 : p2;
+            }
+            if (j < nb) quant16_store(cur, lane & 15, qb);
+        } else {
+            float v[4 * NL];
+            values(0, v);
+            quant_wide_store<LP>(v, sl(), qb, j < nb);
+        }
+    }
+
+    // After the caller's wait for the loads: transform and quantize every pass. `sx`
+    // (diagnostic builds): the time between the two. diag bits 32 / 64 (timing only): skip
+    // the transform / the quantization.
+    template <int PRO>
+    __device__ __forceinline__ void finish(uint8_t *act, double *sums, const float *x, float eps, int diag, bool stamp,
+                                           uint64_t &sx) {
+        pin<PRO>();
+        if (diag & 32) {
+        } else if (PRO == ROWS_PRO_SWIGLU) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+                if (i < qw) swiglu_pass(i);
+        } else if (PRO == ROWS_PRO_NORM) {
+            norm(sums, x, eps);
+        }
+        if (stamp) sx = __builtin_amdgcn_s_memrealtime();
+        if (!(diag & 64)) {
+#pragma unroll 1
+            for (int i = 0; i < qw; ++i) quantize_pass(i, act);
+        }
+    }
+};
+
+// The shared prologue alone (mi355x_debug_rows_prologue): one workgroup of cfg's waves runs
+// load (with ordinary loads) / finish and copies its Q8L image (nb * 304 B) to `out`, so that a test sees the
+// bytes the GEMV's dot products read (d and every q of a block flip together with a wrong
+// tie sign: the GEMV's outputs cannot show it).
+template <int PRO, int LSH>
+__global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_prologue_dbg(const float *x, const float *x2, int nb, int cfg,
+                                                                        float eps, uint8_t *out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RowsLead ld = rows_lead(x, x2, nullptr, nullptr, nb, 0, 1, cfg, 0, 0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    RowsPrologue<LSH> pg;
+    pg.template load<PRO, false>(ld, wave, lane, 0, 0);
+    uint64_t sx = 0;
+    pg.template finish<PRO>(smem, (double *)(smem + nb * Q8L_STRIDE), x, eps, 0, false, sx);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const int ng = nb * (Q8L_STRIDE / 16);
+    for (int k = threadIdx.x; k < ng; k += ld.nwv * 64) ((u32x4 *)out)[k] = ((const u32x4 *)smem)[k];
+}
+
+template <int PRO>
+static auto rows_prologue_dbg_fn(int lsh) {
+    return lsh == 2 ? kq_rows_prologue_dbg<PRO, 2> : lsh == 1 ? kq_rows_prologue_dbg<PRO, 1> : kq_rows_prologue_dbg<PRO, 0>;
+}
+
+int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps, int nb, int waves, uint8_t *out,
+                             hipStream_t s) {
+    const RowsProForm f = rows_pro_form(nb, waves);
+    const int cfg = rows_cfg(waves, f.passes, 1, 0);
+    const size_t lds = (size_t)nb * Q8L_STRIDE + (size_t)nb * 8;
+    const auto fn = pro == ROWS_PRO_NORM ? rows_prologue_dbg_fn<ROWS_PRO_NORM>(f.lsh)
+                    : pro == ROWS_PRO_SWIGLU ? rows_prologue_dbg_fn<ROWS_PRO_SWIGLU>(f.lsh)
+                                             : rows_prologue_dbg_fn<ROWS_PRO_NONE>(f.lsh);
+    allow_lds((const void *)fn, lds);
+    hipLaunchKernelGGL(fn, dim3(1), dim3(waves * 64), lds, s, x, x2, nb, cfg, eps, out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MI355X_OK : (int)e;
+}
+
 // `resolve` returns the wave's RowsHot: called after the activation loads are issued (they
 // need the leading parameters only), or before the call where the type depends on the matrix.
-template <int TYPE, bool FUSEDQ, int PRO, int TMASK, class Resolve>
+template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH, class Resolve>
 __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
                                           uint64_t st0, Resolve resolve) {
     constexpr int BSZ = block_bytes(TYPE);
@@ -384,40 +621,10 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const int q = lane >> 2, s = lane & 3;
 
     // ---- activation loads first: every wave's requests leave before any argument fetch
-    const int PASS = 4 * nwv;  // superblocks per workgroup pass
     // KQ_ROWS_XMODE >= 0: the prologue fixed at compile time (experiment builds)
     const int xm = !FUSEDQ ? 0 : KQ_ROWS_XMODE >= 0 ? KQ_ROWS_XMODE : a.xmode;
-    u32x4 xv[ROWS_QPASS][4] = {};
-    u32x4 x2v[ROWS_QPASS][4] = {};  // norm weight / up, same elements as xv
-    // passes this wave loads (wave-uniform): pass i while slot 4*wave of it lies in the row
-    int qw = 0;
-    // slot j of the passes -> superblock: rotated by the workgroup (ROWS_X_ROT) so the
-    // grid does not read the activation's lines in one order; slots past the row read
-    // superblock nb-1's place and store nothing
-    const int rot = (xm & ROWS_X_ROT) ? (int)(blockIdx.x % (unsigned)nb) : 0;
-    auto sbk = [&](int j) {
-        int b = (j < nb ? j : nb - 1) + rot;
-        return b >= nb ? b - nb : b;
-    };
-    if (FUSEDQ) {
-        const float *const x = (const float *)ld.x;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < ld.qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) {
-            if (i < qw) {  // waves past the row load nothing
-                const int b = sbk(PASS * i + 4 * wave + (lane >> 4));
-                const float *xp = x + (int64_t)b * QK + 16 * (lane & 15);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
-                if (PRO != ROWS_PRO_NONE) {  // (diag bit 4: read x again instead of x2, timing only)
-                    const float *x2p = ((RDIAG(ld) & 16) ? x : ld.x2) + (int64_t)b * QK + 16 * (lane & 15);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
-                }
-            }
-        }
-    }
+    RowsPrologue<LSH> pg;
+    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, (xm & ROWS_X_ROT) ? (int)(blockIdx.x % (unsigned)nb) : 0, RDIAG(ld));
     const RowsHot h = resolve();
     const uint64_t sa = RSTAMP();  // diagnostics: arguments fetched
     const int bR = h.bR;
@@ -472,7 +679,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     if (FUSEDQ) {
         const float *const x = (const float *)ld.x;
         constexpr int pro = PRO;
-        constexpr int PL = PRO != ROWS_PRO_NONE ? 8 : 4;  // loads per pass
+        constexpr int PL = (PRO != ROWS_PRO_NONE ? 2 : 1) * RowsPrologue<LSH>::NL;  // loads per pass
         // residual of the fused ADD: one row per lane, fetched with the activation. Issued
         // on every path (a dummy read of x without a residual) so that no branch joins a
         // register whose asm load is still in flight; rv stays live until the flush waits
@@ -516,31 +723,15 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         }
         // vector-memory operations younger than the last pass's activation loads
         const int tail = 1 + NI * pre0 + (pf_on ? ROWS_PF : 0);
-        // the asm loads are invisible to the compiler: pin their registers past each wait
-        auto pin = [&]() {
-            asm volatile("" : "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[1][0]),
-                         "+v"(xv[1][1]), "+v"(xv[1][2]), "+v"(xv[1][3]), "+v"(xv[2][0]), "+v"(xv[2][1]),
-                         "+v"(xv[2][2]), "+v"(xv[2][3]));
-            if (pro != ROWS_PRO_NONE) {
-#pragma unroll
-                for (int i = 0; i < ROWS_QPASS; ++i)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(x2v[i][k]));
-            }
-        };
         if (pro != ROWS_PRO_NORM && (xm & ROWS_X_PIPE)) {
             // pass by pass: pass i's transform + quantization overlap the later passes' loads
 #pragma unroll
-            for (int i = 0; i < ROWS_QPASS; ++i) {
-                if (i < qw) {
-                    vm_wait_dyn((qw - 1 - i) * PL + tail);
-                    pin();
-                    if (pro == ROWS_PRO_SWIGLU && !(RDIAG(ld) & 32)) {  // ggml_vec_swiglu_f32: silu(gate) * up
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) xv[i][k] = swiglu4(xv[i][k], x2v[i][k]);
-                    }
-                    const int j = PASS * i + 4 * wave + (lane >> 4);
-                    if (j < nb && !(RDIAG(ld) & 64)) quant16_store(xv[i], lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));
+            for (int i = 0; i < RowsPrologue<LSH>::NP; ++i) {
+                if (i < pg.qw) {
+                    vm_wait_dyn((pg.qw - 1 - i) * PL + tail);
+                    pg.template pin<PRO>();
+                    if (pro == ROWS_PRO_SWIGLU && !(RDIAG(ld) & 32)) pg.swiglu_pass(i);
+                    if (!(RDIAG(ld) & 64)) pg.quantize_pass(i, smem + L.act);
                 }
             }
             if (RSTAMPS(h)) sx = sq = __builtin_amdgcn_s_memrealtime();
@@ -558,57 +749,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             } else {
                 vm_wait_dyn(tail);
             }
-            pin();
-            if (RDIAG(ld) & 32) {  // diagnostics (timing only): skip the transform
-            } else if (pro == ROWS_PRO_SWIGLU) {  // ggml_vec_swiglu_f32: silu(gate) * up
-#pragma unroll
-                for (int i = 0; i < ROWS_QPASS; ++i)
-                    if (i < qw)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) xv[i][k] = swiglu4(xv[i][k], x2v[i][k]);
-            } else if (pro == ROWS_PRO_NORM) {  // rms_norm then MUL by the norm weight
-                double *sums = (double *)(smem + L.sums);
-#pragma unroll
-                for (int i = 0; i < ROWS_QPASS; ++i) {
-                    if (i < qw) {  // wave-uniform: this wave holds x of the pass
-                        const int j = PASS * i + 4 * wave + (lane >> 4);
-                        double sq = 0.0;
-                        if (j < nb) {
-                            float v[16];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                v[4 * k] = __uint_as_float(xv[i][k].x), v[4 * k + 1] = __uint_as_float(xv[i][k].y);
-                                v[4 * k + 2] = __uint_as_float(xv[i][k].z), v[4 * k + 3] = __uint_as_float(xv[i][k].w);
-                            }
-                            sq = sumsq16(v);
-                        }
-                        sq = row16_sum(sq);  // DPP, every lane of the wave active
-                        if (j < nb && (lane & 15) == 0) sums[sbk(j)] = sq;
-                    }
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                double tot = seq_sum_lanes(sums, nb, lane);  // superblocks in order
-                // workgroup-uniform (every wave sums the same LDS values): the rare rows whose
-                // float mean could depend on the order are summed in ggml's order (each wave)
-                if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
-                    tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
-                const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
-                const float scale = 1.0f / sqrtf(mean + h.eps);
-#pragma unroll
-                for (int i = 0; i < ROWS_QPASS; ++i)
-                    if (i < qw)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) xv[i][k] = normmul4(xv[i][k], x2v[i][k], scale);
-            }
-            if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
-#pragma unroll 1
-            for (int i = 0; i < qw; ++i) {  // one copy of the quantizer; pick the pass's registers
-                u32x4 cur[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) cur[k] = i == 0 ? xv[0][k] : i == 1 ? xv[1][k] : xv[2][k];
-                const int j = PASS * i + 4 * wave + (lane >> 4);
-                if (j < nb && !(RDIAG(ld) & 64)) quant16_store(cur, lane & 15, smem + L.act + Q8L_STRIDE * sbk(j));  // (diag 64: timing only)
-            }
+            pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, RDIAG(ld), RSTAMPS(h) != nullptr, sx);
             if (RSTAMPS(h)) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 sq = __builtin_amdgcn_s_memrealtime();
@@ -765,7 +906,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     }
 }
 
-template <int TMASK, bool FUSEDQ, int PRO>
+template <int TMASK, bool FUSEDQ, int PRO, int LSH>
 __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const RowsLead ld = rows_lead(x, x2, w0, res0, nb, waves_total, grid, cfg, rbase0, rrem0);
@@ -777,26 +918,24 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     auto resolve = [&]() { return rows_resolve<TMASK>(ld, gw); };
 
     if (TMASK == 1) {
-        rows_body<Q4_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 2) {
-        rows_body<Q5_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 4) {
-        rows_body<Q6_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
     } else {  // the type is the matrix's: the entry batch first
         const RowsHot h = resolve();
         auto resolved = [&]() { return h; };
-        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
-        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
-        else rows_body<Q4_K, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0, resolved);
+        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
+        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
+        else rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
     }
 }
 
-#define KQ_ROWS_INST(TM, FQ, PR) template __global__ void kq_rows<TM, FQ, PR>(KQ_ROWS_PARAMS);
-#define KQ_ROWS_INST_T(TM)        \
-    KQ_ROWS_INST(TM, true, 0)     \
-    KQ_ROWS_INST(TM, true, 1)     \
-    KQ_ROWS_INST(TM, true, 2)     \
-    KQ_ROWS_INST(TM, false, 0)
+// (the prologue's form LSH: every fused-quantization kernel in its three forms)
+#define KQ_ROWS_INST(TM, FQ, PR, LS) template __global__ void kq_rows<TM, FQ, PR, LS>(KQ_ROWS_PARAMS);
+#define KQ_ROWS_INST_P(TM, PR) KQ_ROWS_INST(TM, true, PR, 0) KQ_ROWS_INST(TM, true, PR, 1) KQ_ROWS_INST(TM, true, PR, 2)
+#define KQ_ROWS_INST_T(TM) KQ_ROWS_INST_P(TM, 0) KQ_ROWS_INST_P(TM, 1) KQ_ROWS_INST_P(TM, 2) KQ_ROWS_INST(TM, false, 0, 0)
 KQ_ROWS_INST_T(1)
 KQ_ROWS_INST_T(2)
 KQ_ROWS_INST_T(4)
@@ -863,7 +1002,7 @@ __device__ __forceinline__ RowsDynHot rows_dyn_resolve() {
     return h;
 }
 
-template <int TYPE, bool FUSEDQ, int PRO, int TMASK>
+template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH>
 __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
                                               uint64_t st0) {
     uint64_t sx = 0, sq = 0, sf = 0;  // diagnostics (KQ_ROWS_DIAG builds): x landed, quantized, first step
@@ -880,29 +1019,8 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
 
     // ---- activation loads first (the leading parameters only), then the entry batch
     const float *const x = (const float *)ld.x;
-    const int PASS = 4 * nwv;
-    u32x4 xv[ROWS_QPASS][4] = {};
-    u32x4 x2v[ROWS_QPASS][4] = {};
-    int qw = 0;
-    if (FUSEDQ) {
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) qw += (i < ld.qiters && PASS * i + 4 * wave < nb) ? 1 : 0;
-#pragma unroll
-        for (int i = 0; i < ROWS_QPASS; ++i) {
-            if (i < qw) {
-                const int j = PASS * i + 4 * wave + (lane >> 4);
-                const int bb = j < nb ? j : nb - 1;
-                const float *xp = x + (int64_t)bb * QK + 16 * (lane & 15);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xv[i][k] = gload16_asm(xp + 4 * k);
-                if (PRO != ROWS_PRO_NONE) {
-                    const float *x2p = ld.x2 + (int64_t)bb * QK + 16 * (lane & 15);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) x2v[i][k] = gload16_asm(x2p + 4 * k);
-                }
-            }
-        }
-    }
+    RowsPrologue<LSH> pg;
+    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, 0, 0);
     const RowsDynHot h = rows_dyn_resolve();
     // (scalars of their own: a pick among struct members becomes a pick of addresses, in scratch)
     const uint8_t *const w0 = ld.w0, *const w1 = h.w1, *const w2 = h.w2, *const w3 = h.w3;
@@ -1042,61 +1160,8 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
         }
         vm_wait<NI + 1>();  // x landed; the residual load and the step's DMAs may be in flight
         if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
-        asm volatile("" : "+v"(xv[0][0]), "+v"(xv[0][1]), "+v"(xv[0][2]), "+v"(xv[0][3]), "+v"(xv[1][0]),
-                     "+v"(xv[1][1]), "+v"(xv[1][2]), "+v"(xv[1][3]), "+v"(xv[2][0]), "+v"(xv[2][1]),
-                     "+v"(xv[2][2]), "+v"(xv[2][3]));
-        if (PRO != ROWS_PRO_NONE) {
-#pragma unroll
-            for (int i = 0; i < ROWS_QPASS; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(x2v[i][k]));
-        }
-        if (PRO == ROWS_PRO_SWIGLU) {
-#pragma unroll
-            for (int i = 0; i < ROWS_QPASS; ++i)
-                if (i < qw)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) xv[i][k] = swiglu4(xv[i][k], x2v[i][k]);
-        } else if (PRO == ROWS_PRO_NORM) {
-            double *sums = (double *)(smem + L.sums);
-#pragma unroll
-            for (int i = 0; i < ROWS_QPASS; ++i) {
-                if (i < qw) {
-                    const int j = PASS * i + 4 * wave + (lane >> 4);
-                    double sq = 0.0;
-                    if (j < nb) {
-                        float v[16];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            v[4 * k] = __uint_as_float(xv[i][k].x), v[4 * k + 1] = __uint_as_float(xv[i][k].y);
-                            v[4 * k + 2] = __uint_as_float(xv[i][k].z), v[4 * k + 3] = __uint_as_float(xv[i][k].w);
-                        }
-                        sq = sumsq16(v);
-                    }
-                    sq = row16_sum(sq);
-                    if (j < nb && (lane & 15) == 0) sums[j] = sq;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            double tot = seq_sum_lanes(sums, nb, lane);
-            if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
-                tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
-            const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
-            const float scale = 1.0f / sqrtf(mean + h.eps);
-#pragma unroll
-            for (int i = 0; i < ROWS_QPASS; ++i)
-                if (i < qw)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) xv[i][k] = normmul4(xv[i][k], x2v[i][k], scale);
-        }
-#pragma unroll 1
-        for (int i = 0; i < qw; ++i) {
-            u32x4 cur[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) cur[k] = i == 0 ? xv[0][k] : i == 1 ? xv[1][k] : xv[2][k];
-            const int j = PASS * i + 4 * wave + (lane >> 4);
-            if (j < nb) quant16_store(cur, lane & 15, smem + L.act + Q8L_STRIDE * j);
-        }
+        uint64_t sxt = 0;  // (kq_rows' stamp between transform and quantization: not taken here)
+        pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, 0, false, sxt);
         if (RSTAMPS(h)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             sq = __builtin_amdgcn_s_memrealtime();
@@ -1236,7 +1301,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
         }
     }
 }
-template <int TMASK, bool FUSEDQ, int PRO>
+template <int TMASK, bool FUSEDQ, int PRO, int LSH>
 __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_dyn(KQ_ROWS_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const RowsLead ld = rows_lead(x, x2, w0, res0, nb, waves_total, grid, cfg, rbase0, rrem0);
@@ -1244,15 +1309,14 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_dyn(KQ_ROWS_PARAMS) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int TYPE = TMASK == 1 ? Q4_K : TMASK == 2 ? Q5_K : Q6_K;
-    rows_dyn_body<TYPE, FUSEDQ, PRO, TMASK>(a, ld, smem, wave, lane, st0);
+    rows_dyn_body<TYPE, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0);
 }
 
-#define KQ_ROWS_DYN_INST(TM, FQ, PR) template __global__ void kq_rows_dyn<TM, FQ, PR>(KQ_ROWS_PARAMS);
-#define KQ_ROWS_DYN_INST_T(TM)        \
-    KQ_ROWS_DYN_INST(TM, true, 0)     \
-    KQ_ROWS_DYN_INST(TM, true, 1)     \
-    KQ_ROWS_DYN_INST(TM, true, 2)     \
-    KQ_ROWS_DYN_INST(TM, false, 0)
+#define KQ_ROWS_DYN_INST(TM, FQ, PR, LS) template __global__ void kq_rows_dyn<TM, FQ, PR, LS>(KQ_ROWS_PARAMS);
+#define KQ_ROWS_DYN_INST_P(TM, PR) \
+    KQ_ROWS_DYN_INST(TM, true, PR, 0) KQ_ROWS_DYN_INST(TM, true, PR, 1) KQ_ROWS_DYN_INST(TM, true, PR, 2)
+#define KQ_ROWS_DYN_INST_T(TM) \
+    KQ_ROWS_DYN_INST_P(TM, 0) KQ_ROWS_DYN_INST_P(TM, 1) KQ_ROWS_DYN_INST_P(TM, 2) KQ_ROWS_DYN_INST(TM, false, 0, 0)
 KQ_ROWS_DYN_INST_T(1)
 KQ_ROWS_DYN_INST_T(2)
 KQ_ROWS_DYN_INST_T(4)

@@ -97,6 +97,105 @@ __device__ __forceinline__ void quant16_store(const u32x4 v[4], int l, uint8_t *
     if (l == 0) *(float *)qb = d;
 }
 
+// ---- one superblock on 32 or 64 lanes (kq_rows' prologue when the row leaves waves idle)
+// Rows of 16 lanes exchanged by gfx950's lane swaps: v_permlane16_swap with both operands
+// v leaves rows {0, 0, 2, 2} of v in one result and rows {1, 1, 3, 3} in the other, so one
+// op of the two combines each row with its neighbour (xor 16) in every lane;
+// v_permlane32_swap does the same with the wave's halves (xor 32).
+__device__ __forceinline__ void swap_rows16(uint32_t v, uint32_t &a, uint32_t &b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    a = r[0], b = r[1];
+}
+__device__ __forceinline__ void swap_rows32(uint32_t v, uint32_t &a, uint32_t &b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    a = r[0], b = r[1];
+}
+// Reduction over the LP (32, 64) lanes of a superblock: every lane ends with the result.
+template <int LP, typename Op>
+__device__ __forceinline__ int sblk_reduce(int v, Op op) {
+    static_assert(LP == 32 || LP == 64, "lanes per superblock");
+    v = row16_reduce(v, op);
+    uint32_t a, b;
+    swap_rows16((uint32_t)v, a, b);
+    v = op((int)a, (int)b);
+    if (LP == 64) {
+        swap_rows32((uint32_t)v, a, b);
+        v = op((int)a, (int)b);
+    }
+    return v;
+}
+// The same tree in double (xor 1, 2, 4, 8, 16[, 32]; addition is commutative, so every lane
+// of the superblock ends with the same bits). Every lane of the wave must be active.
+template <int LP>
+__device__ __forceinline__ double sblk_sum(double v) {
+    static_assert(LP == 32 || LP == 64, "lanes per superblock");
+    v = row16_sum(v);
+#pragma unroll
+    for (int step = 0; step < (LP == 64 ? 2 : 1); ++step) {
+        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        uint32_t la, lb, ha, hb;
+        if (step == 0) swap_rows16((uint32_t)u, la, lb), swap_rows16((uint32_t)(u >> 32), ha, hb);
+        else swap_rows32((uint32_t)u, la, lb), swap_rows32((uint32_t)(u >> 32), ha, hb);
+        v = __builtin_bit_cast(double, ((uint64_t)ha << 32) | la) + __builtin_bit_cast(double, ((uint64_t)hb << 32) | lb);
+    }
+    return v;
+}
+
+// quant16_store's quantizer with one superblock on LP = 32 or 64 lanes: lane l of the
+// superblock owns the VP = 256 / LP consecutive values x[VP l .. VP l + VP). The same
+// quantize_row_q8_K_ref semantics: the first-index scan of a +-amax tie orders the keys
+// 2 (VP l + k) + sign over every lane of the superblock (across its 16-lane rows), bsums are
+// the sums of 16 / VP neighbouring lanes. Every lane of the wave runs it (the reductions
+// cross 16-lane rows); `st`: this lane's superblock lies in the row and is stored.
+template <int LP>
+__device__ __forceinline__ void quant_wide_store(const float *x, int l, uint8_t *qb, bool st) {
+    constexpr int VP = 256 / LP;
+    float mp = 0.f, mn = 0.f;
+#pragma unroll
+    for (int k = 0; k < VP; ++k) {
+        mp = fmaxf(mp, x[k]);
+        mn = fmaxf(mn, -x[k]);
+    }
+    const int mpb = sblk_reduce<LP>(__float_as_int(mp), [](int a, int c) { return a > c ? a : c; });
+    const int mnb = sblk_reduce<LP>(__float_as_int(mn), [](int a, int c) { return a > c ? a : c; });
+    const float m = __int_as_float(mpb > mnb ? mpb : mnb);
+    bool neg = mnb > mpb;
+    if (__any(mpb == mnb && mpb != 0)) {  // a tie somewhere in the wave (wave-uniform: the swaps need every lane)
+        uint32_t key = 0xffffffffu;
+#pragma unroll
+        for (int k = VP - 1; k >= 0; --k)
+            if (fabsf(x[k]) == m) key = 2u * (uint32_t)(VP * l + k) + (x[k] < 0.f ? 1u : 0u);
+        key = (uint32_t)sblk_reduce<LP>((int)key, [](int a, int c) { return (uint32_t)a < (uint32_t)c ? a : c; });
+        if (mpb == mnb && mpb != 0) neg = (key & 1u) != 0;
+    }
+    const float maxv = neg ? -m : m;
+    const float iscale = -127.f / maxv;
+    uint32_t q[VP / 4];
+    int bsum = 0;
+#pragma unroll
+    for (int k = 0; k < VP / 4; ++k) {
+        q[k] = qbyte(iscale, x[4 * k]) | (qbyte(iscale, x[4 * k + 1]) << 8) | (qbyte(iscale, x[4 * k + 2]) << 16) |
+               (qbyte(iscale, x[4 * k + 3]) << 24);
+        bsum = sdot4(q[k], 0x01010101u, bsum);
+    }
+    float d = 1.f / iscale;
+    if (m == 0.f) {  // `if (!amax)`: d = 0, qs = 0 (bsums then 0)
+#pragma unroll
+        for (int k = 0; k < VP / 4; ++k) q[k] = 0u;
+        bsum = 0;
+        d = 0.f;
+    }
+    // 16 values = 16 / VP neighbouring lanes (exact integer adds)
+    bsum += __builtin_amdgcn_update_dpp(bsum, bsum, 0xB1, 0xF, 0xF, false);
+    if (VP == 4) bsum += __builtin_amdgcn_update_dpp(bsum, bsum, 0x4E, 0xF, 0xF, false);
+    if (st) {
+        if (VP == 8) *(uint2 *)(qb + 16 + 8 * l) = make_uint2(q[0], q[VP / 4 - 1]);
+        else *(uint32_t *)(qb + 16 + 4 * l) = q[0];
+        if (!(l & (16 / VP - 1))) *(int16_t *)(qb + 272 + 2 * (l / (16 / VP))) = (int16_t)bsum;
+        if (l == 0) *(float *)qb = d;
+    }
+}
+
 __device__ __forceinline__ uint32_t gload4_asm(const float *p) {
     uint32_t r;
     asm volatile("global_load_dword %0, %1, off" : "=v"(r) : "v"(p) : "memory");
@@ -127,6 +226,13 @@ __device__ __forceinline__ u32x4 gload16_asm(const float *p) {
     u32x4 r;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
     return r;
+}
+
+// The same load into a register that already holds a value (tied in/out): on a path that skips
+// the load the register keeps that value, so no copy joins the two paths while the load is in
+// flight (with a fresh "=v" destination the compiler placed such copies behind the load).
+__device__ __forceinline__ void gload16_into(u32x4 &r, const float *p) {
+    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(r) : "v"(p) : "memory");
 }
 
 // ---------------------------------------------------------------- per-type quad partials

@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_attn_prompt",
     "mi355x_attn_prompt_impl",
     "mi355x_attn_batch", "mi355x_attn_batch_path",
+    "mi355x_rows_prologue_plan", "mi355x_debug_rows_prologue",
 )
 
 
@@ -181,6 +182,10 @@ def lib():
     L.mi355x_debug_block_partials.restype = i32
     L.mi355x_debug_stream.argtypes = [vp, sz, vp, vp]
     L.mi355x_debug_stream.restype = i32
+    L.mi355x_rows_prologue_plan.argtypes = [i64, i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.mi355x_rows_prologue_plan.restype = i32
+    L.mi355x_debug_rows_prologue.argtypes = [i32, vp, vp, ctypes.c_float, i64, i32, vp, sz, vp]
+    L.mi355x_debug_rows_prologue.restype = i32
     L.mi355x_backend_init.argtypes = [i32]
     L.mi355x_backend_init.restype = vp
     L.mi355x_backend_free.argtypes = [vp]
@@ -430,6 +435,30 @@ def prefill_precision(p=-1):
 def gemv_waves(waves):
     """kq_rows waves per workgroup: 0 = by launch size, else fixed (1..12); returns the previous."""
     return int(lib().mi355x_gemv_waves(waves))
+
+
+def rows_prologue_plan(k, waves, steps=0):
+    """(lanes per superblock, passes) of the fused GEMV prologue for a k-element row on a
+    workgroup of `waves` waves whose longest wave streams `steps` 16-superblock steps
+    (mi355x_rows_prologue_plan: the host's choice, no device), or the error code
+    (E_UNSUPPORTED: the row does not fit that many waves)."""
+    lanes, passes = ctypes.c_int(0), ctypes.c_int(0)
+    rc = int(lib().mi355x_rows_prologue_plan(k, waves, steps, ctypes.byref(lanes), ctypes.byref(passes)))
+    return (lanes.value, passes.value) if rc == 0 else rc
+
+
+def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=None):
+    """The fused GEMV prologue alone on one workgroup of `waves` waves
+    (mi355x_debug_rows_prologue): the Q8L image of x after `prologue`, a uint8 tensor
+    [K / 256, 304] (d f32 @0, 256 int8 @16, 16 int16 bsums @272)."""
+    _require_device()
+    torch = _torch()
+    K = x.shape[-1]
+    out = torch.empty((K // QK_K, 304), dtype=torch.uint8, device=x.device)
+    _check(lib().mi355x_debug_rows_prologue(prologue, x.data_ptr(), x2.data_ptr() if x2 is not None else None, eps, K,
+                                            waves, out.data_ptr(), out.numel(), _stream(stream)),
+           "mi355x_debug_rows_prologue")
+    return out
 
 
 DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_PF", "GEMV_XMODE", "GEMV_SMALL_MB", "GEMV_WPC",

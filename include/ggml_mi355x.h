@@ -215,6 +215,21 @@ int mi355x_gemv_fused_ext(const mi355x_gemv_desc *descs, int n_desc, const float
 int mi355x_debug_stream(const void *buf, size_t bytes, void *sink, void *stream);
 int mi355x_debug_block_partials(int src0_type, const void *src0, int64_t ne00, int64_t ne01,
                                 size_t nb01, const void *src1_q8, int32_t *out, void *stream);
+/* The fused GEMV prologue's mapping of a k-element activation row to a workgroup of `waves`
+ * waves whose longest wave streams `steps` steps of 16 superblocks (no launch, no device
+ * access): *lanes = lanes that quantize one superblock (16, 32 or 64: the widest with
+ * k/256 * lanes <= 64 * waves where steps <= 2, the short launches; 16 for longer streams),
+ * *passes = passes over the row (1 for 32 and 64 lanes). MI355X_E_UNSUPPORTED where `waves`
+ * waves cannot hold the row (more than 3 passes: the GEMV then runs 12 waves). The debug
+ * entry below runs the form of steps = 0. */
+int mi355x_rows_prologue_plan(int64_t k, int waves, int64_t steps, int *lanes, int *passes);
+/* Debug/parity hook: the fused GEMV prologue alone. One workgroup of `waves` waves loads x
+ * (and x2), applies `prologue` (MI355X_PRO_*: x2 = norm weight / up, x = gate) and quantizes
+ * to Q8_K exactly as the decode GEMV does before its barrier, then copies the workgroup's
+ * image to out: k/256 blocks of 304 B (d f32 @0, 256 int8 @16, 16 int16 bsums @272).
+ * Device pointers, 16-B aligned; out_bytes >= k/256 * 304. */
+int mi355x_debug_rows_prologue(int prologue, const float *x, const float *x2, float eps, int64_t k, int waves,
+                               void *out, size_t out_bytes, void *stream);
 
 /* ------------------------------------------------------------ profiling */
 /* Per-launch kernel timing. While enabled, every GEMV/quantize launch made
