@@ -11,8 +11,10 @@
 //     order, a balanced tree over the 16 groups of a 256-element superblock, then
 //     superblocks in order; the kq_rows norm prologue sums the 16, 8 or 4 consecutive
 //     elements a lane holds (its form, kq_rows.hip RowsPrologue), a xor tree over the
-//     superblock's 16, 32 or 64 lanes, then superblocks in order (every aligned group of 16
-//     elements is a subtree of each). ggml sums sequentially in double
+//     superblock's 16, 32 or 64 lanes, then the superblocks as a xor tree where their number
+//     is a power of two <= 64 (tree_sum_lanes, kq_rows_device.h: at most 16 + 6 + 6 adds per
+//     value) and in order otherwise (every aligned group of 16 elements is a subtree of
+//     each). ggml sums sequentially in double
 //     (ggml_compute_forward_rms_norm_f32); any two such orders can differ only in the last
 //     bits of the double, which reach the float mean only when it lies within ~2^-40
 //     (relative) of a rounding boundary — detected exactly (rms_mean_ambiguous, whose bound

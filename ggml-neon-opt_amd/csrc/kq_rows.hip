@@ -47,6 +47,13 @@
 #define RSTAMPS(h) ((uint64_t *)nullptr)
 #define RSTAMP() ((uint64_t)0)
 #endif
+// Stamp slots per wave (tools/stamps.py): entry, ring filled, loop end, exit, transformed,
+// quantized, first step, arguments fetched (kq_rows_dyn: units taken), x landed, and the norm
+// interval's sums published, barrier passed, scale known, then the passes of x the wave holds.
+constexpr int ROWS_STAMP_SLOTS = 16;
+struct NormStamps {
+    uint64_t pub = 0, bar = 0, scale = 0;
+};
 
 #ifndef KQ_ROWS_XMODE
 #define KQ_ROWS_XMODE 0  // fused-quantization prologue (ROWS_X_* bits); -1: a.xmode at run time
@@ -68,6 +75,23 @@
 // Llama-3-8B +3.1 %. 1: the masked DMA with the old wait; 0: both as before (experiments).
 #ifndef KQ_ROWS_MASKED
 #define KQ_ROWS_MASKED 2
+#endif
+// The norm prologue's steps, each a build constant of its own (A/B per step: make variant-rows,
+// profiles/r09_norm_ab.txt); 0 is the form before the step.
+//  NORM_SKIP   waves that hold no part of the row go from the norm's barrier straight to
+//              their ring fill (no total, guard, scale or transform);
+//  NORM_LATE   wide forms: scale from the fast total, transform into registers of their own,
+//              quantize and store, and only then the exactness guard; an ambiguous row is
+//              redone from the preserved x and its blocks overwritten;
+//  NORM_TREE   the row's total as a tree over the superblock sums (nb a power of two <= 64);
+#ifndef KQ_ROWS_NORM_SKIP
+#define KQ_ROWS_NORM_SKIP 1
+#endif
+#ifndef KQ_ROWS_NORM_LATE
+#define KQ_ROWS_NORM_LATE 1
+#endif
+#ifndef KQ_ROWS_NORM_TREE
+#define KQ_ROWS_NORM_TREE 1
 #endif
 #ifndef KQ_ROWS_LINT_BREAK
 #define KQ_ROWS_LINT_BREAK 0  // 1: drop the activation wait (a lint self-test build, never run)
@@ -479,12 +503,16 @@ struct RowsPrologue {
     }
 
     // rms_norm then MUL by the norm weight: this wave's superblock sums of squares to `sums`
-    // (LDS), a workgroup barrier, the row's total in superblock order; the rare rows whose
-    // float mean could depend on the order are summed in ggml's order (each wave; the test is
-    // workgroup-uniform: every wave sums the same LDS values). The fast order: the lane's
-    // 16 >> LSH squares in order, then the xor tree over the superblock's lanes, so every
-    // aligned group of 16 elements is a subtree for every LSH.
-    __device__ __forceinline__ void norm(double *sums, const float *x, float eps) {
+    // (LDS), a workgroup barrier, the row's total from them on every wave that holds a part of
+    // the row (NORM_SKIP: a wave without one goes on to its ring fill; it has joined the
+    // barrier, so every wave passes the same barriers). The fast order: the lane's 16 >> LSH
+    // squares in order, the xor tree over the superblock's lanes (every aligned group of 16
+    // elements is a subtree for every LSH), then the superblocks as a tree where nb is a power
+    // of two <= 64 (NORM_TREE: at most 16 + 6 + 6 adds per value), else in order. The rare rows
+    // whose float mean could depend on the order (rms_mean_ambiguous, whose bound holds for any
+    // order of at most n + 32 adds per value) are summed again in ggml's order, by each wave:
+    // the test is workgroup-uniform, every wave sums the same LDS values by the same instructions.
+    __device__ __forceinline__ void norm_publish(double *sums) {
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             if (i < qw) {  // wave-uniform: this wave holds x of the pass
@@ -510,17 +538,87 @@ struct RowsPrologue {
                 if (j < nb && sl() == 0) sums[sbk(j)] = sq;
             }
         }
+    }
+    __device__ __forceinline__ double norm_total(const double *sums) const {
+        if (KQ_ROWS_NORM_TREE && nb <= 64 && (nb & (nb - 1)) == 0) return tree_sum_lanes(sums, nb, lane);
+        return seq_sum_lanes(sums, nb, lane);  // superblocks in order
+    }
+    static __device__ __forceinline__ float norm_scale(double tot, int64_t n, float eps) {
+        const float mean = (float)div_by_count(tot, n);
+        return 1.0f / sqrtf(mean + eps);
+    }
+
+    // The 16-lane form, and every form without NORM_LATE: total, guard, scale, transform in place.
+    __device__ __forceinline__ void norm(double *sums, const float *x, float eps, NormStamps &ns) {
+        norm_publish(sums);
+        ns.pub = RSTAMP();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        double tot = seq_sum_lanes(sums, nb, lane);  // superblocks in order
-        if (rms_mean_ambiguous(div_by_count(tot, (int64_t)nb * QK), (int64_t)nb * QK))
-            tot = seq_sumsq_wave(x, (int64_t)nb * QK, lane);
-        const float mean = (float)div_by_count(tot, (int64_t)nb * QK);
-        const float scale = 1.0f / sqrtf(mean + eps);
+        ns.bar = RSTAMP();
+        if (KQ_ROWS_NORM_SKIP && qw == 0) return;
+        const int64_t n = (int64_t)nb * QK;
+        double tot = norm_total(sums);
+        if (rms_mean_ambiguous(div_by_count(tot, n), n)) tot = seq_sumsq_wave(x, n, lane);
+        float scale = norm_scale(tot, n, eps);
+        if (KQ_ROWS_DIAG) asm volatile("" : "+v"(scale));  // (the stamp behind the value)
+        ns.scale = RSTAMP();
 #pragma unroll
         for (int i = 0; i < NP; ++i)
             if (i < qw)
 #pragma unroll
                 for (int k = 0; k < NL; ++k) xv[i][k] = normmul4(xv[i][k], x2v[i][k], scale);
+    }
+
+    // the wide forms' one pass, transformed into `t`, into the Q8L row at `act`
+    __device__ __forceinline__ void quantize_wide(const u32x4 t[NL], uint8_t *act) {
+        const int j = slot(0);
+        float v[4 * NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            v[4 * k] = __uint_as_float(t[k].x), v[4 * k + 1] = __uint_as_float(t[k].y);
+            v[4 * k + 2] = __uint_as_float(t[k].z), v[4 * k + 3] = __uint_as_float(t[k].w);
+        }
+        quant_wide_store<LP>(v, sl(), act + Q8L_STRIDE * sbk(j), j < nb);
+    }
+
+    // The wide forms (NORM_LATE): the guard after the quantized row is stored. Scale from the
+    // fast total, transform into registers of their own (x stays), quantize and store; then the
+    // guard, and on an ambiguous row the sum in ggml's order, the transform and the quantization
+    // again from x, over this wave's own blocks (same lanes, same addresses, LDS in order). The
+    // decision is the same on every wave that holds x, so no barrier is added; the caller's
+    // closing barrier publishes whichever blocks were stored last.
+    __device__ __forceinline__ void norm_late(uint8_t *act, double *sums, const float *x, float eps, int diag, bool stamp,
+                                              uint64_t &sx, NormStamps &ns) {
+        static_assert(LSH >= 1 && NP == 1, "one pass in registers");
+        norm_publish(sums);
+        ns.pub = RSTAMP();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        ns.bar = RSTAMP();
+        if (KQ_ROWS_NORM_SKIP && qw == 0) {
+            if (stamp) sx = __builtin_amdgcn_s_memrealtime();
+            return;
+        }
+        const int64_t n = (int64_t)nb * QK;
+        const double md = div_by_count(norm_total(sums), n);
+        float scale = 1.0f / sqrtf((float)md + eps);
+        if (KQ_ROWS_DIAG) asm volatile("" : "+v"(scale));
+        ns.scale = RSTAMP();
+        u32x4 t[NL];
+        if (qw) {
+#pragma unroll
+            for (int k = 0; k < NL; ++k) t[k] = normmul4(xv[0][k], x2v[0][k], scale);
+        }
+        if (stamp) sx = __builtin_amdgcn_s_memrealtime();
+        if (qw && !(diag & 64)) quantize_wide(t, act);
+        double mdg = md;
+        asm volatile("" : "+v"(mdg));  // the guard's arithmetic stays behind the stores
+        if (rms_mean_ambiguous(mdg, n)) {  // about one row in 10^4-10^5
+            scale = norm_scale(seq_sumsq_wave(x, n, lane), n, eps);
+            if (qw) {
+#pragma unroll
+                for (int k = 0; k < NL; ++k) t[k] = normmul4(xv[0][k], x2v[0][k], scale);
+                if (!(diag & 64)) quantize_wide(t, act);
+            }
+        }
     }
 
     // pass i (wave-uniform, i < qw) into the Q8L row at `act`
@@ -548,7 +646,7 @@ struct RowsPrologue {
     // the transform / the quantization.
     template <int PRO>
     __device__ __forceinline__ void finish(uint8_t *act, double *sums, const float *x, float eps, int diag, bool stamp,
-                                           uint64_t &sx) {
+                                           uint64_t &sx, NormStamps &ns) {
         pin<PRO>();
         if (diag & 32) {
         } else if (PRO == ROWS_PRO_SWIGLU) {
@@ -556,7 +654,12 @@ struct RowsPrologue {
             for (int i = 0; i < NP; ++i)
                 if (i < qw) swiglu_pass(i);
         } else if (PRO == ROWS_PRO_NORM) {
-            norm(sums, x, eps);
+            if constexpr (KQ_ROWS_NORM_LATE && LSH >= 1) {
+                norm_late(act, sums, x, eps, diag, stamp, sx, ns);
+                return;
+            } else {
+                norm(sums, x, eps, ns);
+            }
         }
         if (stamp) sx = __builtin_amdgcn_s_memrealtime();
         if (!(diag & 64)) {
@@ -580,7 +683,8 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_prologue_dbg(const fl
     RowsPrologue<LSH> pg;
     pg.template load<PRO, false>(ld, wave, lane, 0, 0);
     uint64_t sx = 0;
-    pg.template finish<PRO>(smem, (double *)(smem + nb * Q8L_STRIDE), x, eps, 0, false, sx);
+    NormStamps ns;
+    pg.template finish<PRO>(smem, (double *)(smem + nb * Q8L_STRIDE), x, eps, 0, false, sx, ns);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const int ng = nb * (Q8L_STRIDE / 16);
     for (int k = threadIdx.x; k < ng; k += ld.nwv * 64) ((u32x4 *)out)[k] = ((const u32x4 *)smem)[k];
@@ -675,7 +779,8 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const int pre_cap = pre_req < D ? pre_req : D;  // never more than the ring holds
     // min(T, pre_cap) written so that the compiler sees 0 <= pre0 <= pre_cap (T >= 0)
     const int pre0 = T >= pre_cap ? pre_cap : (T > 0 ? T : 0);
-    uint64_t sx = 0, sq = 0, sf = 0;  // diagnostics: x landed, quantized, first step computed
+    uint64_t sx = 0, sq = 0, sf = 0, sl = 0;  // diagnostics: transformed, quantized, first step computed, x landed
+    NormStamps ns;
     if (FUSEDQ) {
         const float *const x = (const float *)ld.x;
         constexpr int pro = PRO;
@@ -734,7 +839,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                     if (!(RDIAG(ld) & 64)) pg.quantize_pass(i, smem + L.act);
                 }
             }
-            if (RSTAMPS(h)) sx = sq = __builtin_amdgcn_s_memrealtime();
+            if (RSTAMPS(h)) sl = sx = sq = __builtin_amdgcn_s_memrealtime();
         } else {
             // every pass landed: all but the pre0 weight steps (and prefetch touches); with
             // compile-time pre0 / prefetch a constant per path
@@ -749,7 +854,8 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             } else {
                 vm_wait_dyn(tail);
             }
-            pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, RDIAG(ld), RSTAMPS(h) != nullptr, sx);
+            sl = RSTAMP();
+            pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, RDIAG(ld), RSTAMPS(h) != nullptr, sx, ns);
             if (RSTAMPS(h)) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 sq = __builtin_amdgcn_s_memrealtime();
@@ -892,8 +998,8 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         }
     }
     if (RSTAMPS(h)) {
-        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * 8;  // stamp slots sized for the most waves
-        if (lane == 0 && o + 7 < h.stamps_cap) {
+        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;  // sized for the most waves
+        if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
             RSTAMPS(h)[o] = st0;
             RSTAMPS(h)[o + 1] = st1;
             RSTAMPS(h)[o + 2] = st2;
@@ -902,6 +1008,11 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             RSTAMPS(h)[o + 5] = sq;
             RSTAMPS(h)[o + 6] = sf;
             RSTAMPS(h)[o + 7] = sa;
+            RSTAMPS(h)[o + 8] = sl;
+            RSTAMPS(h)[o + 9] = ns.pub;
+            RSTAMPS(h)[o + 10] = ns.bar;
+            RSTAMPS(h)[o + 11] = ns.scale;
+            RSTAMPS(h)[o + 12] = (uint64_t)pg.qw;  // passes of x this wave holds
         }
     }
 }
@@ -1161,7 +1272,8 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
         vm_wait<NI + 1>();  // x landed; the residual load and the step's DMAs may be in flight
         if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
         uint64_t sxt = 0;  // (kq_rows' stamp between transform and quantization: not taken here)
-        pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, 0, false, sxt);
+        NormStamps ns;
+        pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, 0, false, sxt, ns);
         if (RSTAMPS(h)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             sq = __builtin_amdgcn_s_memrealtime();
@@ -1288,8 +1400,8 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
         }
     }
     if (RSTAMPS(h)) {  // the kq_rows stamp layout (tools/stamps.py); slot 7: units this wave took
-        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * 8;
-        if (lane == 0 && o + 7 < h.stamps_cap) {
+        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;
+        if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
             RSTAMPS(h)[o] = st0;
             RSTAMPS(h)[o + 1] = st1;
             RSTAMPS(h)[o + 2] = st2;

@@ -141,6 +141,30 @@ __device__ __forceinline__ double sblk_sum(double v) {
     return v;
 }
 
+// The total of nb <= 64 doubles in LDS, nb a power of two, as a balanced tree (the norm
+// prologue's superblock sums): lane l reads sums[l], then the xor tree over the nb lanes, by
+// DPP within a row of 16 and the lane swaps across rows. Lanes from nb on hold +0.0 and add
+// it to sums that are >= 0 or NaN, which changes no bit, so for nb < 16 the row's tree is the
+// tree over the first nb lanes. Every lane of the wave must be active; returns lane 0's total
+// (wave-uniform).
+__device__ __forceinline__ double tree_sum_lanes(const double *sums, int nb, int lane) {
+    double v = lane < nb ? sums[lane] : 0.0;
+    v = row16_sum(v);
+    if (nb > 16) {  // (uniform)
+        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        uint32_t la, lb, ha, hb;
+        swap_rows16((uint32_t)u, la, lb), swap_rows16((uint32_t)(u >> 32), ha, hb);
+        v = __builtin_bit_cast(double, ((uint64_t)ha << 32) | la) + __builtin_bit_cast(double, ((uint64_t)hb << 32) | lb);
+    }
+    if (nb > 32) {
+        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        uint32_t la, lb, ha, hb;
+        swap_rows32((uint32_t)u, la, lb), swap_rows32((uint32_t)(u >> 32), ha, hb);
+        v = __builtin_bit_cast(double, ((uint64_t)ha << 32) | la) + __builtin_bit_cast(double, ((uint64_t)hb << 32) | lb);
+    }
+    return readlane_f64(v, 0);
+}
+
 // quant16_store's quantizer with one superblock on LP = 32 or 64 lanes: lane l of the
 // superblock owns the VP = 256 / LP consecutive values x[VP l .. VP l + VP). The same
 // quantize_row_q8_K_ref semantics: the first-index scan of a +-amax tie orders the keys

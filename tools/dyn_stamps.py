@@ -37,7 +37,7 @@ for label, typ, K, N in SHAPES:
                 g.mul_mat(typ, ws[(r * 40 + i) % len(ws)], K, x, out=y)
             torch.cuda.synchronize()
             g.lib().mi355x_diag_stamps(None, 0)
-            st = buf.cpu().numpy().astype(np.int64).reshape(-1, 8)[:256 * 12]
+            st = buf.cpu().numpy().astype(np.int64).reshape(-1, 16)[:256 * 12]  # kq_rows.hip ROWS_STAMP_SLOTS
             idx = np.nonzero(st[:, 0])[0]
             st = st[idx]
             wave = idx % 12

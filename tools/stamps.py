@@ -29,6 +29,9 @@ PRO = os.environ.get("STAMPS_PRO", "none")  # none | norm | swiglu: fused prolog
 # the GPU idles between the eager launches of a short kernel and its XCDs wake in turn
 # (tools/xcd_skew.hip: 0.1 .. 1.4 us apart), which the entry stamps then show.
 SLEEP = os.environ.get("STAMPS_SLEEP", "0") == "1"
+# STAMPS_SHAPES="tl q,l3 up": only these rows of SHAPES
+ONLY = [v.strip() for v in os.environ.get("STAMPS_SHAPES", "").split(",") if v.strip()]
+SLOTS = 16  # stamp slots per wave of kq_rows (kq_rows.hip ROWS_STAMP_SLOTS)
 
 
 def main(impl):
@@ -40,6 +43,8 @@ def main(impl):
     gen.manual_seed(3)
     buf = torch.zeros(1 << 20, dtype=torch.int64, device=dev)
     for label, typ, K, N in SHAPES:
+        if ONLY and label not in ONLY:
+            continue
         ws = [random_kquant(typ, N, K, gen, dev) for _ in range(max(2, int(600e6 // (N * K // 256 * 144))))]
         x = torch.randn(1, K, device=dev)
         x2 = torch.rand(K, device=dev) + 0.5
@@ -52,7 +57,7 @@ def main(impl):
                 g.gemv_fused_ext([(typ, w, y[0])], x[0], prologue=pro, x2=x2, eps=1e-5)
         for w in ws:
             mm(w)
-        res = []
+        res, nres = [], []
         for r in range(5):
             buf.zero_()
             torch.cuda.synchronize()
@@ -65,7 +70,7 @@ def main(impl):
                 mm(ws[(r * 60 + i) % len(ws)])
             torch.cuda.synchronize()
             g.lib().mi355x_diag_stamps(None, 0)
-            st = buf.cpu().numpy().astype(np.int64).reshape(-1, 8)
+            st = buf.cpu().numpy().astype(np.int64).reshape(-1, SLOTS if impl == 0 else 8)  # (kq_gemv, kq_kernels.hip: 8 slots)
             if os.environ.get("STAMPS_DUMP") and r == 4:  # raw per-(block, wave) rows for offline analysis
                 np.save(os.environ["STAMPS_DUMP"] + "_" + label.replace(" ", "_") + ".npy", st[:256 * 12])
             st = st[st[:, 0] != 0]
@@ -83,6 +88,16 @@ def main(impl):
                             med(rel[:, 1] - rel[:, 5]), med(rel[ok, 6] - rel[ok, 1]),
                             med(rel[:, 1] - rel[:, 0]), med(rel[:, 2] - rel[:, 1]), np.max(rel[:, 2] - rel[:, 1]),
                             rel[:, 3].max(), rel[:, 2].max(), med(rel[:, 2]), args))
+                # the norm interval of the waves that hold a part of the row (slot 12: passes of x
+                # held): [8] x landed, [9] sums published, [10] barrier passed, [11] scale known,
+                # [4] transformed; waves without x: their whole prologue
+                hx = ok & (st[:, 12] > 0) & (st[:, 11] >= t0)
+                if PRO == "norm" and hx.any():
+                    nx = ok & (st[:, 10] >= t0) & (st[:, 12] == 0)
+                    nres.append((med(rel[hx, 8] - rel[hx, 0]), med(rel[hx, 9] - rel[hx, 8]), med(rel[hx, 10] - rel[hx, 9]),
+                                 med(rel[hx, 11] - rel[hx, 10]), med(rel[hx, 4] - rel[hx, 11]), med(rel[hx, 5] - rel[hx, 4]),
+                                 med(rel[hx, 1] - rel[hx, 0]), float(hx.sum()) / len(st),
+                                 med(rel[nx, 1] - rel[nx, 0]) if nx.any() else float("nan")))
                 continue
             res.append((len(st), rel[:, 0].max(), med(rel[:, 4] - rel[:, 0]), med(rel[:, 5] - rel[:, 4]),
                         med(rel[:, 6] - rel[:, 5]), med(rel[:, 1] - rel[:, 6]),
@@ -93,6 +108,11 @@ def main(impl):
             print(f"{tag} {label:12s} waves={int(a[0]):5d} start_spread={a[1]:5.2f}us | x-wait {a[2]:4.2f} (args {a[12]:4.2f}) quant {a[3]:4.2f} "
                   f"barrier+fill {a[4]:4.2f} = prologue {a[6]:4.2f} | first step {a[5]:4.2f} loop med/max={a[7]:5.2f}/{a[8]:5.2f} "
                   f"loop end med/max={a[11]:6.2f}/{a[10]:6.2f} end={a[9]:6.2f}us")
+            if nres:
+                b = np.array(nres)[1:].mean(0)
+                print(f"{tag} {label:12s}   norm interval, waves with x ({b[7]:4.2f} of all): x landed {b[0]:4.2f} | sums published "
+                      f"{b[1]:4.2f} | barrier passed {b[2]:4.2f} | scale known {b[3]:4.2f} | transformed {b[4]:4.2f} | quantized "
+                      f"{b[5]:4.2f} | prologue {b[6]:4.2f}; waves without x: prologue {b[8]:4.2f}")
             continue
         print(f"{tag} {label:12s} waves={int(a[0]):5d} start_spread={a[1]:5.2f}us | lookup {a[2]:4.2f} issue {a[3]:4.2f} "
               f"wait {a[4]:4.2f} quant {a[5]:4.2f} = prologue {a[6]:4.2f} | loop med/max={a[7]:5.2f}/{a[8]:5.2f} "
