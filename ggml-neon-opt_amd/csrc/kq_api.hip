@@ -21,7 +21,7 @@ namespace kq {
 template <int NCOL, bool FUSEDQ, bool DEBUG, int TMASK>
 __global__ void kq_gemv(const GemvArgs a);
 __global__ void kq_quantize_q8K(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
-template <int TMASK, bool FUSEDQ, int PRO, int LSH>
+template <int TMASK, bool FUSEDQ, int PRO, int LSH, bool SH>
 __global__ void kq_rows(KQ_ROWS_PARAMS);
 template <int TMASK, bool FUSEDQ, int PRO, int LSH>
 __global__ void kq_rows_dyn(KQ_ROWS_PARAMS);
@@ -119,6 +119,7 @@ const KnobDef kKnobs[KNOB_COUNT] = {
     {"GEMV_SMALL_WG", 0}, {"GEMV_FQMAX", (double)kRowsFusedMaxNb},   {"MMF_WAVES", 0},
     {"MMF_ORDER", 0},  {"ATTN_DIAG", 0},     {"LOOPBACK_NOCOPY", 0}, {"ATTN_OPROJ", 1},
     {"AO_NRB", 0},     {"GEMV_DYN", 8},    {"GEMV_DYN_P", 0},      {"GEMV_DYN_STEPS", 16},
+    {"GEMV_SHORT", 1},
 };
 std::atomic<double> g_knob[KNOB_COUNT];
 std::atomic<bool> g_knob_set[KNOB_COUNT];
@@ -357,34 +358,42 @@ bool rows_enabled() {
 }
 
 
+// (sh: the short-stream form, of the statically split fused-quantization kernels only)
 template <int TM, bool FQ, int PR, int LS>
-rows_fn rows_inst(bool dyn) {
+rows_fn rows_inst(bool dyn, bool sh) {
     if constexpr (TM == 7) {
-        return kq_rows<TM, FQ, PR, LS>;
+        if constexpr (FQ) return sh ? kq_rows<TM, FQ, PR, LS, true> : kq_rows<TM, FQ, PR, LS, false>;
+        else return kq_rows<TM, FQ, PR, LS, false>;
     } else {
-        return dyn ? kq_rows_dyn<TM, FQ, PR, LS> : kq_rows<TM, FQ, PR, LS>;
+        if (dyn) return kq_rows_dyn<TM, FQ, PR, LS>;
+        if constexpr (FQ) return sh ? kq_rows<TM, FQ, PR, LS, true> : kq_rows<TM, FQ, PR, LS, false>;
+        else return kq_rows<TM, FQ, PR, LS, false>;
     }
 }
 
 template <int TM, int PR>
-rows_fn rows_pick_form(int lsh, bool dyn) {
-    return lsh == 2 ? rows_inst<TM, true, PR, 2>(dyn) : lsh == 1 ? rows_inst<TM, true, PR, 1>(dyn) : rows_inst<TM, true, PR, 0>(dyn);
+rows_fn rows_pick_form(int lsh, bool dyn, bool sh) {
+    return lsh == 2   ? rows_inst<TM, true, PR, 2>(dyn, sh)
+           : lsh == 1 ? rows_inst<TM, true, PR, 1>(dyn, sh)
+                      : rows_inst<TM, true, PR, 0>(dyn, sh);
 }
 
 template <int TM>
-rows_fn rows_pick_pro(bool fusedq, int pro, bool dyn, int lsh) {
-    if (!fusedq) return rows_inst<TM, false, 0, 0>(dyn);
-    return pro == ROWS_PRO_NORM ? rows_pick_form<TM, 1>(lsh, dyn) : pro == ROWS_PRO_SWIGLU ? rows_pick_form<TM, 2>(lsh, dyn)
-                                                                                         : rows_pick_form<TM, 0>(lsh, dyn);
+rows_fn rows_pick_pro(bool fusedq, int pro, bool dyn, int lsh, bool sh) {
+    if (!fusedq) return rows_inst<TM, false, 0, 0>(dyn, false);
+    return pro == ROWS_PRO_NORM     ? rows_pick_form<TM, 1>(lsh, dyn, sh)
+           : pro == ROWS_PRO_SWIGLU ? rows_pick_form<TM, 2>(lsh, dyn, sh)
+                                    : rows_pick_form<TM, 0>(lsh, dyn, sh);
 }
 
-// lsh: the fused prologue's form (RowsPlan::lsh), a template parameter of the kernels
-rows_fn pick_rows(int tmask, bool fusedq, int pro, bool dyn, int lsh) {
+// lsh: the fused prologue's form (RowsPlan::lsh), sh: the short-stream form (RowsPlan::sh),
+// template parameters of the kernels
+rows_fn pick_rows(int tmask, bool fusedq, int pro, bool dyn, int lsh, bool sh) {
     switch (tmask) {
-        case 1: return rows_pick_pro<1>(fusedq, pro, dyn, lsh);
-        case 2: return rows_pick_pro<2>(fusedq, pro, dyn, lsh);
-        case 4: return rows_pick_pro<4>(fusedq, pro, dyn, lsh);
-        default: return rows_pick_pro<7>(fusedq, pro, false, lsh);
+        case 1: return rows_pick_pro<1>(fusedq, pro, dyn, lsh, sh);
+        case 2: return rows_pick_pro<2>(fusedq, pro, dyn, lsh, sh);
+        case 4: return rows_pick_pro<4>(fusedq, pro, dyn, lsh, sh);
+        default: return rows_pick_pro<7>(fusedq, pro, false, lsh, sh);
     }
 }
 
@@ -502,7 +511,6 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
     a.rpw = (int)(rpw > 0 ? rpw : 1);
     // the prologue's form, by the row, the waves and the longest stream of the launch
     pl.lsh = fusedq ? rows_pro_form((int)nb, pl.nwv, (rpw * nb + ROWS_SB - 1) / ROWS_SB).lsh : 0;
-    pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, false, pl.lsh);
     // rows per chain batch: ~ROWS_RECS records, batch ends on a step boundary (bR*nb % 16 == 0)
     int g16 = ROWS_SB;
     while (nb % g16) g16 >>= 1;
@@ -510,6 +518,19 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
     int bR_full = (int)(ROWS_RECS / nb) / u * u;
     if (bR_full < u) bR_full = u;
     a.bR = a.rpw <= bR_full ? a.rpw : bR_full;
+    // the short-stream form: every matrix's longest stream fits the ring of its type, and one
+    // chain batch covers a wave's rows (GEMV_SHORT 0: the generic form, A/B runs). The plan
+    // keeps the steps and depth of the matrix with the least room (depth - steps).
+    pl.steps = 0, pl.depth = 0;
+    for (int i = 0; i < n_desc; ++i) {
+        if (wv[i] == 0) continue;
+        const int st = (int)(((int64_t)(a.rbase[i] + (a.rrem[i] ? 1 : 0)) * nb + ROWS_SB - 1) / ROWS_SB);
+        const int dp = rows_depth(d[i].type);
+        if (!pl.depth || dp - st < pl.depth - pl.steps || (dp - st == pl.depth - pl.steps && st > pl.steps))
+            pl.steps = st, pl.depth = dp;
+    }
+    pl.sh = fusedq && knob(KNOB_GEMV_SHORT) != 0 && rows_short_form(pl.steps, pl.depth, a.bR, a.rpw);
+    pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, false, pl.lsh, pl.sh);
     const RowsLayout L = rows_layout((int)nb, tmask, a.bR, a.rpw, pl.nwv);
     if ((size_t)L.total > kMaxLds) return MI355X_E_UNSUPPORTED;
     pl.lds = (size_t)L.total;
@@ -560,7 +581,8 @@ int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, Row
             a.rpw = (int)flat;
             pl.lds = (size_t)DL.total;
             pl.grid = dim3((unsigned)n_wg, 1, 1);
-            pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, true, pl.lsh);
+            pl.sh = false;
+            pl.fn = pick_rows(tmask, fusedq, ROWS_PRO_NONE, true, pl.lsh, false);
         }
     }
     return MI355X_OK;
@@ -593,6 +615,8 @@ int launch_rows(const RowsPlan &pl, hipStream_t stream) {
     const int qiters = !pl.fusedq ? 0 : pl.lsh ? 1 : (a.nb + 4 * pl.nwv - 1) / (4 * pl.nwv);
     if (pl.lsh < 0 || pl.lsh > 2 || (pl.lsh && (!pl.fusedq || a.nb * (16 << pl.lsh) > 64 * pl.nwv))) return MI355X_E_INVAL;
     // cfg's fields are a few bits each: a plan outside them would run another launch silently
+    // (the short form's kernel issues nothing after its barrier and replays one batch)
+    if (pl.sh && (!pl.fusedq || pl.dyn || !rows_short_form(pl.steps, pl.depth, a.bR, a.rpw))) return MI355X_E_INVAL;
     if (pl.nwv < 1 || pl.nwv > ROWS_WAVES || qiters > ROWS_QPASS || a.n_desc < 1 || a.n_desc > MI355X_MAX_FUSED)
         return MI355X_E_INVAL;
     const int cfg = rows_cfg(pl.nwv, qiters, a.n_desc, a.diag & 0x1ff);
@@ -1070,7 +1094,7 @@ int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *w
                                                                 : ROWS_PRO_NONE;
                 rp.a.x2 = ext->x2;
                 rp.a.eps = ext->eps;
-                rp.fn = pick_rows(rp.tmask, true, rp.a.pro, rp.dyn, rp.lsh);
+                rp.fn = pick_rows(rp.tmask, true, rp.a.pro, rp.dyn, rp.lsh, rp.sh);
                 for (int i = 0; i < n; ++i) {
                     rp.a.res[i] = ext->residual[i];
                     rp.a.n_rows[i] = (int)d[i].n_rows;
@@ -1416,6 +1440,31 @@ int mi355x_rows_prologue_plan(int64_t k, int waves, int64_t steps, int *lanes, i
     if (f.passes > ROWS_QPASS) return MI355X_E_UNSUPPORTED;  // (plan_rows runs such a row on ROWS_WAVES waves)
     if (lanes) *lanes = 16 << f.lsh;
     if (passes) *passes = f.passes;
+    return MI355X_OK;
+}
+
+int mi355x_rows_stream_plan(const int *types, const int64_t *n_rows, int n, int64_t k, int batch_rows, int *steps,
+                            int *depth, int *form) {
+    if (!types || !n_rows || n < 1 || n > MI355X_MAX_FUSED || batch_rows < 0) return MI355X_E_INVAL;
+    // (the plan reads no weights: a placeholder address with the alignment of a GGUF tensor)
+    alignas(16) static const uint8_t dummy_w[16] = {0};
+    static float dummy_y;
+    mi355x_gemv_desc d[MI355X_MAX_FUSED];
+    if (k <= 0 || k % QK) return MI355X_E_INVAL;
+    for (int i = 0; i < n; ++i) {
+        const int bb = block_bytes(types[i]);
+        if (!bb) return MI355X_E_UNSUPPORTED;
+        d[i] = {types[i], dummy_w, n_rows[i], (size_t)(k / QK) * bb, &dummy_y};
+    }
+    if (k / QK > kRowsFusedMaxNb) return MI355X_E_UNSUPPORTED;
+    RowsPlan pl;
+    const int rc = plan_rows(d, n, k, true, pl);
+    if (rc) return rc;
+    if (batch_rows > 0 && batch_rows < pl.a.bR)  // a smaller chain batch than the plan's
+        pl.sh = pl.sh && rows_short_form(pl.steps, pl.depth, batch_rows, pl.a.rpw);
+    if (steps) *steps = pl.steps;
+    if (depth) *depth = pl.depth;
+    if (form) *form = pl.dyn ? MI355X_ROWS_CLAIMED : pl.sh ? MI355X_ROWS_SHORT : MI355X_ROWS_LONG;
     return MI355X_OK;
 }
 

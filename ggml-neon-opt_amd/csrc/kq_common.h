@@ -137,6 +137,14 @@ __host__ __device__ constexpr RowsProForm rows_pro_form(int nb, int nwv, int64_t
                                          : RowsProForm{0, (nb + 4 * nwv - 1) / (4 * nwv)};
 }
 
+// The short-stream form of kq_rows (its template parameter SH), chosen by the host per launch:
+// every matrix's longest wave streams no more steps than the ring of its type holds (steps <=
+// depth, for the matrix with the least room: the whole stream is issued before the prologue's
+// barrier and nothing after it), and one chain batch covers a wave's rows (bR >= rpw). Only the fused-quantization kernels have the form.
+__host__ __device__ constexpr bool rows_short_form(int64_t steps, int depth, int bR, int rpw) {
+    return steps <= depth && bR >= rpw;
+}
+
 struct RowsArgs {
     // ---- the run the kernels read at entry (one batch)
     int bR;           // rows per chain batch (bR*nb % 16 == 0 unless bR >= rpw)

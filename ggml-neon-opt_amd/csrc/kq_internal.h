@@ -36,6 +36,10 @@ struct RowsPlan {
     int nwv;  // waves per workgroup (one workgroup per CU): ROWS_WAVES, or ROWS_WAVES_SMALL
     int lsh = 0;  // fused prologue: 16 << lsh lanes per superblock (rows_pro_form; the kernel's LSH)
     bool dyn = false;  // kq_rows_dyn: rows claimed from a per-workgroup counter
+    // the longest wave's 16-superblock steps and the ring depth of its type, of the matrix
+    // with the least room in its ring, and the short-stream form (rows_short_form; the kernel's SH)
+    int steps = 0, depth = 0;
+    bool sh = false;
 };
 // Row-stream decode GEMV (kq_rows): returns MI355X_E_UNSUPPORTED when the rows are
 // not contiguous or not aligned for it (callers then use kq_gemv). waves_per_cu = 0:
@@ -149,6 +153,7 @@ enum Knob {
     KNOB_GEMV_DYN,         // kq_rows_dyn when a wave gets at least this many units (and 16 steps) on average (0: never)
     KNOB_GEMV_DYN_P,       // kq_rows_dyn: static units per wave (0: a ring's worth; A/B only)
     KNOB_GEMV_DYN_STEPS,   // kq_rows_dyn AUTO: 16-superblock steps per wave at least (with GEMV_DYN units)
+    KNOB_GEMV_SHORT,       // kq_rows short-stream form where the plan allows it (1); 0: the generic form (A/B)
     KNOB_COUNT
 };
 double knob(Knob k);

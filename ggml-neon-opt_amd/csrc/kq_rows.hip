@@ -24,6 +24,8 @@
 //    as Q8L blocks to a workspace by kq_quantize_q8L and copied by DMA.
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "kq_internal.h"
 #include "kq_ops_device.h"
 #include "kq_rows_device.h"
@@ -49,7 +51,8 @@
 #endif
 // Stamp slots per wave (tools/stamps.py): entry, ring filled, loop end, exit, transformed,
 // quantized, first step, arguments fetched (kq_rows_dyn: units taken), x landed, and the norm
-// interval's sums published, barrier passed, scale known, then the passes of x the wave holds.
+// interval's sums published, barrier passed, scale known, the passes of x the wave holds, and the
+// interval after the barrier: first step's wait passed, chain started, stores issued.
 constexpr int ROWS_STAMP_SLOTS = 16;
 struct NormStamps {
     uint64_t pub = 0, bar = 0, scale = 0;
@@ -92,6 +95,19 @@ struct NormStamps {
 #endif
 #ifndef KQ_ROWS_NORM_TREE
 #define KQ_ROWS_NORM_TREE 1
+#endif
+// The short-stream form (template parameter SH, rows_short_form in kq_common.h: every wave's
+// stream fits its ring and one chain batch covers its rows), each step a build constant of its
+// own (A/B per step: make variant-rows, profiles/r10_short_ab.txt); 0 is the generic code.
+//  SHORT_UNROLL  at most D steps straight-line, the wait of each a constant (0: a loop with
+//                the wait picked by the steps still in flight);
+//  SHORT_LANE    lane r keeps row r's result: residual add and store from the register, LDS
+//                staging only for the SWIGLU epilogue's gate values.
+#ifndef KQ_ROWS_SHORT_UNROLL
+#define KQ_ROWS_SHORT_UNROLL 1
+#endif
+#ifndef KQ_ROWS_SHORT_LANE
+#define KQ_ROWS_SHORT_LANE 1
 #endif
 #ifndef KQ_ROWS_LINT_BREAK
 #define KQ_ROWS_LINT_BREAK 0  // 1: drop the activation wait (a lint self-test build, never run)
@@ -711,9 +727,15 @@ int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps
 
 // `resolve` returns the wave's RowsHot: called after the activation loads are issued (they
 // need the leading parameters only), or before the call where the type depends on the matrix.
-template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH, class Resolve>
+//
+// SH, the short-stream form (the host's choice per launch, rows_short_form): every wave of the
+// launch streams at most D steps, so its whole stream is issued before the prologue's barrier
+// and nothing is issued after it, and its rows are one chain batch. The steps run without ring
+// wrap, batch bookkeeping or issue; integer sums, records and the chain are the generic form's.
+template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH, bool SH, class Resolve>
 __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
                                           uint64_t st0, Resolve resolve) {
+    static_assert(!SH || FUSEDQ, "the short form is built for the fused-quantization launches");
     constexpr int BSZ = block_bytes(TYPE);
     constexpr int GRAN = rows_gran(TYPE);
     constexpr int NI = rows_ni(TYPE);
@@ -747,6 +769,28 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const uint8_t *s16 = src - mis;
     const uint8_t *last16 =
         G > 0 ? (const uint8_t *)((uintptr_t)(src + (int64_t)G * BSZ - 1) & ~(uintptr_t)15) : s16;
+
+    // SH: the steps' state, none of which needs the activation: the quad's superblock e_g of the
+    // stream (q in step 0), its block and row-in-batch (one division where a step holds whole
+    // rows), the LDS offsets of its weight block, activation block and record, and what a step
+    // of 16 superblocks advances (row, block) by. They stand in front of the activation wait in
+    // the source; pinning them there by an empty asm changed nothing for the token
+    // (profiles/r10_short_ab.txt section 2) and was taken out.
+    int e_outs = L.outs + wave * L.outs_stride, e_a16 = 0, e_b16 = ROWS_SB;
+    int e_g = q, e_io = q, e_rr = 0, e_blk = 0, e_act = 0, e_rec = 0;
+    if constexpr (SH) {
+        if (nb <= ROWS_SB) {  // uniform
+            e_a16 = (int)((unsigned)ROWS_SB / (unsigned)nb);
+            e_b16 = ROWS_SB - e_a16 * nb;
+            e_rr = (int)((unsigned)q / (unsigned)nb);
+            e_io = q - e_rr * nb;
+        }
+        e_blk = L.ring + wave * L.ring_stride + (int)mis + q * BSZ;
+        e_act = L.act + e_io * Q8L_STRIDE;
+        // (24-bit multiply: the 64-bit multiply-add the compiler picks for io * bR + rr names a
+        // register pair whose unused half can be the residual load's, in flight here)
+        e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(Rec);
+    }
 
     // L2 prefetch (uniform per wave): only streams longer than the ring, fused path
     const bool pf_on = FUSEDQ && (KQ_ROWS_L2PF < 0 ? a.pf != 0 : KQ_ROWS_L2PF != 0) && T > D + 1;
@@ -870,9 +914,153 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         for (int j = 0; j < pre0; ++j) issue();
         vm_wait_k<NI>(pre0);
     }
-    while (it_ < D && it_ < T) issue();
+    if constexpr (SH && KQ_ROWS_PRE0 == 1 && KQ_ROWS_L2PF == 0) {
+        // the rest of the stream (T <= D): step j into slot j, every granule clamped to the last
+#pragma unroll
+        for (int j = 1; j < D; ++j)
+            if (j < T) {
+                const uint8_t *base = s16 + j * (ROWS_SB * BSZ) + 16 * lane;
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    const uint8_t *p = base + 1024 * i;
+                    if (i + 1 < NI || lane < GRAN - 64 * (NI - 1))
+                        dma16_nt(p < last16 ? p : last16, (LDS void *)(ring + j * SLOT + 1024 * i));
+                }
+            }
+    } else {
+        while (it_ < D && it_ < T) issue();
+    }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // Q8_K row complete (no vmcnt drain)
     const uint64_t st1 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
+    uint64_t st2 = 0, sw = 0, sc = 0, ss = 0;  // diagnostics: loop end, first wait passed, chain start, stores issued
+    auto put_stamps = [&]() {
+        if (RSTAMPS(h)) {
+            const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;  // sized for the most waves
+            if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
+                RSTAMPS(h)[o] = st0;
+                RSTAMPS(h)[o + 1] = st1;
+                RSTAMPS(h)[o + 2] = st2;
+                RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
+                RSTAMPS(h)[o + 4] = sx;
+                RSTAMPS(h)[o + 5] = sq;
+                RSTAMPS(h)[o + 6] = sf;
+                RSTAMPS(h)[o + 7] = sa;
+                RSTAMPS(h)[o + 8] = sl;
+                RSTAMPS(h)[o + 9] = ns.pub;
+                RSTAMPS(h)[o + 10] = ns.bar;
+                RSTAMPS(h)[o + 11] = ns.scale;
+                RSTAMPS(h)[o + 12] = (uint64_t)pg.qw;  // passes of x this wave holds
+                RSTAMPS(h)[o + 13] = sw;
+                RSTAMPS(h)[o + 14] = sc;
+                RSTAMPS(h)[o + 15] = ss;
+            }
+        }
+    };
+
+    if constexpr (SH) {
+        // ---- the short form's steps: copy k runs the step that has k younger steps in flight
+        // (step T - 1 - k), so each copy's wait is a constant and a wave with fewer steps enters
+        // at a later copy. The state (e_*) advances by one step of 16 superblocks.
+        auto step = [&](bool advance) {
+            if (!(RDIAG(ld) & 8) && e_g < G) {
+                const uint8_t *blk = smem + e_blk;
+                const uint8_t *ab = smem + e_act;
+                QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
+                const int isum = quad_sum(r.isum);
+                const int imin = quad_sum(r.imin);
+                if (s == 0) {
+                    const float yd = *(const float *)ab;
+                    Rec rec;
+                    if (TYPE == Q6_K) {
+                        rec.a = isum - 32 * imin;
+                        rec.b = 0;
+                        rec.c = h2f(r.dh) * yd;  // d_all * y.d
+                        rec.e = 0.f;
+                    } else {
+                        rec.a = isum;
+                        rec.b = imin;
+                        rec.c = yd * h2f(r.dh & 0xffffu);  // y.d * fp16(x.d)
+                        rec.e = yd * h2f(r.dh >> 16);      // y.d * fp16(x.dmin)
+                    }
+                    *(Rec *)(smem + e_rec) = rec;
+                }
+            }
+            if (advance) {
+                e_g += ROWS_SB, e_blk += SLOT;
+                e_io += e_b16, e_rr += e_a16;
+                if (e_io >= nb) e_io -= nb, ++e_rr;
+                e_act = L.act + e_io * Q8L_STRIDE;
+                e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(Rec);
+            }
+        };
+        if constexpr (KQ_ROWS_SHORT_UNROLL != 0) {
+            auto copy = [&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if (T > k) {  // uniform
+                    vm_wait<NI * k>();
+                    if (RSTAMPS(h) && T == k + 1) sw = __builtin_amdgcn_s_memrealtime();
+                    step(k > 0);
+                    if (RSTAMPS(h) && T == k + 1) sf = __builtin_amdgcn_s_memrealtime();
+                }
+            };
+            if constexpr (D > 3) copy(std::integral_constant<int, 3>{});
+            if constexpr (D > 2) copy(std::integral_constant<int, 2>{});
+            copy(std::integral_constant<int, 1>{});
+            copy(std::integral_constant<int, 0>{});
+        } else {
+#pragma unroll 1
+            for (int k = T - 1; k >= 0; --k) {
+                vm_wait_k<NI>(k);
+                if (RSTAMPS(h) && T == k + 1) sw = __builtin_amdgcn_s_memrealtime();
+                step(true);
+                if (RSTAMPS(h) && T == k + 1) sf = __builtin_amdgcn_s_memrealtime();
+            }
+        }
+        // ---- the one chain batch: lane r replays row r's records in superblock order and keeps
+        // the result; the residual add and the store come from the register
+        float v = 0.f;
+        float *const outs_s = (float *)(smem + e_outs);
+        if (h.nrows > 0) {
+            wave_lds_fence();
+            sc = RSTAMP();
+            if (lane < h.nrows) {
+                const Rec *rc = (const Rec *)(smem + L.recs + wave * L.recs_stride) + lane;
+#pragma unroll 4
+                for (int i = 0; i < nb; ++i) v = chain_step(TYPE, rc[i * bR], v);
+            }
+            if (KQ_ROWS_DIAG) asm volatile("" : "+v"(v));  // (the stamp behind the value)
+            st2 = RSTAMP();
+            if constexpr (KQ_ROWS_SHORT_LANE == 0) {  // the generic form's round trip through LDS
+                if (lane < h.nrows) outs_s[lane] = v;
+                wave_lds_fence();
+                wave_lds_fence();
+                if (lane < h.nrows) v = outs_s[lane];
+            }
+            float *y = h.y + h.r0;
+            if (res_p) {  // ggml_add(mul_mat, residual): the same single f32 add per element
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                asm volatile("" : "+v"(rv));
+                if (lane < h.nrows) store_y(y + lane, v + __uint_as_float(rv));
+            } else {
+                if (lane < h.nrows) store_y(y + lane, v);
+            }
+            ss = RSTAMP();
+        }
+        // ---- SWIGLU epilogue: the gate wave stages its rows for its up partner, which keeps its own
+        if (h.epi && !(RDIAG(ld) & 128)) {  // uniform over the grid
+            if (h.m == 0 && lane < h.nrows) outs_s[lane] = v;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (h.m == 1 && lane < h.nrows) {
+                const float *gouts = (const float *)(smem + L.outs + (wave - h.epi_wave_off) * L.outs_stride);
+                const int n4 = h.epi_n & ~3;
+                const int r = h.r0 + lane;
+                const float gv = gouts[lane], uv = v;
+                store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+            }
+        }
+        put_stamps();
+        return;
+    }
 
     // ---- main loop
     int io = q, rr = 0;  // quad's (block, row-in-batch) of superblock 16t+q
@@ -906,6 +1094,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         } else {
             vm_wait_k<NI>(T - t - 1);
         }
+        if (RSTAMPS(h) && t == 0) sw = __builtin_amdgcn_s_memrealtime();
         if (!(RDIAG(ld) & 8) && ROWS_SB * t + q < G) {
             const uint8_t *blk = cslot + mis + q * BSZ;
             const uint8_t *ab = actq + io * Q8L_STRIDE;
@@ -946,6 +1135,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         if (RSTAMPS(h) && t == 0) sf = __builtin_amdgcn_s_memrealtime();
         if (ROWS_SB * (t + 1) >= bend) {  // batch complete: replay its rows' chains, lane r <-> row r
             wave_lds_fence();
+            if (RSTAMPS(h) && brow == 0) sc = __builtin_amdgcn_s_memrealtime();
             const int nr = bR < h.nrows - brow ? bR : h.nrows - brow;
             if (lane < nr) {
                 float v = 0.f;
@@ -961,7 +1151,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         }
     }
     if (KQ_ROWS_PRIO) __builtin_amdgcn_s_setprio(0);
-    const uint64_t st2 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
+    st2 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
     if (pf_on) {  // every touch has landed (they are older than step pre0): release the register
         asm volatile("" ::"v"(pf_sink));
     }
@@ -980,6 +1170,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             for (int k = 0; k < h.nrows; k += 64)
                 if (k + lane < h.nrows) store_y(y + k + lane, outs[k + lane]);
         }
+        ss = RSTAMP();
     }
     // ---- SWIGLU epilogue (the GLU node after the gate/up MUL_MATs): up wave and its
     // gate partner own the same rows in this workgroup; both results are staged in LDS.
@@ -997,27 +1188,11 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 }
         }
     }
-    if (RSTAMPS(h)) {
-        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;  // sized for the most waves
-        if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
-            RSTAMPS(h)[o] = st0;
-            RSTAMPS(h)[o + 1] = st1;
-            RSTAMPS(h)[o + 2] = st2;
-            RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
-            RSTAMPS(h)[o + 4] = sx;
-            RSTAMPS(h)[o + 5] = sq;
-            RSTAMPS(h)[o + 6] = sf;
-            RSTAMPS(h)[o + 7] = sa;
-            RSTAMPS(h)[o + 8] = sl;
-            RSTAMPS(h)[o + 9] = ns.pub;
-            RSTAMPS(h)[o + 10] = ns.bar;
-            RSTAMPS(h)[o + 11] = ns.scale;
-            RSTAMPS(h)[o + 12] = (uint64_t)pg.qw;  // passes of x this wave holds
-        }
-    }
+    put_stamps();
 }
 
-template <int TMASK, bool FUSEDQ, int PRO, int LSH>
+// SH: the short-stream form of rows_body (the host picks it per launch, as it picks LSH)
+template <int TMASK, bool FUSEDQ, int PRO, int LSH, bool SH>
 __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const RowsLead ld = rows_lead(x, x2, w0, res0, nb, waves_total, grid, cfg, rbase0, rrem0);
@@ -1029,24 +1204,26 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     auto resolve = [&]() { return rows_resolve<TMASK>(ld, gw); };
 
     if (TMASK == 1) {
-        rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 2) {
-        rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 4) {
-        rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
     } else {  // the type is the matrix's: the entry batch first
         const RowsHot h = resolve();
         auto resolved = [&]() { return h; };
-        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
-        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
-        else rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0, resolved);
+        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
+        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
+        else rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
     }
 }
 
-// (the prologue's form LSH: every fused-quantization kernel in its three forms)
-#define KQ_ROWS_INST(TM, FQ, PR, LS) template __global__ void kq_rows<TM, FQ, PR, LS>(KQ_ROWS_PARAMS);
-#define KQ_ROWS_INST_P(TM, PR) KQ_ROWS_INST(TM, true, PR, 0) KQ_ROWS_INST(TM, true, PR, 1) KQ_ROWS_INST(TM, true, PR, 2)
-#define KQ_ROWS_INST_T(TM) KQ_ROWS_INST_P(TM, 0) KQ_ROWS_INST_P(TM, 1) KQ_ROWS_INST_P(TM, 2) KQ_ROWS_INST(TM, false, 0, 0)
+// (the prologue's form LSH: every fused-quantization kernel in its three forms, each in the
+// generic and the short-stream form; the Q8L-row kernels only in the generic one)
+#define KQ_ROWS_INST(TM, FQ, PR, LS, SH) template __global__ void kq_rows<TM, FQ, PR, LS, SH>(KQ_ROWS_PARAMS);
+#define KQ_ROWS_INST_F(TM, PR, LS) KQ_ROWS_INST(TM, true, PR, LS, false) KQ_ROWS_INST(TM, true, PR, LS, true)
+#define KQ_ROWS_INST_P(TM, PR) KQ_ROWS_INST_F(TM, PR, 0) KQ_ROWS_INST_F(TM, PR, 1) KQ_ROWS_INST_F(TM, PR, 2)
+#define KQ_ROWS_INST_T(TM) KQ_ROWS_INST_P(TM, 0) KQ_ROWS_INST_P(TM, 1) KQ_ROWS_INST_P(TM, 2) KQ_ROWS_INST(TM, false, 0, 0, false)
 KQ_ROWS_INST_T(1)
 KQ_ROWS_INST_T(2)
 KQ_ROWS_INST_T(4)

@@ -67,7 +67,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_attn_prompt",
     "mi355x_attn_prompt_impl",
     "mi355x_attn_batch", "mi355x_attn_batch_path",
-    "mi355x_rows_prologue_plan", "mi355x_debug_rows_prologue",
+    "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
 )
 
 
@@ -184,6 +184,10 @@ def lib():
     L.mi355x_debug_stream.restype = i32
     L.mi355x_rows_prologue_plan.argtypes = [i64, i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.mi355x_rows_prologue_plan.restype = i32
+    if hasattr(L, "mi355x_rows_stream_plan"):  # (an older library under MI355X_LIB, A/B runs: without it)
+        L.mi355x_rows_stream_plan.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i64), i32, i64, i32,
+                                              ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.mi355x_rows_stream_plan.restype = i32
     L.mi355x_debug_rows_prologue.argtypes = [i32, vp, vp, ctypes.c_float, i64, i32, vp, sz, vp]
     L.mi355x_debug_rows_prologue.restype = i32
     L.mi355x_backend_init.argtypes = [i32]
@@ -447,6 +451,23 @@ def rows_prologue_plan(k, waves, steps=0):
     return (lanes.value, passes.value) if rc == 0 else rc
 
 
+ROWS_LONG, ROWS_SHORT, ROWS_CLAIMED = 0, 1, 2
+
+
+def rows_stream_plan(mats, k, batch_rows=0):
+    """(steps, depth, form) of one decode GEMV launch of `mats` = [(type, n_rows), ...] over
+    k-element rows (mi355x_rows_stream_plan: the host's choice, no device): the most
+    16-superblock steps a wave streams and the ring depth of its type, for the matrix with the
+    least room in its ring, and ROWS_SHORT / ROWS_LONG / ROWS_CLAIMED; or the error code."""
+    n = len(mats)
+    types = (ctypes.c_int32 * n)(*[int(t) for t, _ in mats])
+    rows = (ctypes.c_int64 * n)(*[int(r) for _, r in mats])
+    steps, depth, form = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = int(lib().mi355x_rows_stream_plan(types, rows, n, k, batch_rows, ctypes.byref(steps), ctypes.byref(depth),
+                                           ctypes.byref(form)))
+    return (steps.value, depth.value, form.value) if rc == 0 else rc
+
+
 def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=None):
     """The fused GEMV prologue alone on one workgroup of `waves` waves
     (mi355x_debug_rows_prologue): the Q8L image of x after `prologue`, a uint8 tensor
@@ -463,7 +484,7 @@ def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=No
 
 DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_PF", "GEMV_XMODE", "GEMV_SMALL_MB", "GEMV_WPC",
                "GEMV_SMALL_WG", "GEMV_FQMAX", "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY",
-               "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS")
+               "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT")
 
 
 def debug_knob(name, value=float("nan")):

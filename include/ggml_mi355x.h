@@ -223,6 +223,18 @@ int mi355x_debug_block_partials(int src0_type, const void *src0, int64_t ne00, i
  * waves cannot hold the row (more than 3 passes: the GEMV then runs 12 waves). The debug
  * entry below runs the form of steps = 0. */
 int mi355x_rows_prologue_plan(int64_t k, int waves, int64_t steps, int *lanes, int *passes);
+/* The decode GEMV's stream plan for one launch of n <= 4 matrices (types[i], n_rows[i] rows of
+ * k elements) on the fused-quantization path (no launch, no device access). Per matrix: the
+ * most 16-superblock steps one of its waves streams, and the depth of its type's weight ring
+ * (3 steps for Q4_K / Q5_K, 2 for Q6_K); *steps and *depth are those of the matrix with the
+ * least room (depth - steps). *form = MI355X_ROWS_SHORT where steps <= depth for every matrix
+ * and one chain batch covers a wave's rows (the kernel then issues its whole stream before its
+ * barrier and runs the steps straight-line), MI355X_ROWS_LONG otherwise (the generic loop), or
+ * MI355X_ROWS_CLAIMED (claimed rows, always the generic loop). batch_rows > 0: the form with a
+ * chain batch of at most that many rows (0: the plan's own batch). */
+enum { MI355X_ROWS_LONG = 0, MI355X_ROWS_SHORT = 1, MI355X_ROWS_CLAIMED = 2 };
+int mi355x_rows_stream_plan(const int *types, const int64_t *n_rows, int n, int64_t k, int batch_rows, int *steps,
+                            int *depth, int *form);
 /* Debug/parity hook: the fused GEMV prologue alone. One workgroup of `waves` waves loads x
  * (and x2), applies `prologue` (MI355X_PRO_*: x2 = norm weight / up, x = gate) and quantizes
  * to Q8_K exactly as the decode GEMV does before its barrier, then copies the workgroup's

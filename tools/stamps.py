@@ -57,7 +57,7 @@ def main(impl):
                 g.gemv_fused_ext([(typ, w, y[0])], x[0], prologue=pro, x2=x2, eps=1e-5)
         for w in ws:
             mm(w)
-        res, nres = [], []
+        res, nres, sres = [], [], []
         for r in range(5):
             buf.zero_()
             torch.cuda.synchronize()
@@ -91,6 +91,14 @@ def main(impl):
                 # the norm interval of the waves that hold a part of the row (slot 12: passes of x
                 # held): [8] x landed, [9] sums published, [10] barrier passed, [11] scale known,
                 # [4] transformed; waves without x: their whole prologue
+                # the interval after the barrier of the waves that stream rows: [1] barrier passed,
+                # [13] first step's wait passed, [6] first record written, [14] chain started (the
+                # last step's records written), [2] chain done, [15] stores issued, [3] exit
+                hs = (st[:, 13] >= t0) & (st[:, 15] >= t0) & (st[:, 14] >= t0)
+                if hs.any():
+                    sres.append((med(rel[hs, 13] - rel[hs, 1]), med(rel[hs, 6] - rel[hs, 13]), med(rel[hs, 14] - rel[hs, 6]),
+                                 med(rel[hs, 2] - rel[hs, 14]), med(rel[hs, 15] - rel[hs, 2]), med(rel[hs, 3] - rel[hs, 15]),
+                                 med(rel[hs, 3] - rel[hs, 1]), float(np.max(rel[hs, 3] - rel[hs, 1])), float(hs.sum()) / len(st)))
                 hx = ok & (st[:, 12] > 0) & (st[:, 11] >= t0)
                 if PRO == "norm" and hx.any():
                     nx = ok & (st[:, 10] >= t0) & (st[:, 12] == 0)
@@ -108,6 +116,11 @@ def main(impl):
             print(f"{tag} {label:12s} waves={int(a[0]):5d} start_spread={a[1]:5.2f}us | x-wait {a[2]:4.2f} (args {a[12]:4.2f}) quant {a[3]:4.2f} "
                   f"barrier+fill {a[4]:4.2f} = prologue {a[6]:4.2f} | first step {a[5]:4.2f} loop med/max={a[7]:5.2f}/{a[8]:5.2f} "
                   f"loop end med/max={a[11]:6.2f}/{a[10]:6.2f} end={a[9]:6.2f}us")
+            if sres:
+                c = np.array(sres)[1:].mean(0)
+                print(f"{tag} {label:12s}   after the barrier, waves with rows ({c[8]:4.2f} of all): first wait {c[0]:4.2f} | first "
+                      f"record {c[1]:4.2f} | later steps {c[2]:4.2f} | chain {c[3]:4.2f} | stores {c[4]:4.2f} | exit {c[5]:4.2f} | "
+                      f"barrier -> exit med/max {c[6]:4.2f}/{c[7]:4.2f}")
             if nres:
                 b = np.array(nres)[1:].mean(0)
                 print(f"{tag} {label:12s}   norm interval, waves with x ({b[7]:4.2f} of all): x landed {b[0]:4.2f} | sums published "
