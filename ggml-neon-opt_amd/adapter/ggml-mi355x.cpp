@@ -590,6 +590,8 @@ ggml_backend_dev_t reg_device(ggml_backend_reg_t reg, size_t i) {
 void *reg_proc(ggml_backend_reg_t, const char *name) {
     if (name && std::strcmp(name, "ggml_backend_mi355x_set_multi_seq") == 0)
         return (void *)ggml_backend_mi355x_set_multi_seq;
+    if (name && std::strcmp(name, "ggml_backend_mi355x_set_long_context") == 0)
+        return (void *)ggml_backend_mi355x_set_long_context;
     return nullptr;
 }
 
@@ -645,6 +647,8 @@ int ggml_backend_mi355x_get_device_count(void) { return (int)registry()->devices
 void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable) {
     if (ggml_backend_is_mi355x(backend)) ((Backend *)backend->context)->multi_seq = enable;
 }
+
+void ggml_backend_mi355x_set_long_context(bool enable) { mi355x_attn_stream(enable ? 1 : 0); }
 
 GGML_BACKEND_DL_IMPL(ggml_backend_mi355x_reg)
 GGML_BACKEND_DL_SCORE_IMPL(mi355x_score)

@@ -32,6 +32,13 @@ GGML_BACKEND_API int ggml_backend_mi355x_get_device_count(void);
 // keep the single-sequence path either way. Also returned by the registry's get_proc_address
 // under this name.
 GGML_BACKEND_API void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable);
+// KV caches of more than 7040-7616 cells (the per-head attention kernels' limit), up to 131072:
+// off (the default), a graph over such a cache is refused (GGML_STATUS_FAILED); on, its
+// attention runs on the library's streamed kernels (mi355x_attn_stream mode 1, same bits).
+// Process-wide, like the library's selector; caches that run today keep their kernels either
+// way. Not covered: multi-sequence graphs (ATTN_BATCH) over such caches. Also returned by the
+// registry's get_proc_address under this name.
+GGML_BACKEND_API void ggml_backend_mi355x_set_long_context(bool enable);
 
 #ifdef __cplusplus
 }

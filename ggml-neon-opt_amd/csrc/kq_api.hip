@@ -119,7 +119,7 @@ const KnobDef kKnobs[KNOB_COUNT] = {
     {"GEMV_SMALL_WG", 0}, {"GEMV_FQMAX", (double)kRowsFusedMaxNb},   {"MMF_WAVES", 0},
     {"MMF_ORDER", 0},  {"ATTN_DIAG", 0},     {"LOOPBACK_NOCOPY", 0}, {"ATTN_OPROJ", 1},
     {"AO_NRB", 0},     {"GEMV_DYN", 8},    {"GEMV_DYN_P", 0},      {"GEMV_DYN_STEPS", 16},
-    {"GEMV_SHORT", 1},
+    {"GEMV_SHORT", 1}, {"ATTN_STREAM", -1},  {"ATTN_STREAM_TILE", 0},
 };
 std::atomic<double> g_knob[KNOB_COUNT];
 std::atomic<bool> g_knob_set[KNOB_COUNT];

@@ -290,6 +290,7 @@ int check_attn_batch(const AttnBatchArgs &b) {
     if (b.mask_row_bytes < (int64_t)b.n_kv * (b.mask_f16 ? 2 : 4)) return MI355X_E_INVAL;
     if (b.a.rope_row) return MI355X_E_INVAL;  // per-token positions: the whole rope table
     if (b.n_tok > 65535) return MI355X_E_UNSUPPORTED;  // one grid row per token
+    if (attn_size_refused(b.a)) return MI355X_E_UNSUPPORTED;  // (mi355x_attn_stream lifts the size limit for decode / prompt only)
     const int form = attn_batch_form(b);
     return form < 0 ? form : MI355X_OK;
 }

@@ -628,15 +628,18 @@ int ensure_layer_tables(mi355x_backend *b, const std::vector<Launch> &launches) 
     return MI355X_OK;
 }
 
-// long-cache decode attention: its score workspace
+// long-cache attention: the score workspace of a decode node (the split over cells, the
+// streamed kernels) and of a prompt node that takes the streamed kernels
 int reserve_attn_cells(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<Launch> &launches) {
     for (const Launch &l : launches) {
         const mi355x_tensor *t = nodes[l.first];
-        if (l.kind != LaunchKind::Node || t->op != MI355X_OP_ATTN_DECODE || t->src[0]->ne[1] != 1) continue;
+        if (l.kind != LaunchKind::Node || t->op != MI355X_OP_ATTN_DECODE) continue;
+        const int64_t T = t->src[0]->ne[1];
         mi355x_attn_desc d = {};
         attn_desc_of(t, d);
+        if (T > 1) d.rope_row = 0;
         kq::AttnArgs a = {};
-        if (kq::attn_args_from(&d, a) == MI355X_OK && kq::attn_cells_reserve(a, b->stream) != MI355X_OK)
+        if (kq::attn_args_from(&d, a) == MI355X_OK && kq::attn_cells_reserve(a, b->stream, (int)T) != MI355X_OK)
             return MI355X_E_WORKSPACE;
     }
     return MI355X_OK;

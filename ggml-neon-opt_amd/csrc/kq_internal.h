@@ -60,8 +60,26 @@ int launch_rms_norm(const float *x, const float *w, float *y, int64_t n, int64_t
 int launch_binary(int op, const float *a, const float *b, float *y, int64_t n, hipStream_t s,
                   int64_t nb = 0);  // 0 add, 1 mul; b of nb elements repeated (0: nb = n)
 int launch_attn_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
-int attn_cells_reserve(const AttnArgs &a, hipStream_t stream);  // long-cache attention workspace (per stream), before any capture
+// long-cache attention workspace (per stream), before any capture; n_tok > 1: a prompt node
+int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok = 1);
 bool attn_prompt_q8_ok(const AttnArgs &a);  // the group kernel can write a.q8_out
+// kq_attn_stream.hip: streamed attention for caches of up to kAttnStreamMaxCtx cells (mi355x_attn_stream).
+// attn_stream_applies / _prompt_applies: launch_attn / launch_attn_prompt take the streamed kernels
+// for these (checked) arguments; attn_stream_workspace: the bytes of attn_cells_buffer they need
+// (6 per (token of a tile, head, cell)).
+constexpr int kAttnStreamMaxCtx = 131072;
+int attn_stream_mode();                         // 0 off, 1 where the other kernels refuse the cache's size, 2 always
+bool attn_size_refused(const AttnArgs &a);      // n_ctx > 8192 or attn_lds > 64 KB: refused unless streamed
+bool attn_stream_applies(const AttnArgs &a);
+bool attn_stream_prompt_applies(const AttnArgs &a);
+size_t attn_stream_workspace(const AttnArgs &a, int n_tok);
+int launch_attn_stream(const AttnArgs &a, hipStream_t s);
+int launch_attn_stream_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
+// kq_ops.hip pieces the streamed path shares
+size_t attn_lds(int hd, int n_ctx);
+size_t attn_prompt_lds(int hd, int n_ctx);
+void *attn_cells_buffer(size_t bytes, hipStream_t stream, bool may_alloc);
+int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
 // prefill (ne11 >= 16) pieces, for the backend's shared-activation runs
 bool mmq_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M);
 int launch_quantize_q8L(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
@@ -154,6 +172,8 @@ enum Knob {
     KNOB_GEMV_DYN_P,       // kq_rows_dyn: static units per wave (0: a ring's worth; A/B only)
     KNOB_GEMV_DYN_STEPS,   // kq_rows_dyn AUTO: 16-superblock steps per wave at least (with GEMV_DYN units)
     KNOB_GEMV_SHORT,       // kq_rows short-stream form where the plan allows it (1); 0: the generic form (A/B)
+    KNOB_ATTN_STREAM,      // 0 / 1 / 2: overrides mi355x_attn_stream's mode (-1: the selector's own value)
+    KNOB_ATTN_STREAM_TILE, // streamed prompt attention: tokens per tile (0: by the workspace cap)
     KNOB_COUNT
 };
 double knob(Knob k);

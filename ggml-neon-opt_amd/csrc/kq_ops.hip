@@ -1161,8 +1161,10 @@ bool attn_cells_applies(const AttnArgs &a) {
 
 // The workspace of a decode attention that will take the two launches, allocated now (callers
 // that capture graphs call this first; an eager launch allocates on its own)
-int attn_cells_reserve(const AttnArgs &a, hipStream_t stream) {
-    if (!attn_cells_applies(a)) return MI355X_OK;
+int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok) {
+    if (n_tok > 1 ? attn_stream_prompt_applies(a) : attn_stream_applies(a))
+        return attn_cells_buffer(attn_stream_workspace(a, n_tok), stream, true) ? MI355X_OK : MI355X_E_WORKSPACE;
+    if (n_tok > 1 || !attn_cells_applies(a)) return MI355X_OK;
     return attn_cells_buffer((size_t)a.n_head * a.n_ctx * 4, stream, true) ? MI355X_OK : MI355X_E_WORKSPACE;
 }
 
@@ -1188,6 +1190,7 @@ int launch_attn_cells(const AttnArgs &a, float *ws, hipStream_t s) {
 // The kernel launch_attn runs for these arguments (mi355x_attn_path; a captured launch without
 // a reserved workspace takes MI355X_ATTN_PATH_HEAD_BATCH instead of the cells split).
 int attn_path(const AttnArgs &a) {
+    if (attn_stream_applies(a)) return MI355X_ATTN_PATH_STREAM;
     if (attn_impl() == MI355X_ATTN_GROUP && attn_group_ok(a, attn_group_waves(a))) return MI355X_ATTN_PATH_GROUP;
     const int ds = attn_slices(a);
     if (ds > 1 && !attn_cells_applies(a)) return ds == 4 ? MI355X_ATTN_PATH_SPLIT4 : MI355X_ATTN_PATH_SPLIT8;
@@ -1201,6 +1204,7 @@ int attn_path(const AttnArgs &a) {
 int launch_attn(const AttnArgs &a, hipStream_t s) {
     const double bytes = 0;  // context-dependent; not a roofline kernel
     const int path = attn_path(a);
+    if (path == MI355X_ATTN_PATH_STREAM) return launch_attn_stream(a, s);  // (unreserved under capture: E_WORKSPACE)
     if (path == MI355X_ATTN_PATH_GROUP) {
         const int nw = attn_group_waves(a);
         const size_t glds = attn_group_bytes(a, nw);
@@ -1291,12 +1295,19 @@ int attn_prompt_tpw(const AttnArgs &a) {
 
 // Q8L rows written by the group kernel: its slice (gsz*head_dim) must be whole superblocks
 bool attn_prompt_q8_ok(const AttnArgs &a) {
-    return attn_prompt_group_ok(a) && ((a.n_head / a.n_head_kv) * a.head_dim) % QK == 0 &&
+    return !attn_stream_prompt_applies(a) && attn_prompt_group_ok(a) && ((a.n_head / a.n_head_kv) * a.head_dim) % QK == 0 &&
            a.n_ctx >= a.head_dim;  // staged in the score rows: gsz*head_dim floats
+}
+
+int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s) {
+    const dim3 gs((unsigned)n_tok, (unsigned)a.n_head_kv);
+    return a.head_dim == 64 ? timed_launch("kq::kq_kv_store<64>", 0.0, kq_kv_store<64>, gs, dim3(256), 0, s, a)
+                            : timed_launch("kq::kq_kv_store<128>", 0.0, kq_kv_store<128>, gs, dim3(256), 0, s, a);
 }
 
 int launch_attn_prompt(const AttnArgs &a0, int n_tok, hipStream_t s) {
     if (n_tok <= 0) return MI355X_OK;
+    if (attn_stream_prompt_applies(a0)) return launch_attn_stream_prompt(a0, n_tok, s);
     AttnArgs a = a0;
     a.n_tok = n_tok;
     const size_t lds = attn_prompt_lds(a.head_dim, a.n_ctx);
@@ -1346,14 +1357,16 @@ int check_attn(const AttnArgs &a) {
     if (!a.q || !a.k || !a.v || !a.pos || !a.rope_table || !a.k_cache || !a.v_cache || !a.out) return MI355X_E_INVAL;
     if (a.head_dim != 64 && a.head_dim != 128) return MI355X_E_UNSUPPORTED;
     if (a.n_head <= 0 || a.n_head_kv <= 0 || a.n_head % a.n_head_kv) return MI355X_E_INVAL;
-    if (a.n_ctx < 32 || a.n_ctx % 32 || a.n_ctx > 8192) return MI355X_E_UNSUPPORTED;
+    if (a.n_ctx < 32 || a.n_ctx % 32) return MI355X_E_UNSUPPORTED;
     if (((uintptr_t)a.k_cache & 15u) || ((uintptr_t)a.v_cache & 15u)) return MI355X_E_INVAL;
-    if (attn_lds(a.head_dim, a.n_ctx) > 64 * 1024) return MI355X_E_UNSUPPORTED;
+    // past 8192 cells, or the per-head layout's 64 KB: the streamed kernels where mi355x_attn_stream allows them
+    if (attn_size_refused(a) && !attn_stream_applies(a)) return MI355X_E_UNSUPPORTED;
     return MI355X_OK;
 }
 
 uint64_t ops_selector_key() {
-    return (uint64_t)(uint32_t)attn_impl() | ((uint64_t)(uint32_t)g_prompt_impl.load() << 8);
+    return (uint64_t)(uint32_t)attn_impl() | ((uint64_t)(uint32_t)g_prompt_impl.load() << 8) |
+           ((uint64_t)(uint32_t)attn_stream_mode() << 16);
 }
 
 }  // namespace kq
@@ -1463,7 +1476,7 @@ int mi355x_attn_prompt(const mi355x_attn_desc *d, int n_tokens, void *stream) {
     AttnArgs a;
     const int rc = attn_args_from(d, a);
     if (rc) return rc;
-    if (attn_prompt_lds(a.head_dim, a.n_ctx) > 160 * 1024) return MI355X_E_UNSUPPORTED;
+    if (attn_prompt_lds(a.head_dim, a.n_ctx) > 160 * 1024 && !attn_stream_prompt_applies(a)) return MI355X_E_UNSUPPORTED;
     if (n_tokens == 0) return MI355X_OK;
     if (!device_ok()) return MI355X_E_NODEVICE;
     return launch_attn_prompt(a, n_tokens, (hipStream_t)stream);

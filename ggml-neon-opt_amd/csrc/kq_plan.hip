@@ -189,7 +189,7 @@ bool layer_match(const PlanOpts &po, mi355x_tensor *const *nodes, int n, int i, 
     mi355x_attn_desc d;
     attn_desc_of(at, d);
     d.rope_row = 1;
-    if (attn_args_from(&d, la.at) != 0) return false;
+    if (attn_args_from(&d, la.at) != 0 || attn_size_refused(la.at)) return false;  // (streamed caches: ATTN_DECODE alone)
     return layer_plan(la, hd, nh) == MI355X_OK;
 }
 
@@ -197,8 +197,9 @@ bool layer_match(const PlanOpts &po, mi355x_tensor *const *nodes, int n, int i, 
 bool contig_f32(const mi355x_tensor *t) { return t && t->type == MI355X_TYPE_F32 && t->nb[0] == 4 && t->data; }
 
 // ATTN_DECODE / ATTN_BATCH: the caches (src4, src5) exactly [n_ctx][kvw] and [kvw][n_ctx] f16,
-// 16-B aligned (the kernels' addressing), n_ctx a multiple of 32 up to 8192; pos (src3) i32
-bool kv_caches_ok(const mi355x_tensor *op, int nkv, int hd) {
+// 16-B aligned (the kernels' addressing), n_ctx a multiple of 32 up to max_ctx (8192; ATTN_DECODE
+// up to kAttnStreamMaxCtx while mi355x_attn_stream is on); pos (src3) i32
+bool kv_caches_ok(const mi355x_tensor *op, int nkv, int hd, int64_t max_ctx = 8192) {
     const mi355x_tensor *kc = op->src[4], *vc = op->src[5];
     if (kc->type != MI355X_TYPE_F16 || vc->type != MI355X_TYPE_F16) return false;
     if (kc->ne[0] != (int64_t)nkv * hd || op->src[3]->type != MI355X_TYPE_I32) return false;
@@ -207,7 +208,7 @@ bool kv_caches_ok(const mi355x_tensor *op, int nkv, int hd) {
     if (vc->nb[0] != 2 || vc->nb[1] != (size_t)vc->ne[0] * 2) return false;
     if (((uintptr_t)kc->data & 15u) || ((uintptr_t)vc->data & 15u)) return false;
     const int64_t n_ctx = kc->ne[1];
-    return n_ctx >= 32 && n_ctx % 32 == 0 && n_ctx <= 8192;
+    return n_ctx >= 32 && n_ctx % 32 == 0 && n_ctx <= max_ctx;
 }
 
 // T tokens (T > 1: rows packed): q [nh*hd, T], k, v [kvw, T] contiguous f32, pos [T]
@@ -603,7 +604,9 @@ bool supports_op(const mi355x_tensor *op) {
             // T tokens (T > 1: a prompt batch): one rope row per position of the whole table
             const int64_t T = op->src[0]->ne[1], n_ctx = op->src[4]->ne[1];
             if (T < 1 || T > 0x7fffffff) return false;
-            if (!kv_caches_ok(op, nkv, hd) || !qkv_rows_ok(op, nh, nkv, hd, T)) return false;
+            if (!kv_caches_ok(op, nkv, hd, attn_stream_mode() != 0 ? kAttnStreamMaxCtx : 8192) ||
+                !qkv_rows_ok(op, nh, nkv, hd, T))
+                return false;
             if (T > 1 && op->src[6]->ne[1] < n_ctx) return false;
             if (op->src[6]->ne[1] != 1 && op->src[6]->ne[1] < n_ctx) return false;  // row or table
             if (op->src[6]->ne[0] != hd) return false;

@@ -34,6 +34,7 @@ EPI_NONE, EPI_SWIGLU = 0, 1
 ATTN_GROUP, ATTN_HEAD, ATTN_SPLIT = 0, 1, 2
 # mi355x_attn_path: the decode attention kernel a descriptor takes
 ATTN_PATH_HEAD, ATTN_PATH_HEAD_BATCH, ATTN_PATH_SPLIT4, ATTN_PATH_SPLIT8, ATTN_PATH_CELLS, ATTN_PATH_GROUP, ATTN_PATH_KD1 = range(7)
+ATTN_PATH_STREAM = 7  # the streamed kernels (attn_stream)
 MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE128X, MMQ_TILE192 = 0, 1, 2, 3, 4, 5, 6
 PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
 
@@ -65,7 +66,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_device_count", "mi355x_device_ordinal", "mi355x_device_memory", "mi355x_backend_memset", "mi355x_backend_set_attn_oproj",
     "mi355x_backend_set_layer_engine", "mi355x_backend_layer_error",
     "mi355x_attn_prompt",
-    "mi355x_attn_prompt_impl",
+    "mi355x_attn_prompt_impl", "mi355x_attn_stream",
     "mi355x_attn_batch", "mi355x_attn_batch_path",
     "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
 )
@@ -246,6 +247,8 @@ def lib():
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
     L.mi355x_attn_impl.restype = i32
+    L.mi355x_attn_stream.argtypes = [i32]
+    L.mi355x_attn_stream.restype = i32
     L.mi355x_mmq_impl.argtypes = [i32]
     L.mi355x_mmq_impl.restype = i32
     L.mi355x_prefill_precision.argtypes = [i32]
@@ -484,7 +487,8 @@ def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=No
 
 DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_PF", "GEMV_XMODE", "GEMV_SMALL_MB", "GEMV_WPC",
                "GEMV_SMALL_WG", "GEMV_FQMAX", "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY",
-               "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT")
+               "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT", "ATTN_STREAM",
+               "ATTN_STREAM_TILE")
 
 
 def debug_knob(name, value=float("nan")):
@@ -507,6 +511,14 @@ def attn_impl(impl):
     """ATTN_SPLIT (default: per query head, split by output past 256 cache cells) / ATTN_HEAD
     (per query head) / ATTN_GROUP (per kv group); returns the previous."""
     return int(lib().mi355x_attn_impl(impl))
+
+
+def attn_stream(mode):
+    """Streamed attention for caches of up to 131072 cells (mi355x_attn_stream): 0 off (default),
+    1 for the descriptors refused for their cache size alone, 2 for every valid descriptor (tests,
+    A/B). attn_path / attn_decode / attn_prompt and the graph backend follow it. Returns the
+    previous mode, E_INVAL for any other value."""
+    return int(lib().mi355x_attn_stream(mode))
 
 
 def gemv_fused_ext(mats, x, prologue=PRO_NONE, x2=None, eps=0.0, residual=None, epi_y=None, stream=None):

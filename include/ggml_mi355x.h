@@ -363,7 +363,9 @@ int mi355x_rope(const float *x, float *y, int head_dim, int n_dims, int n_heads,
  * KQ = mul_mat(k_cache f16, q->f16) via ggml_vec_dot_f16 (NEON FP16 accumulation,
  * out.folded:140-144), soft_max_ext(scale, causal mask) (out.folded:216-234), KQV =
  * mul_mat(v_cache, kq->f16), permute + cont -> out[n_head*head_dim]. n_kv =
- * min(n_ctx, max(32, pad32(pos+1))). head_dim 64 or 128; n_ctx % 32 == 0, <= 8192;
+ * min(n_ctx, max(32, pad32(pos+1))). head_dim 64 or 128; n_ctx % 32 == 0, <= 8192 and within
+ * the per-head kernel's 64 KB layout (8 n_ctx + 70 head_dim + 16 bytes past 4096 cells: 7616
+ * cells at head_dim 64, 7040 at 128); with mi355x_attn_stream on, up to 131072 cells;
  * caches zero-initialised by the caller, 16-B aligned. */
 typedef struct {
     const float *q, *k, *v;    /* this token's projections, before rope */
@@ -391,6 +393,7 @@ int mi355x_attn_decode(const mi355x_attn_desc *a, void *stream);
 #define MI355X_ATTN_PATH_CELLS 4      /* KQ split over cells: kq_attn_cells + kq_attn_cells_kqv */
 #define MI355X_ATTN_PATH_GROUP 5      /* one workgroup per KV group (MI355X_ATTN_GROUP) */
 #define MI355X_ATTN_PATH_KD1 6        /* experiment builds (KQ_ATTN_KDMA1) */
+#define MI355X_ATTN_PATH_STREAM 7     /* streamed: kq_attn_stream_scores + _softmax + _kqv (mi355x_attn_stream) */
 int mi355x_attn_path(const mi355x_attn_desc *a);
 /* The same block for a prompt of n_tokens tokens in one graph (llama-bench pp: ggml's
  * batched non-flash path — SET_ROWS of the batch's cells, then KQ / soft_max with the
@@ -411,6 +414,22 @@ int mi355x_attn_prompt(const mi355x_attn_desc *a, int n_tokens, void *stream);
 #define MI355X_ATTN_HEAD 1
 #define MI355X_ATTN_SPLIT 2
 int mi355x_attn_impl(int impl);
+/* Streamed attention for long caches (process-wide, like mi355x_attn_impl; default 0). The
+ * streamed kernels keep scores and soft_max weights in a global workspace (6 bytes per token,
+ * head and cell, on the per-stream attention workspace) and pass the V rows through a fixed LDS
+ * ring, so nothing on the chip grows with the cache: 32 <= n_ctx <= 131072, n_ctx % 32 == 0,
+ * same bits as the other kernels.
+ *   0: off: caches past 8192 cells, or past the per-head kernel's 64 KB layout, are refused;
+ *   1: a descriptor refused only for its cache size (mi355x_attn_prompt: also one whose prompt
+ *      kernel does not fit the LDS) takes the streamed kernels; every descriptor that runs with
+ *      0 keeps its kernel;
+ *   2: every valid descriptor takes them, decode and prompt (tests, A/B runs).
+ * mi355x_attn_prompt runs its tokens in tiles whose workspace stays under 256 MiB (at least one
+ * token). A launch captured into a hipGraph needs its workspace reserved beforehand (the graph
+ * backend does it); otherwise it returns MI355X_E_WORKSPACE. The mode is part of the graph
+ * backend's plan key. Not covered: ATTN_BATCH, the attention + o-proj fusion and the layer
+ * engine keep their sizes. Returns the previous mode, or MI355X_E_INVAL. */
+int mi355x_attn_stream(int mode);
 /* Prompt attention selector (A/B runs, parity of both): MI355X_ATTN_GROUP (default: one
  * workgroup per kv group and token, the group's query heads sharing every K/V load, where
  * n_head/n_head_kv <= 8 and its LDS fits) or MI355X_ATTN_HEAD (one per query head and
@@ -466,6 +485,11 @@ int mi355x_attn_batch_path(const mi355x_attn_batch_desc *d);
  *                token's position, staged with pos; op_params = {n_head, n_head_kv, head_dim, scale bits}
  *                -> f32 [head_dim*n_head]: the non-flash attention block
  *                (set_rows, mul_mat f16, soft_max_ext, mul_mat f16, permute, cont).
+ *                n_ctx a multiple of 32 within mi355x_attn_decode's sizes: up to 8192 cells
+ *                and the per-head kernel's 64 KB layout, or, while mi355x_attn_stream is on,
+ *                up to 131072 cells on the streamed kernels (decode and prompt; such a node
+ *                joins neither the attention + o-proj fusion nor the layer engine, and a
+ *                prompt's o-proj quantization stays unfused).
  *   ATTN_BATCH   src0..src6 as ATTN_DECODE for T tokens (q [n_head*head_dim, T], k, v [kvw, T]
  *                packed rows, pos I32 [T], both caches, the whole rope table [head_dim, n_pos]:
  *                a position >= n_pos has no rope row), src7 cells I32 or I64 [T], src8 mask F16
