@@ -433,3 +433,67 @@ def test_softmax_sum_bound_by_total():
             assert st == seq == math.fsum(d)
         admitted_old += ok_old
     assert admitted_new > admitted_old
+
+
+@pytest.mark.parametrize("hd,nh,nkv,n_ctx,pos", [(128, 12, 4, 64, (5, 3, 4, 40, 31, 32, 33, 63, 0)),
+                                                 (64, 16, 1, 320, tuple(range(250, 290)))],
+                         ids=["shuffled-64", "strides-320"])
+def test_prompt_reference_equals_sequential_decode(O, hd, nh, nkv, n_ctx, pos):
+    """The reference of tests/test_gpu_attn_prompt.py (tests/attn_prompt_ref.py: every cell of the batch
+    stored first, then one attn_decode per token in batch order) equals attn_decode token by token in
+    ascending position on
+    the same junk caches, outputs and both caches: the cells a sequential token has not yet seen lie
+    after its position, where soft_max gives them an exact zero."""
+    from tests.attn_prompt_ref import qkv, rand_caches, ref_attn_prompt, scale_of
+    rng = np.random.default_rng(n_ctx + hd)
+    tref = O.rope_table(n_ctx, hd, 10000.0)
+    kc0, vc0 = rand_caches(rng, n_ctx, nkv * hd)
+    q, k, v = qkv(rng, len(pos), nh, nkv, hd, 2.0)
+    kc, vc = kc0.copy(), vc0.copy()
+    got = ref_attn_prompt(O, q, k, v, pos, kc, vc, tref, nh, nkv, hd)
+    kc2, vc2 = kc0.copy(), vc0.copy()
+    for i in sorted(range(len(pos)), key=lambda j: pos[j]):
+        want = O.attn_decode(O.rope(q[i], hd, hd, pos[i], tref), O.rope(k[i], hd, hd, pos[i], tref), v[i], kc2, vc2,
+                             pos[i], nh, nkv, hd, scale_of(hd))
+        assert (got[i].view(np.uint32) == want.view(np.uint32)).all(), (i, pos[i])
+    assert (kc == kc2).all() and (vc == vc2).all()
+    owned = np.zeros(n_ctx, bool)
+    owned[list(pos)] = True
+    assert (kc[~owned] == kc0[~owned]).all() and (vc[:, ~owned] == vc0[:, ~owned]).all()
+
+
+def _softmax_sum_is_exact(O, kc, q16, p, n_ctx, g, h, nkv, hd, scale):
+    """sum_exact_ok of csrc/kq_ops_device.h for one query row of the prompt kernels: the row's scores
+    over cells 0..p, ggml_v_expf, the float group sums of 4 cells, and the bound S <= (1 - 2^-40)
+    2^(Gmin + 53) under which the wave tree is ggml's in-order double sum."""
+    import math
+    L = O.lib()
+    kq = np.array([L.kqo_vec_dot_f16(hd, kc.ctypes.data + 2 * (c * nkv * hd + g * hd), q16.ctypes.data + 2 * h * hd)
+                   for c in range(p + 1)], np.float32) * np.float32(scale)
+    e = np.zeros(O.attn_n_kv(p, n_ctx), np.float32)
+    e[:p + 1] = O.v_expf(kq - kq.max())
+    e = e.reshape(-1, 4)
+    gs = ((e[:, 0] + e[:, 1]) + (e[:, 2] + e[:, 3])).astype(np.float32)
+    nz = gs[gs != 0]
+    gmin = int((np.maximum((nz.view(np.uint32) >> 23) & 0xFF, 1).astype(np.int64) - 150).min())
+    return math.fsum(gs.astype(np.float64)) <= math.ldexp(1.0 - 2.0 ** -40, gmin + 53)
+
+
+@pytest.mark.parametrize("hd,nh,nkv", [(64, 6, 2), (128, 8, 1)])
+def test_prompt_softmax_cases_reach_both_sums(O, hd, nh, nkv):
+    """The inputs of tests/test_gpu_attn_prompt.py::test_softmax_sum_tree_and_fallback reach the sums
+    its docstring names: every flat and N(0, 2) row the exact tree, every peaked row the in-order
+    fallback, and under "mixed" every (token, kv group) — one workgroup of the group kernel — rows of
+    both kinds."""
+    from tests.attn_prompt_ref import MIXED, STRIDE_BATCH, case_reference, scale_of
+    n_ctx, gsz = 320, nh // nkv
+    tref = O.rope_table(n_ctx, hd, 10000.0)
+    for qscale, want in ((0.05, {True}), (2.0, {True}), (40.0, {False}), (MIXED, {True, False})):
+        _, _, steps = case_reference(O, hd, nh, nkv, n_ctx, STRIDE_BATCH, qscale)
+        pos, q, _, _, _, kc, _ = steps[0]
+        for i in range(0, len(pos), 13):  # tokens 0, 13, 26, 39: n_kv 256, 288, 288 and 320
+            q16 = O.fp32_to_fp16(O.rope(q[i], hd, hd, pos[i], tref))
+            for g in range(nkv):
+                exact = {_softmax_sum_is_exact(O, kc, q16, pos[i], n_ctx, g, h, nkv, hd, scale_of(hd))
+                         for h in range(g * gsz, (g + 1) * gsz)}
+                assert exact == want, (qscale, "token", i, "group", g, exact)
