@@ -255,19 +255,6 @@ __global__ void __launch_bounds__(256) kq_attn_batch(const AttnBatchArgs b) {
 
 namespace {
 
-template <typename K, typename... Args>
-int timed_launch(const char *name, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
-    hipEvent_t e0, e1;
-    if (timing_slot(s, e0, e1)) {
-        hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, e0, e1, 0, args...);
-        timing_log(name, 0.0, e0, e1);
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
-}
-
 constexpr size_t kBatchLdsMax = 160 * 1024;
 
 }  // namespace
@@ -309,17 +296,17 @@ int launch_attn_batch(const AttnBatchArgs &b0, hipStream_t s) {
 #define KQ_BATCH_LAUNCH(HD, G)                                                                                  \
     {                                                                                                         \
         allow_lds((const void *)kq_attn_batch<HD, G>, lds);                                                   \
-        return timed_launch("kq::kq_attn_batch<" #HD ">", kq_attn_batch<HD, G>, ga, dim3(256), lds, s, b);   \
+        return timed_launch("kq::kq_attn_batch<" #HD ">", 0.0, kq_attn_batch<HD, G>, ga, dim3(256), lds, s, b);   \
     }
     if (a.head_dim == 64) {
-        rc = timed_launch("kq::kq_kv_store_batch<64>", kq_kv_store_batch<64>, gs, dim3(256), 0, s, b);
+        rc = timed_launch("kq::kq_kv_store_batch<64>", 0.0, kq_kv_store_batch<64>, gs, dim3(256), 0, s, b);
         if (rc) return rc;
         if (rows == 1) KQ_BATCH_LAUNCH(64, 1)
         if (rows == 4) KQ_BATCH_LAUNCH(64, 4)
         if (rows == 8) KQ_BATCH_LAUNCH(64, 8)
         KQ_BATCH_LAUNCH(64, 0)
     }
-    rc = timed_launch("kq::kq_kv_store_batch<128>", kq_kv_store_batch<128>, gs, dim3(256), 0, s, b);
+    rc = timed_launch("kq::kq_kv_store_batch<128>", 0.0, kq_kv_store_batch<128>, gs, dim3(256), 0, s, b);
     if (rc) return rc;
     if (rows == 1) KQ_BATCH_LAUNCH(128, 1)
     if (rows == 4) KQ_BATCH_LAUNCH(128, 4)

@@ -304,19 +304,12 @@ int launch_attn_oproj(const AttnArgs &a, int type, const void *w, int64_t n_rows
     allow_lds(fn, sh.lds);
     const dim3 grid((unsigned)(sh.nsb * sh.n_rb)), block(512u);
     void *args[] = {&p};
-    hipEvent_t e0, e1;
-    hipError_t e;
-    if (timing_slot(stream, e0, e1)) {
-        e = hipExtLaunchKernel(fn, grid, block, args, sh.lds, stream, e0, e1, 0);
-        const std::string name = std::string("kq::kq_attn_oproj<") + std::to_string(a.head_dim) + ", " +
-                                 std::to_string(type) + ">";
-        timing_log(name, (double)n_rows * sh.nsb * block_bytes(type) + (double)n_rows * 4.0 * (res ? 2 : 1), e0, e1);
-    } else {
-        e = hipLaunchKernel(fn, grid, block, args, sh.lds, stream);
-    }
-    if (e != hipSuccess) return (int)e;
-    e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
+    return timed_launch_args(
+        [&] {
+            return LaunchInfo{std::string("kq::kq_attn_oproj<") + std::to_string(a.head_dim) + ", " + std::to_string(type) + ">",
+                              (double)n_rows * sh.nsb * block_bytes(type) + (double)n_rows * 4.0 * (res ? 2 : 1)};
+        },
+        fn, grid, block, sh.lds, stream, args);
 }
 
 }  // namespace kq

@@ -317,19 +317,6 @@ __global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, cons
 // ------------------------------------------------------------------ host side
 namespace {
 
-template <typename K, typename... Args>
-int timed_launch(const char *name, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
-    hipEvent_t e0, e1;
-    if (timing_slot(s, e0, e1)) {
-        hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, e0, e1, 0, args...);
-        timing_log(name, 0.0, e0, e1);
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
-}
-
 std::atomic<int> g_attn_stream{0};
 
 size_t stream_scores_lds(int hd, int gsz) {
@@ -350,15 +337,15 @@ int launch_stream_tile(const AttnArgs &a, bool prompt, int tok0, int nt, uint8_t
     const dim3 ga((unsigned)((a.n_ctx + STREAM_CHUNK - 1) / STREAM_CHUNK), (unsigned)a.n_head_kv, (unsigned)nt);
     const size_t la = stream_scores_lds(HD, gsz);
     int rc = prompt ? timed_launch(HD == 64 ? "kq::kq_attn_stream_scores<64, prompt>" : "kq::kq_attn_stream_scores<128, prompt>",
-                                   kq_attn_stream_scores<HD, true>, ga, dim3(256), la, s, a, scores, tok0)
+                                   0.0, kq_attn_stream_scores<HD, true>, ga, dim3(256), la, s, a, scores, tok0)
                     : timed_launch(HD == 64 ? "kq::kq_attn_stream_scores<64>" : "kq::kq_attn_stream_scores<128>",
-                                   kq_attn_stream_scores<HD, false>, ga, dim3(256), la, s, a, scores, tok0);
+                                   0.0, kq_attn_stream_scores<HD, false>, ga, dim3(256), la, s, a, scores, tok0);
     if (rc) return rc;
-    rc = timed_launch("kq::kq_attn_stream_softmax", kq_attn_stream_softmax, dim3((unsigned)a.n_head, (unsigned)nt),
+    rc = timed_launch("kq::kq_attn_stream_softmax", 0.0, kq_attn_stream_softmax, dim3((unsigned)a.n_head, (unsigned)nt),
                       dim3(STREAM_SM_NT), 0, s, a, scores, p16, tok0);
     if (rc) return rc;
     allow_lds((const void *)kq_attn_stream_kqv<HD>, kStreamKqvLds);
-    return timed_launch(HD == 64 ? "kq::kq_attn_stream_kqv<64>" : "kq::kq_attn_stream_kqv<128>", kq_attn_stream_kqv<HD>,
+    return timed_launch(HD == 64 ? "kq::kq_attn_stream_kqv<64>" : "kq::kq_attn_stream_kqv<128>", 0.0, kq_attn_stream_kqv<HD>,
                         dim3((unsigned)(a.n_head * (HD / STREAM_RS)), (unsigned)nt), dim3(256), kStreamKqvLds, s, a,
                         (const uint16_t *)p16, tok0);
 }

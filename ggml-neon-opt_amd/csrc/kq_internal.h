@@ -1,154 +1,25 @@
-// kq_internal.h — host-side helpers shared by the C-ABI (kq_api.hip) and the
-// backend mirror (kq_backend.hip). Not part of the public ABI.
+// kq_internal.h — host-side helpers shared by the C-ABI (kq_api.hip), the host paths of the
+// kernels and the backend mirror (kq_backend.hip), one section per source file. Not part of
+// the public ABI.
 #pragma once
 
 #include <string>
+#include <tuple>
+
+#include <hip/hip_ext.h>
 
 #include "kq_common.h"
 
 namespace kq {
 
+// ---------------------------------------------------------------- kq_api.hip
 int device_ok();
-bool timing_slot(hipStream_t s, hipEvent_t &a, hipEvent_t &b);
-void timing_log(const std::string &kernel, double bytes, hipEvent_t a, hipEvent_t b);
 int num_cus();
-int choose_ncol(int64_t M, int nb);
-typedef void (*gemv_fn)(const GemvArgs);
-struct GemvPlan {
-    GemvArgs a;
-    dim3 grid;
-    size_t lds;
-    gemv_fn fn;
-    int ncol, tmask;
-    bool fusedq, debug;
-};
-int plan_gemv(const mi355x_gemv_desc *d, int n_desc, int64_t K, int64_t M, int ncol, bool fusedq, bool debug,
-              GemvPlan &pl);
-int launch_gemv(const GemvPlan &pl, hipStream_t stream);
-typedef void (*rows_fn)(KQ_ROWS_PARAMS);
-struct RowsPlan {
-    RowsArgs a;
-    dim3 grid;
-    size_t lds;
-    rows_fn fn;
-    int tmask;
-    bool fusedq;
-    int nwv;  // waves per workgroup (one workgroup per CU): ROWS_WAVES, or ROWS_WAVES_SMALL
-    int lsh = 0;  // fused prologue: 16 << lsh lanes per superblock (rows_pro_form; the kernel's LSH)
-    bool dyn = false;  // kq_rows_dyn: rows claimed from a per-workgroup counter
-    // the longest wave's 16-superblock steps and the ring depth of its type, of the matrix
-    // with the least room in its ring, and the short-stream form (rows_short_form; the kernel's SH)
-    int steps = 0, depth = 0;
-    bool sh = false;
-};
-// Row-stream decode GEMV (kq_rows): returns MI355X_E_UNSUPPORTED when the rows are
-// not contiguous or not aligned for it (callers then use kq_gemv). waves_per_cu = 0:
-// ROWS_WAVES_SMALL waves per workgroup for launches under kRowsSmallBytes of weights,
-// ROWS_WAVES otherwise.
-int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, RowsPlan &pl,
-              int waves_per_cu = 0);
-int launch_rows(const RowsPlan &pl, hipStream_t stream);
-int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps, int nb, int waves, uint8_t *out,
-                             hipStream_t s);
-bool rows_enabled();
-int launch_quantize(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
-                    hipStream_t stream);
-int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *ws, size_t ws_size,
-            hipStream_t stream, const mi355x_gemv_ext *ext = nullptr);
-// kq_ops.hip
-int launch_rms_norm(const float *x, const float *w, float *y, int64_t n, int64_t nrows, float eps, hipStream_t s);
-int launch_binary(int op, const float *a, const float *b, float *y, int64_t n, hipStream_t s,
-                  int64_t nb = 0);  // 0 add, 1 mul; b of nb elements repeated (0: nb = n)
-int launch_attn_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
-// long-cache attention workspace (per stream), before any capture; n_tok > 1: a prompt node
-int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok = 1);
-bool attn_prompt_q8_ok(const AttnArgs &a);  // the group kernel can write a.q8_out
-// kq_attn_stream.hip: streamed attention for caches of up to kAttnStreamMaxCtx cells (mi355x_attn_stream).
-// attn_stream_applies / _prompt_applies: launch_attn / launch_attn_prompt take the streamed kernels
-// for these (checked) arguments; attn_stream_workspace: the bytes of attn_cells_buffer they need
-// (6 per (token of a tile, head, cell)).
-constexpr int kAttnStreamMaxCtx = 131072;
-int attn_stream_mode();                         // 0 off, 1 where the other kernels refuse the cache's size, 2 always
-bool attn_size_refused(const AttnArgs &a);      // n_ctx > 8192 or attn_lds > 64 KB: refused unless streamed
-bool attn_stream_applies(const AttnArgs &a);
-bool attn_stream_prompt_applies(const AttnArgs &a);
-size_t attn_stream_workspace(const AttnArgs &a, int n_tok);
-int launch_attn_stream(const AttnArgs &a, hipStream_t s);
-int launch_attn_stream_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
-// kq_ops.hip pieces the streamed path shares
-size_t attn_lds(int hd, int n_ctx);
-size_t attn_prompt_lds(int hd, int n_ctx);
-void *attn_cells_buffer(size_t bytes, hipStream_t stream, bool may_alloc);
-int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
-// prefill (ne11 >= 16) pieces, for the backend's shared-activation runs
-bool mmq_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M);
-int launch_quantize_q8L(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
-                        hipStream_t stream, bool mmq = false);  // mmq: the prefill GEMMs' Q8L/mmq layout
-int launch_mmq(int type, const void *w, int64_t K, int64_t N, size_t row_stride, const uint8_t *xq, int64_t M,
-               float *y, int64_t y_col_stride, hipStream_t stream, const float *res = nullptr,
-               int64_t res_col_stride = 0);  // res: ADD epilogue
-bool mmq_tile64(int type, int64_t N, int64_t M);  // launch_mmq would use the 64 x 64 tile kernel
-// f16 prefill path (mi355x_prefill_precision F16, csrc/kq_mmf.hip): the activation image
-// (kq_quantize_f16img) at the workspace start, then the GEMM (its split-K slabs after the
-// image); res: ADD epilogue
-bool mmf_on();
-bool mmf_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M, int64_t K);  // + mmf_prefers
-bool mmf_prefers(int type, int64_t N, int64_t K);  // the f16 kernel is the faster one at this shape
-int launch_f16img(const float *x, int64_t x_stride_floats, uint8_t *ws, int64_t K, int64_t M, hipStream_t stream);
-int launch_mmf_gemm(int type, const void *w, int64_t K, int64_t N, size_t row_stride, uint8_t *ws, int64_t M,
-                    float *y, int64_t y_col_stride, hipStream_t stream, const float *res = nullptr,
-                    int64_t res_col_stride = 0);
-// up to 4 matrices of one type on the image in one launch (split-K slabs only where they
-// fit ws_size)
-int launch_mmf_multi(int type, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
-                     float *const *y, const int64_t *y_col_stride, int64_t K, uint8_t *ws, size_t ws_size, int64_t M,
-                     hipStream_t stream, const float *res = nullptr, int64_t res_col_stride = 0);
-// KV-cache store epilogue of launch_mmq_multi (a prompt's k / v projections): kind[d] 1 k,
-// 2 v, 0 none; the cells of kq_kv_store (rope(k) -> f16 rows, v -> f16 transposed)
-struct MmqKv {
-    int kind[4];
-    const int32_t *pos;
-    const float *rope;
-    uint16_t *k_cache, *v_cache;
-    int n_ctx, hd;
-};
-int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
-                     float *const *y, const int64_t *y_col_stride, int64_t K, const uint8_t *xq, int64_t M,
-                     hipStream_t stream, const MmqKv *kv = nullptr);  // types: Q4_K/Q6_K may mix (kq_mmq_mixed)
-// prefill prologues: rms_norm(x) * w -> Q8L, swiglu(g, u) -> Q8L (nrows rows of n)
-int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s);
-int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s);
-int launch_swiglu(const float *g, const float *u, float *y, int64_t n, hipStream_t s);
-int attn_args_from(const mi355x_attn_desc *d, AttnArgs &a);  // + check_attn
-int launch_attn(const AttnArgs &a, hipStream_t s);
-bool attn_group_ok(const AttnArgs &a, int nwaves);      // the one-workgroup-per-kv-group path applies
-size_t attn_group_bytes(const AttnArgs &a, int nwaves);  // its LDS
-// kq_attn_oproj.hip: decode attention + the o-proj GEMV (+ residual ADD) in one launch.
-// attn_oproj_buffer: bytes of the device buffer it needs (arrival counters, zeroed once,
-// then the records), 0 when the shape is not supported; *nsb: the superblocks of K.
-constexpr size_t kAttnOprojCounterBytes = 1024;
-constexpr int kAttnOprojMaxCtx = 256;  // kq_attn_oproj fuses caches of at most this many cells
-size_t attn_oproj_buffer(int hd, int n_head, int n_head_kv, int n_ctx, int type, int64_t K, int64_t n_rows, int *nsb);
-int launch_attn_oproj(const AttnArgs &a, int type, const void *w, int64_t n_rows, size_t row_stride, const float *res,
-                      float *y, uint8_t *buf, size_t buf_size, hipStream_t stream);
-// kq_attn_batch.hip: the attention block with cells and mask from the graph. attn_batch_args_from
-// checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /
-// MI355X_ATTN_HEAD, or MI355X_E_UNSUPPORTED where neither form's LDS fits.
-int attn_batch_args_from(const mi355x_attn_batch_desc *d, int n_pos, AttnBatchArgs &b);
-int attn_batch_form(const AttnBatchArgs &b);
-int launch_attn_batch(const AttnBatchArgs &b, hipStream_t s);
-int attn_impl();  // mi355x_attn_impl (kq_ops.hip)
-size_t attn_lds16(int hd, int n_ctx);  // attn_head's LDS per head, 16-B multiple (kq_attn_oproj.hip)
-// kq_layer.hip: one decode layer as one persistent launch. The caller fills E, F, nq, nkv,
-// type / w, y, x, the norms, eps, att / x1 / h / x2, at (rope_row 1), sync, err; layer_plan
-// checks the shape and fills the rest (grid, attention placement, ring depth, LDS layout).
-int layer_plan(LayerArgs &a, int hd, int n_head);
-int launch_layer(const LayerArgs &a, hipStream_t stream);
-int64_t layer_table_stride(const LayerArgs &a);                  // bytes per workgroup's step lists (-1: too long)
-void layer_table_fill(const LayerArgs &a, uint8_t *buf, int64_t stride);  // G tables (host memory)
+constexpr size_t kMaxLds = 160 * 1024;    // LDS per CU (one workgroup may use it all)
+constexpr size_t kTargetLds = 80 * 1024;  // aim for >= 2 resident workgroups per CU
+void allow_lds(const void *fn, size_t lds);  // dynamic LDS above 64 KB must be opted into per kernel
+int resident_wgs(const void *fn, size_t lds);  // workgroups of WG_THREADS resident per CU (cached)
 uint64_t *diag_stamps(int64_t *cap);  // mi355x_diag_stamps' buffer (diagnostic builds)
-// kq_api.hip
-void allow_lds(const void *fn, size_t lds);
 // Experiment / diagnostic knobs of A/B runs. The product reads no environment: a knob
 // holds its product default until mi355x_debug_knob() sets it (tools only), and every
 // knob that changes a launch plan bumps knob_generation() (part of the graph key).
@@ -182,5 +53,221 @@ uint32_t knob_generation();
 // mmq impl; attention decode / prompt impl), packed for the backend's graph key.
 uint64_t api_selector_key();
 uint64_t ops_selector_key();
+// Launch timing (mi355x_timing_enable): timing_slot returns true (and the events) when this
+// launch should be timed. Called by timed_launch alone.
+bool timing_slot(hipStream_t s, hipEvent_t &a, hipEvent_t &b);
+void timing_log(const std::string &kernel, double bytes, hipEvent_t a, hipEvent_t b);
+
+// The one launch sequence of the library: with timing on (and no capture) the kernel runs
+// between two events and is logged under info()'s name and algorithmic bytes, else it is
+// launched plainly; either way the launch's error, or the runtime's last one, is returned.
+// info() -> LaunchInfo runs on the timed branch only: an untimed launch builds no name.
+struct LaunchInfo {
+    std::string name;
+    double bytes;
+};
+template <typename Info>
+int timed_launch_args(Info &&info, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, void **args) {
+    hipEvent_t e0, e1;
+    hipError_t e;
+    if (timing_slot(s, e0, e1)) {
+        e = hipExtLaunchKernel(fn, grid, block, args, lds, s, e0, e1, 0);
+        const LaunchInfo li = info();
+        timing_log(li.name, li.bytes, e0, e1);
+    } else {
+        e = hipLaunchKernel(fn, grid, block, args, lds, s);
+    }
+    if (e != hipSuccess) return (int)e;
+    e = hipGetLastError();
+    return e == hipSuccess ? MI355X_OK : (int)e;
+}
+// Typed kernels: the arguments are converted to the kernel's parameter types (as
+// hipLaunchKernelGGL does) and passed by address.
+template <typename Info, typename... P, typename... Args>
+int timed_launch_lazy(Info &&info, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                      Args &&...args) {
+    static_assert(sizeof...(P) == sizeof...(Args), "one argument per kernel parameter");
+    std::tuple<P...> params{static_cast<P>(args)...};
+    return std::apply(
+        [&](P &...p) {
+            void *ptrs[] = {(void *)&p...};
+            return timed_launch_args(info, (const void *)kern, grid, block, lds, s, ptrs);
+        },
+        params);
+}
+template <typename... P, typename... Args>
+int timed_launch(const char *name, double bytes, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                 Args &&...args) {
+    return timed_launch_lazy([&] { return LaunchInfo{name, bytes}; }, kern, grid, block, lds, s,
+                             static_cast<Args &&>(args)...);
+}
+
+// ---------------------------------------------------------------- kq_gemv_host.hip
+// The decode GEMVs' host path: descriptor checks, both planners, their launches, gemv_m1.
+constexpr int64_t kFusedQMaxNb = 32;                              // kq_gemv: in-kernel quantization up to K = 8192
+constexpr int64_t kRowsFusedMaxNb = ROWS_QPASS * 4 * ROWS_WAVES;  // kq_rows: up to K = 36864
+// launches below this many weight bytes: ROWS_WAVES_SMALL waves. 10 MB -> 5 MB in round 5
+// (TinyLlama's 6.5 / 9.5 MB ffn_down and the 8B's 9.4 MB o-proj on 12 waves): both tokens
+// +0.3 %, six of six interleaved comparisons; 0 (never) -0.8 % (profiles/r05_gemv_small_mb_ab.txt)
+constexpr double kRowsSmallBytes = 5e6;  // (KNOB_GEMV_SMALL_MB's default)
+int choose_ncol(int64_t M, int nb);
+typedef void (*gemv_fn)(const GemvArgs);
+struct GemvPlan {
+    GemvArgs a;
+    dim3 grid;
+    size_t lds;
+    gemv_fn fn;
+    int ncol, tmask;
+    bool fusedq, debug;
+};
+int plan_gemv(const mi355x_gemv_desc *d, int n_desc, int64_t K, int64_t M, int ncol, bool fusedq, bool debug,
+              GemvPlan &pl);
+int launch_gemv(const GemvPlan &pl, hipStream_t stream);
+typedef void (*rows_fn)(KQ_ROWS_PARAMS);
+struct RowsPlan {
+    RowsArgs a;
+    dim3 grid;
+    size_t lds;
+    rows_fn fn;
+    int tmask;
+    bool fusedq;
+    int nwv;  // waves per workgroup (one workgroup per CU): ROWS_WAVES, or ROWS_WAVES_SMALL
+    int lsh = 0;  // fused prologue: 16 << lsh lanes per superblock (rows_pro_form; the kernel's LSH)
+    bool dyn = false;  // kq_rows_dyn: rows claimed from a per-workgroup counter
+    // the longest wave's 16-superblock steps and the ring depth of its type, of the matrix
+    // with the least room in its ring, and the short-stream form (rows_short_form; the kernel's SH)
+    int steps = 0, depth = 0;
+    bool sh = false;
+};
+// Row-stream decode GEMV (kq_rows): returns MI355X_E_UNSUPPORTED when the rows are
+// not contiguous or not aligned for it (callers then use kq_gemv). pro: ROWS_PRO_* (the fused
+// prologue; ROWS_PRO_NONE unless fusedq). waves_per_cu = 0: ROWS_WAVES_SMALL waves per
+// workgroup for launches under kRowsSmallBytes of weights, ROWS_WAVES otherwise. pl.fn is the
+// kernel launch_rows launches: nothing picks it again.
+int plan_rows(const mi355x_gemv_desc *d, int n_desc, int64_t K, bool fusedq, int pro, RowsPlan &pl,
+              int waves_per_cu = 0);
+int launch_rows(const RowsPlan &pl, hipStream_t stream);
+int rows_kernel_id(rows_fn fn);  // mi355x_debug_rows_plan's `kernel` field
+int rows_pro_kind(int prologue);  // MI355X_PRO_* -> ROWS_PRO_*
+bool rows_enabled();
+int gemv_impl_select(int impl);  // mi355x_gemv_impl / mi355x_gemv_waves: set, return the previous; < 0: query
+int rows_waves_select(int waves);
+int launch_quantize(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
+                    hipStream_t stream);
+int launch_quantize_q8L(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
+                        hipStream_t stream, bool mmq = false);  // mmq: the prefill GEMMs' Q8L/mmq layout
+size_t ext_x_bytes(int64_t k);  // the staged prologue's f32 row at the workspace start
+int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *ws, size_t ws_size,
+            hipStream_t stream, const mi355x_gemv_ext *ext = nullptr);
+
+// ---------------------------------------------------------------- kq_prefill_host.hip
+// prefill (ne11 >= kMmqMinCols) pieces, for the backend's shared-activation runs
+constexpr int64_t kMmqMinCols = 16;  // below this the NCOL GEMV streams the weights fewer times
+int mmq_impl();  // mi355x_mmq_impl / mi355x_prefill_precision: the selectors and their setters
+void mmq_impl_set(int impl);
+int prefill_precision();
+void prefill_precision_set(int precision);
+bool mmq_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M);
+int launch_mmq(int type, const void *w, int64_t K, int64_t N, size_t row_stride, const uint8_t *xq, int64_t M,
+               float *y, int64_t y_col_stride, hipStream_t stream, const float *res = nullptr,
+               int64_t res_col_stride = 0);  // res: ADD epilogue
+bool mmq_tile64(int type, int64_t N, int64_t M);  // launch_mmq would use the 64 x 64 tile kernel
+// f16 prefill path (mi355x_prefill_precision F16, csrc/kq_mmf.hip): the activation image
+// (kq_quantize_f16img) at the workspace start, then the GEMM (its split-K slabs after the
+// image); res: ADD epilogue
+bool mmf_on();
+bool mmf_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M, int64_t K);  // + mmf_prefers
+bool mmf_prefers(int type, int64_t N, int64_t K);  // the f16 kernel is the faster one at this shape
+int launch_f16img(const float *x, int64_t x_stride_floats, uint8_t *ws, int64_t K, int64_t M, hipStream_t stream);
+int launch_mmf_gemm(int type, const void *w, int64_t K, int64_t N, size_t row_stride, uint8_t *ws, int64_t M,
+                    float *y, int64_t y_col_stride, hipStream_t stream, const float *res = nullptr,
+                    int64_t res_col_stride = 0);
+// up to 4 matrices of one type on the image in one launch (split-K slabs only where they
+// fit ws_size)
+int launch_mmf_multi(int type, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
+                     float *const *y, const int64_t *y_col_stride, int64_t K, uint8_t *ws, size_t ws_size, int64_t M,
+                     hipStream_t stream, const float *res = nullptr, int64_t res_col_stride = 0);
+size_t mmf_workspace(int64_t N, int64_t M, int64_t nb);  // activation image + d*bsum16 (+ the split-K slabs)
+// KV-cache store epilogue of launch_mmq_multi (a prompt's k / v projections): kind[d] 1 k,
+// 2 v, 0 none; the cells of kq_kv_store (rope(k) -> f16 rows, v -> f16 transposed)
+struct MmqKv {
+    int kind[4];
+    const int32_t *pos;
+    const float *rope;
+    uint16_t *k_cache, *v_cache;
+    int n_ctx, hd;
+};
+int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
+                     float *const *y, const int64_t *y_col_stride, int64_t K, const uint8_t *xq, int64_t M,
+                     hipStream_t stream, const MmqKv *kv = nullptr);  // types: Q4_K/Q6_K may mix (kq_mmq_mixed)
+
+// ---------------------------------------------------------------- kq_rows.hip
+int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps, int nb, int waves, uint8_t *out,
+                             hipStream_t s);
+// prefill prologues: rms_norm(x) * w -> Q8L, swiglu(g, u) -> Q8L (nrows rows of n)
+int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s);
+int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s);
+
+// ---------------------------------------------------------------- kq_ops.hip
+int launch_rms_norm(const float *x, const float *w, float *y, int64_t n, int64_t nrows, float eps, hipStream_t s);
+int launch_binary(int op, const float *a, const float *b, float *y, int64_t n, hipStream_t s,
+                  int64_t nb = 0);  // 0 add, 1 mul; b of nb elements repeated (0: nb = n)
+int launch_attn_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
+// long-cache attention workspace (per stream), before any capture; n_tok > 1: a prompt node
+int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok = 1);
+bool attn_prompt_q8_ok(const AttnArgs &a);  // the group kernel can write a.q8_out
+int launch_swiglu(const float *g, const float *u, float *y, int64_t n, hipStream_t s);
+int attn_args_from(const mi355x_attn_desc *d, AttnArgs &a);  // + check_attn
+int launch_attn(const AttnArgs &a, hipStream_t s);
+bool attn_group_ok(const AttnArgs &a, int nwaves);      // the one-workgroup-per-kv-group path applies
+size_t attn_group_bytes(const AttnArgs &a, int nwaves);  // its LDS
+int attn_impl();  // mi355x_attn_impl (kq_ops.hip)
+// pieces the streamed path shares
+size_t attn_lds(int hd, int n_ctx);
+size_t attn_prompt_lds(int hd, int n_ctx);
+void *attn_cells_buffer(size_t bytes, hipStream_t stream, bool may_alloc);
+int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
+
+// ---------------------------------------------------------------- kq_attn_stream.hip
+// Streamed attention for caches of up to kAttnStreamMaxCtx cells (mi355x_attn_stream).
+// attn_stream_applies / _prompt_applies: launch_attn / launch_attn_prompt take the streamed kernels
+// for these (checked) arguments; attn_stream_workspace: the bytes of attn_cells_buffer they need
+// (6 per (token of a tile, head, cell)).
+constexpr int kAttnStreamMaxCtx = 131072;
+int attn_stream_mode();                         // 0 off, 1 where the other kernels refuse the cache's size, 2 always
+bool attn_size_refused(const AttnArgs &a);      // n_ctx > 8192 or attn_lds > 64 KB: refused unless streamed
+bool attn_stream_applies(const AttnArgs &a);
+bool attn_stream_prompt_applies(const AttnArgs &a);
+size_t attn_stream_workspace(const AttnArgs &a, int n_tok);
+int launch_attn_stream(const AttnArgs &a, hipStream_t s);
+int launch_attn_stream_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
+
+// ---------------------------------------------------------------- kq_attn_oproj.hip
+// Decode attention + the o-proj GEMV (+ residual ADD) in one launch.
+// attn_oproj_buffer: bytes of the device buffer it needs (arrival counters, zeroed once,
+// then the records), 0 when the shape is not supported; *nsb: the superblocks of K.
+constexpr size_t kAttnOprojCounterBytes = 1024;
+constexpr int kAttnOprojMaxCtx = 256;  // kq_attn_oproj fuses caches of at most this many cells
+size_t attn_oproj_buffer(int hd, int n_head, int n_head_kv, int n_ctx, int type, int64_t K, int64_t n_rows, int *nsb);
+int launch_attn_oproj(const AttnArgs &a, int type, const void *w, int64_t n_rows, size_t row_stride, const float *res,
+                      float *y, uint8_t *buf, size_t buf_size, hipStream_t stream);
+size_t attn_lds16(int hd, int n_ctx);  // attn_head's LDS per head, 16-B multiple (kq_attn_oproj.hip)
+
+// ---------------------------------------------------------------- kq_attn_batch.hip
+// The attention block with cells and mask from the graph. attn_batch_args_from
+// checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /
+// MI355X_ATTN_HEAD, or MI355X_E_UNSUPPORTED where neither form's LDS fits.
+int attn_batch_args_from(const mi355x_attn_batch_desc *d, int n_pos, AttnBatchArgs &b);
+int attn_batch_form(const AttnBatchArgs &b);
+int launch_attn_batch(const AttnBatchArgs &b, hipStream_t s);
+
+// ---------------------------------------------------------------- kq_layer.hip
+// One decode layer as one persistent launch. The caller fills E, F, nq, nkv,
+// type / w, y, x, the norms, eps, att / x1 / h / x2, at (rope_row 1), sync, err; layer_plan
+// checks the shape and fills the rest (grid, attention placement, ring depth, LDS layout).
+int layer_plan(LayerArgs &a, int hd, int n_head);
+int launch_layer(const LayerArgs &a, hipStream_t stream);
+int64_t layer_table_stride(const LayerArgs &a);                  // bytes per workgroup's step lists (-1: too long)
+void layer_table_fill(const LayerArgs &a, uint8_t *buf, int64_t stride);  // G tables (host memory)
 
 }  // namespace kq

@@ -915,20 +915,14 @@ int launch_layer(const LayerArgs &a, hipStream_t stream) {
     const void *fn = a.at.head_dim == 64 ? (const void *)kq_layer<64> : (const void *)kq_layer<128>;
     allow_lds(fn, (size_t)a.lds);
     void *args[] = {const_cast<LayerArgs *>(&a)};
-    hipEvent_t e0, e1;
-    hipError_t e;
-    if (timing_slot(stream, e0, e1)) {
-        e = hipExtLaunchKernel(fn, dim3((unsigned)a.G), dim3(LAYER_WAVES * 64), args, (size_t)a.lds, stream, e0, e1, 0);
-        double bytes = 0;
-        const int64_t rows[7] = {a.nq, a.nkv, a.nkv, a.E, a.F, a.F, a.E};
-        for (int m = 0; m < 7; ++m) bytes += (double)rows[m] * (m == 6 ? a.nb_f : a.nb_e) * block_bytes(a.type[m]);
-        timing_log(std::string("kq::kq_layer<") + std::to_string(a.at.head_dim) + ">", bytes, e0, e1);
-    } else {
-        e = hipLaunchKernel(fn, dim3((unsigned)a.G), dim3(LAYER_WAVES * 64), args, (size_t)a.lds, stream);
-    }
-    if (e != hipSuccess) return (int)e;
-    e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
+    return timed_launch_args(
+        [&] {
+            double bytes = 0;
+            const int64_t rows[7] = {a.nq, a.nkv, a.nkv, a.E, a.F, a.F, a.E};
+            for (int m = 0; m < 7; ++m) bytes += (double)rows[m] * (m == 6 ? a.nb_f : a.nb_e) * block_bytes(a.type[m]);
+            return LaunchInfo{std::string("kq::kq_layer<") + std::to_string(a.at.head_dim) + ">", bytes};
+        },
+        fn, dim3((unsigned)a.G), dim3(LAYER_WAVES * 64), (size_t)a.lds, stream, args);
 }
 
 }  // namespace kq

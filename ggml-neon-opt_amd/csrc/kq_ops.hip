@@ -1030,24 +1030,6 @@ int attn_slices(const AttnArgs &a) {
 }
 
 // ------------------------------------------------------------ launch helpers
-int check_launch() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
-}
-
-template <typename K, typename... Args>
-int timed_launch(const char *name, double bytes, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s,
-                 Args... args) {
-    hipEvent_t e0, e1;
-    if (timing_slot(s, e0, e1)) {
-        hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, e0, e1, 0, args...);
-        timing_log(name, bytes, e0, e1);
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
-    }
-    return check_launch();
-}
-
 int elem_grid(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);

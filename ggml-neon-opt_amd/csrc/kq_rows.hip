@@ -236,33 +236,17 @@ __global__ void __launch_bounds__(256) kq_swiglu_q8L(const float *__restrict__ g
 
 int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s) {
     if (nrows == 0) return MI355X_OK;
-    hipEvent_t e0, e1;
     const size_t lds = (size_t)(n / QK) * 8 + 8;
-    if (timing_slot(s, e0, e1)) {
-        hipExtLaunchKernelGGL(kq_rms_norm_q8L, dim3((unsigned)nrows), dim3(256), (uint32_t)lds, s, e0, e1, 0, x, w,
-                              (uint8_t *)yq, n, eps);
-        timing_log("kq::kq_rms_norm_q8L", (double)nrows * (n * 4.0 + (n / QK) * (double)Q8L_STRIDE) + n * 4.0, e0, e1);
-    } else {
-        hipLaunchKernelGGL(kq_rms_norm_q8L, dim3((unsigned)nrows), dim3(256), lds, s, x, w, (uint8_t *)yq, n, eps);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
+    return timed_launch("kq::kq_rms_norm_q8L", (double)nrows * (n * 4.0 + (n / QK) * (double)Q8L_STRIDE) + n * 4.0,
+                        kq_rms_norm_q8L, dim3((unsigned)nrows), dim3(256), lds, s, x, w, (uint8_t *)yq, n, eps);
 }
 
 int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s) {
     const int64_t nb = n / QK, nblocks = nb * nrows;
     if (nblocks == 0) return MI355X_OK;
     const int64_t wgs = (nblocks + 15) / 16;
-    hipEvent_t e0, e1;
-    if (timing_slot(s, e0, e1)) {
-        hipExtLaunchKernelGGL(kq_swiglu_q8L, dim3((unsigned)wgs), dim3(256), 0, s, e0, e1, 0, g, u, (uint8_t *)yq,
-                              (int)nb, nblocks);
-        timing_log("kq::kq_swiglu_q8L", (double)nblocks * (QK * 8.0 + Q8L_STRIDE), e0, e1);
-    } else {
-        hipLaunchKernelGGL(kq_swiglu_q8L, dim3((unsigned)wgs), dim3(256), 0, s, g, u, (uint8_t *)yq, (int)nb, nblocks);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI355X_OK : (int)e;
+    return timed_launch("kq::kq_swiglu_q8L", (double)nblocks * (QK * 8.0 + Q8L_STRIDE), kq_swiglu_q8L, dim3((unsigned)wgs),
+                        dim3(256), 0, s, g, u, (uint8_t *)yq, (int)nb, nblocks);
 }
 
 // ---------------------------------------------------------------- kernel entry

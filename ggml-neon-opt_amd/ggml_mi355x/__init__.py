@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_attn_prompt_impl", "mi355x_attn_stream",
     "mi355x_attn_batch", "mi355x_attn_batch_path",
     "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
+    "mi355x_debug_rows_plan",
 )
 
 
@@ -189,6 +190,10 @@ def lib():
         L.mi355x_rows_stream_plan.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i64), i32, i64, i32,
                                               ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.mi355x_rows_stream_plan.restype = i32
+    if hasattr(L, "mi355x_debug_rows_plan"):
+        L.mi355x_debug_rows_plan.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i64), i32, i64, i32, i32,
+                                             ctypes.POINTER(i64), i32]
+        L.mi355x_debug_rows_plan.restype = i32
     L.mi355x_debug_rows_prologue.argtypes = [i32, vp, vp, ctypes.c_float, i64, i32, vp, sz, vp]
     L.mi355x_debug_rows_prologue.restype = i32
     L.mi355x_backend_init.argtypes = [i32]
@@ -469,6 +474,27 @@ def rows_stream_plan(mats, k, batch_rows=0):
     rc = int(lib().mi355x_rows_stream_plan(types, rows, n, k, batch_rows, ctypes.byref(steps), ctypes.byref(depth),
                                            ctypes.byref(form)))
     return (steps.value, depth.value, form.value) if rc == 0 else rc
+
+
+ROWS_PLAN_FIELDS = ("tmask", "nwv", "grid_x", "lds", "lsh", "sh", "dyn", "steps", "depth", "waves_total",
+                    *(f"wave_prefix{i}" for i in range(MAX_FUSED + 1)), *(f"rbase{i}" for i in range(MAX_FUSED)),
+                    *(f"rrem{i}" for i in range(MAX_FUSED)), "rpw", "bR", "prio_bytes", "pre0", "dyn_u", "dyn_ush",
+                    "dyn_p", "kernel")
+
+
+def rows_plan(mats, k, fusedq=True, prologue=0):
+    """The whole host plan of one decode GEMV launch of `mats` = [(type, n_rows), ...] over
+    k-element rows (mi355x_debug_rows_plan: no launch, no device): a dict keyed by
+    ROWS_PLAN_FIELDS (`kernel`: the selected instantiation, see the header); or the error code."""
+    n = len(mats)
+    types = (ctypes.c_int32 * n)(*[int(t) for t, _ in mats])
+    rows = (ctypes.c_int64 * n)(*[int(r) for _, r in mats])
+    out = (ctypes.c_int64 * len(ROWS_PLAN_FIELDS))()
+    rc = int(lib().mi355x_debug_rows_plan(types, rows, n, k, int(bool(fusedq)), prologue, out, len(out)))
+    if rc < 0:
+        return rc
+    assert rc == len(ROWS_PLAN_FIELDS), rc
+    return dict(zip(ROWS_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=None):

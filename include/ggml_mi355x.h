@@ -235,6 +235,18 @@ int mi355x_rows_prologue_plan(int64_t k, int waves, int64_t steps, int *lanes, i
 enum { MI355X_ROWS_LONG = 0, MI355X_ROWS_SHORT = 1, MI355X_ROWS_CLAIMED = 2 };
 int mi355x_rows_stream_plan(const int *types, const int64_t *n_rows, int n, int64_t k, int batch_rows, int *steps,
                             int *depth, int *form);
+/* The whole host plan of one kq_rows / kq_rows_dyn launch (no launch, no device access), for the
+ * matrices of mi355x_rows_stream_plan; fusedq: the activation is quantized inside the kernel
+ * (else a Q8L row is read), prologue: MI355X_PRO_* (MI355X_PRO_NONE unless fusedq). Writes
+ * MI355X_ROWS_PLAN_FIELDS integers to out (cap: its length) and returns that count, or a
+ * negative error. In order: tmask, nwv, grid_x, lds, lsh, sh, dyn, steps, depth, waves_total,
+ * wave_prefix[0..4], rbase[0..3], rrem[0..3], rpw, bR, prio_bytes, pre0, dyn_u, dyn_ush, dyn_p,
+ * kernel. kernel names the selected instantiation, not an address:
+ * ((((dyn_kernel * 8 + TMASK) * 2 + FUSEDQ) * 4 + PRO) * 4 + LSH) * 2 + SH, dyn_kernel 0 for
+ * kq_rows and 1 for kq_rows_dyn, a parameter the instantiation does not have as 0. */
+enum { MI355X_ROWS_PLAN_FIELDS = 31 };
+int mi355x_debug_rows_plan(const int *types, const int64_t *n_rows, int n, int64_t k, int fusedq, int prologue,
+                           int64_t *out, int cap);
 /* Debug/parity hook: the fused GEMV prologue alone. One workgroup of `waves` waves loads x
  * (and x2), applies `prologue` (MI355X_PRO_*: x2 = norm weight / up, x = gate) and quantizes
  * to Q8_K exactly as the decode GEMV does before its barrier, then copies the workgroup's

@@ -198,7 +198,7 @@ def test_bad_positions_sixteen_heads(dev, O, hd):
 # ---------------------------------------------------------------- 2: the two graph fusions
 Q4_K, Q6_K = 12, 14
 GRAPH_T, GRAPH_E, GRAPH_OUT = 37, 512, 256
-# the activation quantizer's logged name (ggml-neon-opt_amd/csrc/kq_api.hip: launch_quantize_q8L)
+# the activation quantizer's logged name (ggml-neon-opt_amd/csrc/kq_gemv_host.hip: launch_quantize_q8L)
 QUANTIZE = "kq_quantize_q8L"
 
 
