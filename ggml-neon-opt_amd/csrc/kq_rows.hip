@@ -13,8 +13,8 @@
 //    per-wave ring, completion by counted s_waitcnt vmcnt (a constant in steady
 //    state); no workgroup barrier after the prologue;
 //  * lane quad q computes superblock 16t+q of the stream (4 lanes x 64 quants,
-//    v_dot4_i32_i8, 2 DPP adds) and its leader stores the exact fp32 operands of
-//    the reference's update as a 16-B record, block-major per row batch;
+//    v_dot4_i32_i8, 2 DPP adds) and its leader stores what the reference's fp32
+//    update consumes as a 16-B record of floats (RowRec), block-major per row batch;
 //  * when a batch of bR rows is complete, lane r replays row r's records in
 //    superblock order (the serial fp32 chain, 64 rows per instruction);
 //  * the activation is quantized to Q8_K once per workgroup into LDS (aligned
@@ -741,7 +741,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const RowsLayout L = rows_layout(nb, TMASK, bR, h.rpw, nwv);
     uint8_t *const ring = smem + L.ring + wave * L.ring_stride;
     uint8_t *const ring_end = ring + D * SLOT;
-    Rec *const recs = (Rec *)(smem + L.recs + wave * L.recs_stride);
+    RowRec *const recs = (RowRec *)(smem + L.recs + wave * L.recs_stride);
     float *const outs = (float *)(smem + L.outs + wave * L.outs_stride);
     const uint8_t *const actq = smem + L.act;
 
@@ -773,7 +773,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         e_act = L.act + e_io * Q8L_STRIDE;
         // (24-bit multiply: the 64-bit multiply-add the compiler picks for io * bR + rr names a
         // register pair whose unused half can be the residual load's, in flight here)
-        e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(Rec);
+        e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(RowRec);
     }
 
     // L2 prefetch (uniform per wave): only streams longer than the ring, fused path
@@ -954,19 +954,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 const int imin = quad_sum(r.imin);
                 if (s == 0) {
                     const float yd = *(const float *)ab;
-                    Rec rec;
-                    if (TYPE == Q6_K) {
-                        rec.a = isum - 32 * imin;
-                        rec.b = 0;
-                        rec.c = h2f(r.dh) * yd;  // d_all * y.d
-                        rec.e = 0.f;
-                    } else {
-                        rec.a = isum;
-                        rec.b = imin;
-                        rec.c = yd * h2f(r.dh & 0xffffu);  // y.d * fp16(x.d)
-                        rec.e = yd * h2f(r.dh >> 16);      // y.d * fp16(x.dmin)
-                    }
-                    *(Rec *)(smem + e_rec) = rec;
+                    row_rec_store<TYPE>((RowRec *)(smem + e_rec), isum, imin, r.dh, yd);
                 }
             }
             if (advance) {
@@ -974,7 +962,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 e_io += e_b16, e_rr += e_a16;
                 if (e_io >= nb) e_io -= nb, ++e_rr;
                 e_act = L.act + e_io * Q8L_STRIDE;
-                e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(Rec);
+                e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(RowRec);
             }
         };
         if constexpr (KQ_ROWS_SHORT_UNROLL != 0) {
@@ -1008,9 +996,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             wave_lds_fence();
             sc = RSTAMP();
             if (lane < h.nrows) {
-                const Rec *rc = (const Rec *)(smem + L.recs + wave * L.recs_stride) + lane;
-#pragma unroll 4
-                for (int i = 0; i < nb; ++i) v = chain_step(TYPE, rc[i * bR], v);
+                v = rows_chain<TYPE>((const RowRec *)(smem + L.recs + wave * L.recs_stride) + lane, nb, bR);
             }
             if (KQ_ROWS_DIAG) asm volatile("" : "+v"(v));  // (the stamp behind the value)
             st2 = RSTAMP();
@@ -1087,19 +1073,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             const int imin = quad_sum(r.imin);
             if (s == 0) {
                 const float yd = *(const float *)ab;
-                Rec rec;
-                if (TYPE == Q6_K) {
-                    rec.a = isum - 32 * imin;
-                    rec.b = 0;
-                    rec.c = h2f(r.dh) * yd;  // d_all * y.d
-                    rec.e = 0.f;
-                } else {
-                    rec.a = isum;
-                    rec.b = imin;
-                    rec.c = yd * h2f(r.dh & 0xffffu);  // y.d * fp16(x.d)
-                    rec.e = yd * h2f(r.dh >> 16);      // y.d * fp16(x.dmin)
-                }
-                recs[io * bR + rr] = rec;
+                row_rec_store<TYPE>(recs + io * bR + rr, isum, imin, r.dh, yd);
             }
         }
         cslot = cslot + SLOT == ring_end ? ring : cslot + SLOT;
@@ -1122,11 +1096,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             if (RSTAMPS(h) && brow == 0) sc = __builtin_amdgcn_s_memrealtime();
             const int nr = bR < h.nrows - brow ? bR : h.nrows - brow;
             if (lane < nr) {
-                float v = 0.f;
-                const Rec *rc = recs + lane;
-#pragma unroll 4
-                for (int i = 0; i < nb; ++i) v = chain_step(TYPE, rc[i * bR], v);
-                outs[brow + lane] = v;
+                outs[brow + lane] = rows_chain<TYPE>(recs + lane, nb, bR);
             }
             brow += bR;
             rr -= bR;
@@ -1302,7 +1272,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
     const RowsDynLayout L = rows_dyn_layout(nb, TMASK, bR, h.rpw, nwv);
     uint8_t *const ring = smem + L.ring + wave * L.ring_stride;
     uint8_t *const ring_end = ring + D * SLOT;
-    Rec *const recs = (Rec *)(smem + L.recs + wave * L.recs_stride);
+    RowRec *const recs = (RowRec *)(smem + L.recs + wave * L.recs_stride);
     float *const outs = (float *)(smem + L.outs);
     uint32_t *const cnt = (uint32_t *)(smem + L.cnt);
     const uint8_t *const actq = smem + L.act;
@@ -1479,11 +1449,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
     auto replay = [&]() {  // the batch's rows: lane r <-> batch row r, records in superblock order
         wave_lds_fence();
         if (lane < bro) {
-            float v = 0.f;
-            const Rec *rc = recs + lane;
-#pragma unroll 4
-            for (int i = 0; i < nb; ++i) v = chain_step(TYPE, rc[i * bR], v);
-            outs[bfl] = v;
+            outs[bfl] = rows_chain<TYPE>(recs + lane, nb, bR);
         }
         wave_lds_fence();
         bro = 0;
@@ -1502,19 +1468,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
             const int imin = quad_sum(r.imin);
             if (s == 0) {
                 const float yd = *(const float *)ab;
-                Rec rec;
-                if (TYPE == Q6_K) {
-                    rec.a = isum - 32 * imin;
-                    rec.b = 0;
-                    rec.c = h2f(r.dh) * yd;  // d_all * y.d
-                    rec.e = 0.f;
-                } else {
-                    rec.a = isum;
-                    rec.b = imin;
-                    rec.c = yd * h2f(r.dh & 0xffffu);  // y.d * fp16(x.d)
-                    rec.e = yd * h2f(r.dh >> 16);      // y.d * fp16(x.dmin)
-                }
-                recs[io * bR + rr] = rec;
+                row_rec_store<TYPE>(recs + io * bR + rr, isum, imin, r.dh, yd);
             }
         }
         cslot = cslot + SLOT == ring_end ? ring : cslot + SLOT;

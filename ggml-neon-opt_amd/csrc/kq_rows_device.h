@@ -361,6 +361,112 @@ __device__ __forceinline__ int quad_sum(int v) {
     return v;
 }
 
+// ---------------------------------------------------------------- kq_rows' records and chain
+// kq_rows keeps its records in LDS, written by the quad leaders and replayed by lane r for row r
+// (kq_rows.hip). CHAIN_REC (a build constant, A/B: make variant-rows, profiles/r12_chain_ab.txt;
+// 0 is the form before it): the leader stores what the chain consumes, as floats (RowRec), so
+// the conversions leave the serial chain for the leaders, where 16 of them run at once. The same
+// instruction on the same operand gives the same bits in either place.
+#ifndef KQ_ROWS_CHAIN_REC
+#define KQ_ROWS_CHAIN_REC 1
+#endif
+
+#if KQ_ROWS_CHAIN_REC
+// 16 B as Rec, so the LDS layouts stand. Q4_K: a = (float)sumi, c = y.d * d, b = (float)summins,
+// e = y.d * dmin; Q5_K: a = the superblock's whole term (it does not depend on the running sum);
+// Q6_K: a = (float)(isum - 32 * isum_mins), c = d_all * y.d. Fields a type does not use are
+// neither stored nor read.
+struct RowRec {
+    float a, c, b, e;
+};
+static_assert(sizeof(RowRec) == sizeof(Rec), "the record layouts of rows_layout / rows_dyn_layout");
+#else
+typedef Rec RowRec;
+#endif
+
+// The leader's record of one superblock, stored at `p` (LDS). dh: QuadOut's.
+template <int TYPE>
+__device__ __forceinline__ void row_rec_store(RowRec *p, int isum, int imin, uint32_t dh, float yd) {
+#if KQ_ROWS_CHAIN_REC
+    if (TYPE == Q6_K) {
+        const float a = (float)(isum - 32 * imin), c = h2f(dh) * yd;  // d_all * y.d
+        *(float2 *)p = make_float2(a, c);
+    } else {
+        const float c = yd * h2f(dh & 0xffffu);  // y.d * fp16(x.d)
+        const float e = yd * h2f(dh >> 16);      // y.d * fp16(x.dmin)
+        if (TYPE == Q5_K) p->a = fmaf(c, (float)isum, -(e * (float)imin));  // d*sumi - dmin*sumi_mins
+        else *(float4 *)p = make_float4((float)isum, c, (float)imin, e);
+    }
+#else
+    Rec rec;
+    if (TYPE == Q6_K) {
+        rec.a = isum - 32 * imin;
+        rec.b = 0;
+        rec.c = h2f(dh) * yd;  // d_all * y.d
+        rec.e = 0.f;
+    } else {
+        rec.a = isum;
+        rec.b = imin;
+        rec.c = yd * h2f(dh & 0xffffu);  // y.d * fp16(x.d)
+        rec.e = yd * h2f(dh >> 16);      // y.d * fp16(x.dmin)
+    }
+    *p = rec;
+#endif
+}
+
+// One record into registers: one LDS read instruction.
+template <int TYPE>
+__device__ __forceinline__ RowRec row_rec_load(const RowRec *p) {
+#if KQ_ROWS_CHAIN_REC
+    RowRec r = {0.f, 0.f, 0.f, 0.f};
+    if (TYPE == Q5_K) {
+        r.a = p->a;
+    } else if (TYPE == Q6_K) {
+        const float2 v = *(const float2 *)p;
+        r.a = v.x, r.c = v.y;
+    } else {
+        const float4 v = *(const float4 *)p;
+        r.a = v.x, r.c = v.y, r.b = v.z, r.e = v.w;
+    }
+    return r;
+#else
+    return *p;
+#endif
+}
+
+// The reference's per-superblock fp32 update on such a record: with CHAIN_REC its dependent
+// operations and nothing else. The Q4_K negation is of the float (an operand modifier of the
+// FMA), never of the integer: INT_MIN and the sign of a zero product would differ.
+template <int TYPE>
+__device__ __forceinline__ float row_chain_step(const RowRec &r, float s) {
+#if KQ_ROWS_CHAIN_REC
+    if (TYPE == Q4_K) {
+        s = fmaf(-r.b, r.e, s);  // sumf -= dmin * summins   (fmsub, README.md:551)
+        s = fmaf(r.a, r.c, s);   // sumf += d * sumi         (fmadd, README.md:614)
+    } else if (TYPE == Q5_K) {
+        s = s + r.a;
+    } else {  // Q6_K: sum += d_all*y.d*(isum - 32*isum_mins)
+        s = fmaf(r.c, r.a, s);
+    }
+    return s;
+#else
+    return chain_step(TYPE, r, s);
+#endif
+}
+
+// Row r's chain, in lane r: records rc[0], rc[stride], .. rc[(nb - 1) * stride] in superblock
+// order from s = 0 (the three chain sites of kq_rows.hip). Four records are read at a time.
+// Holding a group of 4 or 8 records in registers behind one wait, the next group in flight under
+// its FMAs, measured slower on the token than this loop (profiles/r12_chain_ab.txt) and is not
+// in the source.
+template <int TYPE>
+__device__ __forceinline__ float rows_chain(const RowRec *rc, int nb, int stride) {
+    float s = 0.f;
+#pragma unroll 4
+    for (int i = 0; i < nb; ++i) s = row_chain_step<TYPE>(row_rec_load<TYPE>(rc + i * stride), s);
+    return s;
+}
+
 // ---------------------------------------------------------------- the row stream of one wave
 struct WaveWork {
     int m, r0, nrows;
