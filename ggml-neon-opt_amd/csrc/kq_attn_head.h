@@ -95,7 +95,7 @@ __device__ __forceinline__ float adiag_finite(uint32_t bits) { return __uint_as_
 // cell per thread (n_kv <= TPH), KQV runs HD * 4 / TPH (d, j) items per thread.
 // VPF0: V-cache iterations (32 cells each) prefetched with the position (0: 8 / ITEMS).
 // OUT_WT: out is global memory, stored write-through (sc1) for the next launch (kq_rows'
-// outputs likewise, KQ_ROWS_YSC1).
+// outputs likewise, store_y).
 // SC1_IN: q / k / v were written in this launch by other workgroups (the persistent layer,
 // kq_layer.hip): every load of them is an agent-scope (sc1) load, as the hand-off requires.
 // One LDS-DMA instruction (default cache policy: the V cache is re-read token after token)

@@ -90,14 +90,6 @@ constexpr int ROWS_WAVES = KQ_ROWS_WAVES;  // the most waves per workgroup (LDS 
 #endif
 constexpr int ROWS_WAVES_SMALL = KQ_ROWS_WAVES_SMALL;
 constexpr int ROWS_QPASS = 3;  // fused-quantization passes of 4*ROWS_WAVES superblocks
-// L2 prefetch issued with the first weight step (waves whose stream outlasts the
-// ring): while the activation is fetched and quantized, each wave touches the next
-// ROWS_PF x 4 KB of its stream past the ring (one dword per 64-B sector), so the HBM
-// keeps streaming and those steps later DMA from L2 / the Infinity Cache.
-#ifndef KQ_ROWS_PF
-#define KQ_ROWS_PF 2
-#endif
-constexpr int ROWS_PF = KQ_ROWS_PF;  // touches per wave when a.pf != 0
 
 // Kernel entry (kq_rows, kq_rows_dyn): what a wave needs before its first memory request comes
 // as leading plain parameters, 14 dwords, which the kernarg preload puts in SGPRs at wave start
@@ -107,7 +99,7 @@ constexpr int ROWS_PF = KQ_ROWS_PF;  // touches per wave when a.pf != 0
 // rbase / rrem. RowsArgs follows; the kernels read its first run (up to `stamps_cap`) in ONE
 // batch of scalar loads behind one wait (rows_resolve, kq_rows.hip) and pick per-matrix values
 // from the loaded arrays. The kernels read neither gridDim nor blockDim, and nothing of the
-// host's plan below that run except the experiment knobs of experiment builds.
+// host's plan below that run.
 #define KQ_ROWS_PARAMS                                                                                        \
     const void *x, const float *x2, const uint8_t *w0, const float *res0, int nb, int waves_total, int grid, \
         int cfg, int rbase0, int rrem0, const RowsArgs a
@@ -127,11 +119,8 @@ constexpr int ROWS_PRO_WIDE_STEPS = 2;  // wide forms up to this many steps per 
 struct RowsProForm {
     int lsh, passes;
 };
-#ifndef KQ_ROWS_PRO_WIDE
-#define KQ_ROWS_PRO_WIDE 1  // 0: 16 lanes per superblock for every row (experiment builds: the A/B baseline)
-#endif
 __host__ __device__ constexpr RowsProForm rows_pro_form(int nb, int nwv, int64_t steps = 0) {
-    const bool wide = KQ_ROWS_PRO_WIDE && steps <= ROWS_PRO_WIDE_STEPS;
+    const bool wide = steps <= ROWS_PRO_WIDE_STEPS;
     return wide && nb * 64 <= 64 * nwv   ? RowsProForm{2, 1}
            : wide && nb * 32 <= 64 * nwv ? RowsProForm{1, 1}
                                          : RowsProForm{0, (nb + 4 * nwv - 1) / (4 * nwv)};
@@ -180,21 +169,13 @@ struct RowsArgs {
     const float *x2;      // ROWS_PRO_NORM: norm weight (the MUL after RMS_NORM); ROWS_PRO_SWIGLU: up (x = gate)
     int pro;              // ROWS_PRO_*: transform of x before its Q8_K quantization
     int diag;         // diagnostics (timing only): bit3 stream weights only, 16/32 prologue, 64 no quantization, 128 no SWIGLU epilogue, 256 empty launch
-    // ---- experiment builds only (compile-time constants in the product)
-    int pre0;         // weight steps issued before the activation is quantized
-    int pf;           // L2 prefetch on/off (ROWS_PF 4-KB touches of the stream past the ring)
-    int xmode;        // fused-quantization prologue: ROWS_X_* bits
-    int64_t prio_bytes;  // the most weight bytes any wave streams (KQ_ROWS_PRIO: remaining-work priority)
+    // ---- recorded plan fields (mi355x_debug_rows_plan, tests/golden/rows_plans.json): no kernel
+    // reads them any more; the kernels issue one weight step before the activation wait and
+    // set no wave priority
+    int pre0;         // the GEMV_PRE0 knob: weight steps once issued before the activation was quantized
+    int64_t prio_bytes;  // the most weight bytes any wave streams
 };
 constexpr int ROWS_PRO_NONE = 0, ROWS_PRO_NORM = 1, ROWS_PRO_SWIGLU = 2;
-// Prologue of the fused quantization (a.xmode bits):
-//  ROWS_X_ROT   workgroup b visits the activation's superblocks from b mod nb on, so the
-//               256 workgroups do not all read the same L2 lines at the same moment;
-//  ROWS_X_BAR   a workgroup barrier between every wave's activation loads and the first
-//               weight DMA (the activation requests are queued ahead of the stream's);
-//  ROWS_X_PIPE  pass i is transformed and quantized as soon as ITS loads landed, while
-//               the later passes (and the weight steps) are still in flight.
-constexpr int ROWS_X_ROT = 1, ROWS_X_BAR = 2, ROWS_X_PIPE = 4;
 
 // One step = 16 consecutive superblocks of a wave's row stream (2304 / 2816 / 3360
 // B), fetched as 16-B granules from the 16-B boundary below them (+1 granule of

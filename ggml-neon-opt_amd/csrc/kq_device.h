@@ -287,7 +287,7 @@ __device__ __forceinline__ void dma16_nt(const void *src, LDS void *dst) {
 // is issued on every path (no compiler branch around a partial mask), so a counted wait
 // that covers it holds on every path the ISA lint walks (tools/vmem_lint.py). A
 // vector-memory instruction counts in vmcnt whatever its mask (kq_rows' prologue step,
-// KQ_ROWS_MASKED).
+// profiles/r03_masked_ab.txt).
 __device__ __forceinline__ void dma16_nt_lanes(const void *src, LDS void *dst, int lane, int n) {
     const uint32_t m0 = (uint32_t)(uintptr_t)dst;
     uint64_t save;

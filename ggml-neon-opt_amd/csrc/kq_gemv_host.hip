@@ -252,13 +252,12 @@ void rows_fill_args(const mi355x_gemv_desc *d, int n_desc, int64_t nb, RowsArgs 
         a.y[i] = d[i].y;
         a.n_rows[i] = (int)d[i].n_rows;
     }
-    a.pf = (int)knob(KNOB_GEMV_PF);
-    a.xmode = (int)knob(KNOB_GEMV_XMODE) & 7;
     a.diag = (int)knob(KNOB_GEMV_DIAG);
-    // weight steps issued before the activation is quantized. One: a deeper early burst
-    // delays the activation loads queued behind it. Alone, K = 2048 GEMVs ran 5-9 %
-    // faster with the whole ring (tools/gemv_sweep.py pre0=3), but with the fused norm
-    // prologue (two vectors to fetch) the decode token was 1.6 % slower.
+    // A recorded plan field that no kernel reads (RowsArgs): the kernels issue one weight step
+    // before the activation is quantized. A deeper early burst delays the activation loads
+    // queued behind it: alone, K = 2048 GEMVs ran 5-9 % faster with the whole ring, but with
+    // the fused norm prologue (two vectors to fetch) the decode token was 1.6 % slower
+    // (profiles/r01_wave_priority_and_pre0.txt).
     const int pre = (int)knob(KNOB_GEMV_PRE0);
     a.pre0 = pre < 0 ? 0 : pre > 3 ? 3 : pre;
     a.stamps = diag_stamps(&a.stamps_cap);

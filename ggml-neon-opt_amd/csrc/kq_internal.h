@@ -26,9 +26,7 @@ uint64_t *diag_stamps(int64_t *cap);  // mi355x_diag_stamps' buffer (diagnostic 
 enum Knob {
     KNOB_GEMV_DIAG,        // timing stops of the KQ_ROWS_DIAG / KQ_GEMV_DIAG builds
     KNOB_GEMV_RING,        // kq_gemv ring depth override (0: by LDS)
-    KNOB_GEMV_PRE0,        // kq_rows weight steps issued before the activation (1)
-    KNOB_GEMV_PF,          // kq_rows L2 prefetch of the stream (experiment builds)
-    KNOB_GEMV_XMODE,       // kq_rows prologue variants (experiment builds)
+    KNOB_GEMV_PRE0,        // recorded in the plan (RowsArgs::pre0); the kernels issue one step whatever it says
     KNOB_GEMV_SMALL_MB,    // launches below this many MB of weights: ROWS_WAVES_SMALL waves
     KNOB_GEMV_WPC,         // cap on active waves per CU (0: none)
     KNOB_GEMV_SMALL_WG,    // cap on workgroups of small launches (0: one per CU)

@@ -58,82 +58,29 @@ struct NormStamps {
     uint64_t pub = 0, bar = 0, scale = 0;
 };
 
-#ifndef KQ_ROWS_XMODE
-#define KQ_ROWS_XMODE 0  // fused-quantization prologue (ROWS_X_* bits); -1: a.xmode at run time
-#endif
-// Weight steps issued before the activation wait, and the L2 prefetch touches past the
-// ring: compile-time (-1: from RowsArgs at run time, the experiment knobs
-// MI355X_GEMV_PRE0 / MI355X_GEMV_PF). Constants make every s_waitcnt that covers an
-// inline-asm activation load a constant on each path, which tools/vmem_lint.py checks.
-#ifndef KQ_ROWS_PRE0
-#define KQ_ROWS_PRE0 1
-#endif
-#ifndef KQ_ROWS_L2PF
-#define KQ_ROWS_L2PF 0
-#endif
-// Prologue DMA and activation wait (profiles/r03_masked_ab.txt): 2 (product) issues the
-// step's partial last DMA instruction with its lane mask inside the asm, so it is issued on
-// every path, and the activation wait then leaves the residual load (younger than x, a
-// gather from memory the previous launches did not touch) in flight: TinyLlama token +4.8 %,
-// Llama-3-8B +3.1 %. 1: the masked DMA with the old wait; 0: both as before (experiments).
-#ifndef KQ_ROWS_MASKED
-#define KQ_ROWS_MASKED 2
-#endif
-// The norm prologue's steps, each a build constant of its own (A/B per step: make variant-rows,
-// profiles/r09_norm_ab.txt); 0 is the form before the step.
-//  NORM_SKIP   waves that hold no part of the row go from the norm's barrier straight to
-//              their ring fill (no total, guard, scale or transform);
-//  NORM_LATE   wide forms: scale from the fast total, transform into registers of their own,
-//              quantize and store, and only then the exactness guard; an ambiguous row is
-//              redone from the preserved x and its blocks overwritten;
-//  NORM_TREE   the row's total as a tree over the superblock sums (nb a power of two <= 64);
-#ifndef KQ_ROWS_NORM_SKIP
-#define KQ_ROWS_NORM_SKIP 1
-#endif
-#ifndef KQ_ROWS_NORM_LATE
-#define KQ_ROWS_NORM_LATE 1
-#endif
-#ifndef KQ_ROWS_NORM_TREE
-#define KQ_ROWS_NORM_TREE 1
-#endif
-// The short-stream form (template parameter SH, rows_short_form in kq_common.h: every wave's
-// stream fits its ring and one chain batch covers its rows), each step a build constant of its
-// own (A/B per step: make variant-rows, profiles/r10_short_ab.txt); 0 is the generic code.
-//  SHORT_UNROLL  at most D steps straight-line, the wait of each a constant (0: a loop with
-//                the wait picked by the steps still in flight);
-//  SHORT_LANE    lane r keeps row r's result: residual add and store from the register, LDS
-//                staging only for the SWIGLU epilogue's gate values.
-#ifndef KQ_ROWS_SHORT_UNROLL
-#define KQ_ROWS_SHORT_UNROLL 1
-#endif
-#ifndef KQ_ROWS_SHORT_LANE
-#define KQ_ROWS_SHORT_LANE 1
-#endif
+// The kernels' settled steps, each measured as a build switch of its own and then made the only
+// form (DESIGN.md §7 "Retired build switches" names the record of each):
+//  * the fused prologue issues exactly one weight step before the activation wait, its partial
+//    last DMA instruction masked inside the asm so that it is issued on every path; the one
+//    constant wait then leaves the residual load and that step in flight (tools/vmem_lint.py
+//    checks that every s_waitcnt covering an inline-asm activation load is a constant);
+//  * the norm prologue: waves that hold no part of the row go from the norm's barrier straight
+//    to their ring fill; the wide forms quantize from the fast total and run the exactness guard
+//    afterwards (norm_late); the row's total is a tree where nb is a power of two <= 64;
+//  * the short-stream form (template parameter SH, rows_short_form in kq_common.h): at most D
+//    steps straight-line, each wait a constant, and lane r keeps row r's result in a register.
 #ifndef KQ_ROWS_LINT_BREAK
 #define KQ_ROWS_LINT_BREAK 0  // 1: drop the activation wait (a lint self-test build, never run)
 #endif
 
-// The GEMV's outputs (and the SWIGLU epilogue's) are stored write-through (sc1), so the next
-// launch's activation is in the memory-side caches before the kernel boundary
-// (tools/xfresh.hip: the consumer's fresh-read price 0.15 -> 0.03 us per edge).
-// Issue priority by remaining work (MI355X_MICROARCH.md "Two waves per SIMD": VALU and memory
-// issue go by priority, then age, so with three waves per SIMD the older ones stream faster
-// and the middle one ends last, r05 stamps): every few steps a wave sets s_setprio from the
-// weight bytes it still has to stream, relative to the most any wave streams, so the waves
-// behind catch up.
-#ifndef KQ_ROWS_PRIO
-#define KQ_ROWS_PRIO 0
-#endif
-
-#ifndef KQ_ROWS_YSC1
-#define KQ_ROWS_YSC1 1  // TinyLlama token +0.5-1.4 %, Llama-3-8B +0.7 % (profiles/r04_store_flavour_ab.txt)
-#endif
-
 namespace kq {
 
+// The GEMV's outputs (and the SWIGLU epilogue's) are stored write-through (sc1), so the next
+// launch's activation is in the memory-side caches before the kernel boundary
+// (tools/xfresh.hip: the consumer's fresh-read price 0.15 -> 0.03 us per edge;
+// profiles/r04_store_flavour_ab.txt).
 __device__ __forceinline__ void store_y(float *p, float v) {
-    if (KQ_ROWS_YSC1) asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-    else *p = v;
+    asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 
 // Q8L quantization of whole rows (K > 8192 path): 16 superblocks per workgroup.
@@ -419,23 +366,19 @@ struct RowsPrologue {
     u32x4 xv[NP][NL];
     u32x4 x2v[NP][NL];  // norm weight / up, same elements as xv
     int qw = 0;  // passes this wave loads (wave-uniform): pass i while its first slot lies in the row
-    int nb, pass, rot, wave, lane;
+    int nb, pass, wave, lane;
 
     // slot of pass i held by this lane, its lane index within the superblock, slot -> superblock:
-    // rotated by the workgroup (ROWS_X_ROT) so the grid does not read the activation's lines in
-    // one order; slots past the row read superblock nb-1's place and store nothing
+    // slots past the row read superblock nb-1's place and store nothing
     __device__ __forceinline__ int slot(int i) const { return pass * i + SPW * wave + (lane >> (4 + LSH)); }
     __device__ __forceinline__ int sl() const { return lane & (LP - 1); }
-    __device__ __forceinline__ int sbk(int j) const {
-        const int b = (j < nb ? j : nb - 1) + rot;
-        return b >= nb ? b - nb : b;
-    }
+    __device__ __forceinline__ int sbk(int j) const { return j < nb ? j : nb - 1; }
 
     // ASM: the kernels' inline-asm loads, which the caller waits for; false (the debug kernel):
     // ordinary loads that the compiler waits for itself
     template <int PRO, bool ASM = true>
-    __device__ __forceinline__ void load(const RowsLead &ld, int wave_, int lane_, int rot_, int diag) {
-        nb = ld.nb, pass = SPW * ld.nwv, rot = rot_, wave = wave_, lane = lane_;
+    __device__ __forceinline__ void load(const RowsLead &ld, int wave_, int lane_, int diag) {
+        nb = ld.nb, pass = SPW * ld.nwv, wave = wave_, lane = lane_;
         const float *const x = (const float *)ld.x;
         // (diag bit 4: read x again instead of x2, timing only)
         const float *const x2 = (diag & 16) ? x : ld.x2;
@@ -504,11 +447,11 @@ struct RowsPrologue {
 
     // rms_norm then MUL by the norm weight: this wave's superblock sums of squares to `sums`
     // (LDS), a workgroup barrier, the row's total from them on every wave that holds a part of
-    // the row (NORM_SKIP: a wave without one goes on to its ring fill; it has joined the
+    // the row (a wave without one goes on to its ring fill; it has joined the
     // barrier, so every wave passes the same barriers). The fast order: the lane's 16 >> LSH
     // squares in order, the xor tree over the superblock's lanes (every aligned group of 16
     // elements is a subtree for every LSH), then the superblocks as a tree where nb is a power
-    // of two <= 64 (NORM_TREE: at most 16 + 6 + 6 adds per value), else in order. The rare rows
+    // of two <= 64 (at most 16 + 6 + 6 adds per value), else in order. The rare rows
     // whose float mean could depend on the order (rms_mean_ambiguous, whose bound holds for any
     // order of at most n + 32 adds per value) are summed again in ggml's order, by each wave:
     // the test is workgroup-uniform, every wave sums the same LDS values by the same instructions.
@@ -540,7 +483,7 @@ struct RowsPrologue {
         }
     }
     __device__ __forceinline__ double norm_total(const double *sums) const {
-        if (KQ_ROWS_NORM_TREE && nb <= 64 && (nb & (nb - 1)) == 0) return tree_sum_lanes(sums, nb, lane);
+        if (nb <= 64 && (nb & (nb - 1)) == 0) return tree_sum_lanes(sums, nb, lane);
         return seq_sum_lanes(sums, nb, lane);  // superblocks in order
     }
     static __device__ __forceinline__ float norm_scale(double tot, int64_t n, float eps) {
@@ -548,13 +491,13 @@ struct RowsPrologue {
         return 1.0f / sqrtf(mean + eps);
     }
 
-    // The 16-lane form, and every form without NORM_LATE: total, guard, scale, transform in place.
+    // The 16-lane form: total, guard, scale, transform in place.
     __device__ __forceinline__ void norm(double *sums, const float *x, float eps, NormStamps &ns) {
         norm_publish(sums);
         ns.pub = RSTAMP();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         ns.bar = RSTAMP();
-        if (KQ_ROWS_NORM_SKIP && qw == 0) return;
+        if (qw == 0) return;
         const int64_t n = (int64_t)nb * QK;
         double tot = norm_total(sums);
         if (rms_mean_ambiguous(div_by_count(tot, n), n)) tot = seq_sumsq_wave(x, n, lane);
@@ -580,7 +523,7 @@ struct RowsPrologue {
         quant_wide_store<LP>(v, sl(), act + Q8L_STRIDE * sbk(j), j < nb);
     }
 
-    // The wide forms (NORM_LATE): the guard after the quantized row is stored. Scale from the
+    // The wide forms: the guard after the quantized row is stored. Scale from the
     // fast total, transform into registers of their own (x stays), quantize and store; then the
     // guard, and on an ambiguous row the sum in ggml's order, the transform and the quantization
     // again from x, over this wave's own blocks (same lanes, same addresses, LDS in order). The
@@ -593,7 +536,7 @@ struct RowsPrologue {
         ns.pub = RSTAMP();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         ns.bar = RSTAMP();
-        if (KQ_ROWS_NORM_SKIP && qw == 0) {
+        if (qw == 0) {
             if (stamp) sx = __builtin_amdgcn_s_memrealtime();
             return;
         }
@@ -654,7 +597,7 @@ struct RowsPrologue {
             for (int i = 0; i < NP; ++i)
                 if (i < qw) swiglu_pass(i);
         } else if (PRO == ROWS_PRO_NORM) {
-            if constexpr (KQ_ROWS_NORM_LATE && LSH >= 1) {
+            if constexpr (LSH >= 1) {
                 norm_late(act, sums, x, eps, diag, stamp, sx, ns);
                 return;
             } else {
@@ -681,7 +624,7 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_prologue_dbg(const fl
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     RowsPrologue<LSH> pg;
-    pg.template load<PRO, false>(ld, wave, lane, 0, 0);
+    pg.template load<PRO, false>(ld, wave, lane, 0);
     uint64_t sx = 0;
     NormStamps ns;
     pg.template finish<PRO>(smem, (double *)(smem + nb * Q8L_STRIDE), x, eps, 0, false, sx, ns);
@@ -709,6 +652,53 @@ int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps
     return e == hipSuccess ? MI355X_OK : (int)e;
 }
 
+// The fused prologue of kq_rows and kq_rows_dyn is one sequence. After the activation loads
+// (pg.load) and the entry batch, each body issues the residual load and exactly one weight step's
+// DMA instructions on every path, the partial last one with its lane mask inside the asm, and
+// advances its own stream state; rows_fused_finish is the rest: the one constant wait, which
+// leaves that load and that step in flight (tools/vmem_lint.py checks that every s_waitcnt
+// covering an inline-asm activation load is a constant), then transform and quantization into
+// the Q8L row at `act`. The residual load (this lane's residual of the fused ADD) is issued on
+// every path, a dummy read of x without a residual, so that no branch joins a register whose asm
+// load is still in flight; the body keeps `rv` live until its flush waits for it. An asm load
+// whose register the compiler sees dead is reused while the load is in flight: a build with that
+// branch compiled out faulted (profiles/r02_attn_epilogue_rejected.md).
+// `ps`: the diagnostic builds' stamps (x landed, transformed, quantized, the norm interval's).
+struct ProStamps {
+    uint64_t landed = 0, transformed = 0, quantized = 0;
+    NormStamps ns;
+};
+template <int TYPE, int PRO, int LSH>
+__device__ __forceinline__ void rows_fused_finish(RowsPrologue<LSH> &pg, const float *x, uint8_t *act, double *sums,
+                                                  float eps, int diag, bool stamps, ProStamps &ps) {
+    // x landed: the residual load (younger than x) and the step's DMA instructions (all issued
+    // on every path) may still be in flight
+    if (!KQ_ROWS_LINT_BREAK) vm_wait<rows_ni(TYPE) + 1>();  // (1: tests/test_abi.py, the ISA lint must flag the build)
+    ps.landed = RSTAMP();
+    pg.template finish<PRO>(act, sums, x, eps, diag, stamps, ps.transformed, ps.ns);
+    if (stamps) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        ps.quantized = __builtin_amdgcn_s_memrealtime();
+    }
+}
+
+// The SWIGLU epilogue's value for row r, n4 = n & ~3 rows in the vector body: the arithmetic of
+// kq_swiglu (ggml_vec_swiglu_f32: NEON body, libm tail).
+__device__ __forceinline__ float rows_swiglu_out(float gv, float uv, int r, int n4) {
+    return r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv;
+}
+
+// A wave's stamps (diagnostic builds; the slots' meanings above and in tools/stamps.py). Slot 3,
+// the exit, is taken here.
+__device__ __forceinline__ void rows_put_stamps(uint64_t *stamps, int64_t cap, int wave, int lane,
+                                                const uint64_t (&v)[ROWS_STAMP_SLOTS]) {
+    const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;  // sized for the most waves
+    if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < cap) {
+#pragma unroll
+        for (int k = 0; k < ROWS_STAMP_SLOTS; ++k) stamps[o + k] = k == 3 ? __builtin_amdgcn_s_memrealtime() : v[k];
+    }
+}
+
 // `resolve` returns the wave's RowsHot: called after the activation loads are issued (they
 // need the leading parameters only), or before the call where the type depends on the matrix.
 //
@@ -717,12 +707,12 @@ int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps
 // and nothing is issued after it, and its rows are one chain batch. The steps run without ring
 // wrap, batch bookkeeping or issue; integer sums, records and the chain are the generic form's.
 template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH, bool SH, class Resolve>
-__device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
+__device__ __forceinline__ void rows_body(const RowsLead &ld, uint8_t *smem, int wave, int lane,
                                           uint64_t st0, Resolve resolve) {
     static_assert(!SH || FUSEDQ, "the short form is built for the fused-quantization launches");
     constexpr int BSZ = block_bytes(TYPE);
-    constexpr int GRAN = rows_gran(TYPE);
     constexpr int NI = rows_ni(TYPE);
+    constexpr int PART = rows_gran(TYPE) - 64 * (NI - 1);  // lanes of a step's partial last DMA instruction
     constexpr int SLOT = rows_slot(TYPE);
     constexpr int D = rows_depth(TYPE);
     static_assert(D >= 2 && D <= 4, "vm_wait_k covers 3 steps in flight");
@@ -731,10 +721,8 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const int q = lane >> 2, s = lane & 3;
 
     // ---- activation loads first: every wave's requests leave before any argument fetch
-    // KQ_ROWS_XMODE >= 0: the prologue fixed at compile time (experiment builds)
-    const int xm = !FUSEDQ ? 0 : KQ_ROWS_XMODE >= 0 ? KQ_ROWS_XMODE : a.xmode;
     RowsPrologue<LSH> pg;
-    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, (xm & ROWS_X_ROT) ? (int)(blockIdx.x % (unsigned)nb) : 0, RDIAG(ld));
+    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, RDIAG(ld));
     const RowsHot h = resolve();
     const uint64_t sa = RSTAMP();  // diagnostics: arguments fetched
     const int bR = h.bR;
@@ -776,25 +764,10 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(RowRec);
     }
 
-    // L2 prefetch (uniform per wave): only streams longer than the ring, fused path
-    const bool pf_on = FUSEDQ && (KQ_ROWS_L2PF < 0 ? a.pf != 0 : KQ_ROWS_L2PF != 0) && T > D + 1;
-    uint32_t pf_sink = 0;
     uint8_t *islot = ring;
     int it_ = 0;  // next step to issue
     auto issue = [&]() {
-        const uint8_t *base = s16 + (int64_t)it_ * (ROWS_SB * BSZ) + 16 * lane;
-        if (it_ + 1 < T) {  // interior step: every granule inside the stream
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-                if (i + 1 < NI || lane < GRAN - 64 * (NI - 1)) dma16_nt(base + 1024 * i, (LDS void *)(islot + 1024 * i));
-        } else {            // last step: clamp to the stream's last granule
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const uint8_t *p = base + 1024 * i;
-                if (i + 1 < NI || lane < GRAN - 64 * (NI - 1))
-                    dma16_nt(p < last16 ? p : last16, (LDS void *)(islot + 1024 * i));
-            }
-        }
+        rows_issue_step<TYPE>(s16 + (int64_t)it_ * (ROWS_SB * BSZ) + 16 * lane, last16, islot, lane, it_ + 1 < T);
         islot = islot + SLOT == ring_end ? ring : islot + SLOT;
         ++it_;
     };
@@ -802,40 +775,23 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     const float *const res_p = h.res;
     uint32_t rv = 0;  // residual of the fused ADD for row r0 + lane (first 64 rows)
 
-    // ---- prologue: activation loads, pre0 weight steps, quantize, then the rest of the ring
-    const int pre_req = KQ_ROWS_PRE0 < 0 ? a.pre0 : KQ_ROWS_PRE0;
-    const int pre_cap = pre_req < D ? pre_req : D;  // never more than the ring holds
-    // min(T, pre_cap) written so that the compiler sees 0 <= pre0 <= pre_cap (T >= 0)
-    const int pre0 = T >= pre_cap ? pre_cap : (T > 0 ? T : 0);
-    uint64_t sx = 0, sq = 0, sf = 0, sl = 0;  // diagnostics: transformed, quantized, first step computed, x landed
-    NormStamps ns;
+    // ---- prologue: activation loads, one weight step, quantize, then the rest of the ring
+    uint64_t sf = 0;  // diagnostics: first step computed
+    ProStamps ps;
     if (FUSEDQ) {
+        // residual of the fused ADD: one row per lane, fetched with the activation
         const float *const x = (const float *)ld.x;
-        constexpr int pro = PRO;
-        constexpr int PL = (PRO != ROWS_PRO_NONE ? 2 : 1) * RowsPrologue<LSH>::NL;  // loads per pass
-        // residual of the fused ADD: one row per lane, fetched with the activation. Issued
-        // on every path (a dummy read of x without a residual) so that no branch joins a
-        // register whose asm load is still in flight; rv stays live until the flush waits
-        // for it (the res_p branch is a run-time condition). An asm load whose register the
-        // compiler sees dead is reused while the load is in flight: a build with that branch
-        // compiled out faulted (profiles/r02_attn_epilogue_rejected.md).
         rv = gload4_asm(res_p && h.nrows > 0 ? res_p + h.r0 + (lane < h.nrows ? lane : 0) : x);
-        // ROWS_X_BAR: every wave's activation requests are queued before any weight DMA of
-        // the workgroup (uniform: every wave of the workgroup runs the prologue)
-        if (xm & ROWS_X_BAR) asm volatile("s_barrier" ::: "memory");
-        // The product build (one step ahead, no prefetch touches) issues exactly one step's
-        // DMA instructions on every path: a wave without rows (T == 0) issues them from the
-        // activation (valid memory, into a ring slot it never reads), so the one constant
-        // wait below covers the activation loads on every path (tools/vmem_lint.py).
-        constexpr bool kConstPre = KQ_ROWS_PRE0 == 1 && KQ_ROWS_L2PF == 0;
-        if (kConstPre && T == 0) {
+        // Exactly one step's DMA instructions on every path: a wave without rows (T == 0) issues
+        // them from the activation (valid memory, into a ring slot it never reads)
+        if (T == 0) {
             const uint8_t *xb = (const uint8_t *)x + 16 * lane;
 #pragma unroll
             for (int i = 0; i < NI; ++i)
-                if (KQ_ROWS_MASKED && i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, GRAN - 64 * (NI - 1));
-                else if (i + 1 < NI || lane < GRAN - 64 * (NI - 1)) dma16_nt(xb, (LDS void *)(islot + 1024 * i));
+                if (i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, PART);
+                else dma16_nt(xb, (LDS void *)(islot + 1024 * i));
         }
-        if (KQ_ROWS_MASKED && kConstPre && T > 0) {  // the one step, its partial DMA masked in asm
+        if (T > 0) {  // the one step, its partial DMA masked in asm
             const uint8_t *base = s16 + 16 * lane;
             const uint8_t *lim = T > 1 ? base + 1024 * (NI - 1) : base + 1024 * (NI - 1) < last16 ? base + 1024 * (NI - 1) : last16;
 #pragma unroll
@@ -843,74 +799,28 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 const uint8_t *p = base + 1024 * i;
                 dma16_nt(T > 1 || p < last16 ? p : last16, (LDS void *)(islot + 1024 * i));
             }
-            dma16_nt_lanes(lim, (LDS void *)(islot + 1024 * (NI - 1)), lane, GRAN - 64 * (NI - 1));
+            dma16_nt_lanes(lim, (LDS void *)(islot + 1024 * (NI - 1)), lane, PART);
             islot = islot + SLOT == ring_end ? ring : islot + SLOT;
             ++it_;
-        } else {
-            for (int j = 0; j < pre0; ++j) issue();
         }
-        if (pf_on) {  // L2 prefetch of the stream just past the ring (younger than the pre0 steps)
-            const uint8_t *p = s16 + (int64_t)D * (ROWS_SB * BSZ) + 64 * lane;
-#pragma unroll
-            for (int i = 0; i < ROWS_PF; ++i) l2_touch(p + 4096 * i < last16 ? p + 4096 * i : last16, pf_sink);
-        }
-        // vector-memory operations younger than the last pass's activation loads
-        const int tail = 1 + NI * pre0 + (pf_on ? ROWS_PF : 0);
-        if (pro != ROWS_PRO_NORM && (xm & ROWS_X_PIPE)) {
-            // pass by pass: pass i's transform + quantization overlap the later passes' loads
-#pragma unroll
-            for (int i = 0; i < RowsPrologue<LSH>::NP; ++i) {
-                if (i < pg.qw) {
-                    vm_wait_dyn((pg.qw - 1 - i) * PL + tail);
-                    pg.template pin<PRO>();
-                    if (pro == ROWS_PRO_SWIGLU && !(RDIAG(ld) & 32)) pg.swiglu_pass(i);
-                    if (!(RDIAG(ld) & 64)) pg.quantize_pass(i, smem + L.act);
-                }
-            }
-            if (RSTAMPS(h)) sl = sx = sq = __builtin_amdgcn_s_memrealtime();
-        } else {
-            // every pass landed: all but the pre0 weight steps (and prefetch touches); with
-            // compile-time pre0 / prefetch a constant per path
-            if (KQ_ROWS_LINT_BREAK) {
-                // deliberately broken build (tests/test_abi.py: the ISA lint must flag it): no wait
-            } else if (kConstPre && KQ_ROWS_MASKED == 2) {
-                // x landed: the residual load (rv, younger than x) and the step's NI DMA
-                // instructions (all issued on every path) may still be in flight
-                vm_wait<NI + 1>();
-            } else if (kConstPre) {
-                vm_wait<NI>();  // all but the one step's DMA instructions (fewer if predicated off: a stronger wait)
-            } else {
-                vm_wait_dyn(tail);
-            }
-            sl = RSTAMP();
-            pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, RDIAG(ld), RSTAMPS(h) != nullptr, sx, ns);
-            if (RSTAMPS(h)) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                sq = __builtin_amdgcn_s_memrealtime();
-            }
-        }
+        rows_fused_finish<TYPE, PRO>(pg, x, smem + L.act, (double *)(smem + L.sums), h.eps, RDIAG(ld), RSTAMPS(h) != nullptr, ps);
     } else {
         const int ng = nb * (Q8L_STRIDE / 16);
         for (int j = wave; 64 * j < ng; j += nwv) {
             const int k = 64 * j + lane;
             if (k < ng) dma16((const uint8_t *)ld.x + 16 * k, (LDS void *)(smem + L.act + 1024 * j));
         }
+        // one weight step in front of the wait for the row: min(T, 1), written so that the
+        // compiler sees 0 <= pre0 <= 1 (T >= 0)
+        const int pre0 = T >= 1 ? 1 : (T > 0 ? T : 0);
         for (int j = 0; j < pre0; ++j) issue();
         vm_wait_k<NI>(pre0);
     }
-    if constexpr (SH && KQ_ROWS_PRE0 == 1 && KQ_ROWS_L2PF == 0) {
+    if constexpr (SH) {
         // the rest of the stream (T <= D): step j into slot j, every granule clamped to the last
 #pragma unroll
         for (int j = 1; j < D; ++j)
-            if (j < T) {
-                const uint8_t *base = s16 + j * (ROWS_SB * BSZ) + 16 * lane;
-#pragma unroll
-                for (int i = 0; i < NI; ++i) {
-                    const uint8_t *p = base + 1024 * i;
-                    if (i + 1 < NI || lane < GRAN - 64 * (NI - 1))
-                        dma16_nt(p < last16 ? p : last16, (LDS void *)(ring + j * SLOT + 1024 * i));
-                }
-            }
+            if (j < T) rows_issue_step<TYPE>(s16 + j * (ROWS_SB * BSZ) + 16 * lane, last16, ring + j * SLOT, lane, false);
     } else {
         while (it_ < D && it_ < T) issue();
     }
@@ -919,25 +829,9 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     uint64_t st2 = 0, sw = 0, sc = 0, ss = 0;  // diagnostics: loop end, first wait passed, chain start, stores issued
     auto put_stamps = [&]() {
         if (RSTAMPS(h)) {
-            const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;  // sized for the most waves
-            if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
-                RSTAMPS(h)[o] = st0;
-                RSTAMPS(h)[o + 1] = st1;
-                RSTAMPS(h)[o + 2] = st2;
-                RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
-                RSTAMPS(h)[o + 4] = sx;
-                RSTAMPS(h)[o + 5] = sq;
-                RSTAMPS(h)[o + 6] = sf;
-                RSTAMPS(h)[o + 7] = sa;
-                RSTAMPS(h)[o + 8] = sl;
-                RSTAMPS(h)[o + 9] = ns.pub;
-                RSTAMPS(h)[o + 10] = ns.bar;
-                RSTAMPS(h)[o + 11] = ns.scale;
-                RSTAMPS(h)[o + 12] = (uint64_t)pg.qw;  // passes of x this wave holds
-                RSTAMPS(h)[o + 13] = sw;
-                RSTAMPS(h)[o + 14] = sc;
-                RSTAMPS(h)[o + 15] = ss;
-            }
+            const uint64_t v[ROWS_STAMP_SLOTS] = {st0, st1, st2, 0, ps.transformed, ps.quantized, sf, sa, ps.landed,
+                                                  ps.ns.pub, ps.ns.bar, ps.ns.scale, (uint64_t)pg.qw, sw, sc, ss};
+            rows_put_stamps(RSTAMPS(h), h.stamps_cap, wave, lane, v);
         }
     };
 
@@ -946,17 +840,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
         // (step T - 1 - k), so each copy's wait is a constant and a wave with fewer steps enters
         // at a later copy. The state (e_*) advances by one step of 16 superblocks.
         auto step = [&](bool advance) {
-            if (!(RDIAG(ld) & 8) && e_g < G) {
-                const uint8_t *blk = smem + e_blk;
-                const uint8_t *ab = smem + e_act;
-                QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
-                const int isum = quad_sum(r.isum);
-                const int imin = quad_sum(r.imin);
-                if (s == 0) {
-                    const float yd = *(const float *)ab;
-                    row_rec_store<TYPE>((RowRec *)(smem + e_rec), isum, imin, r.dh, yd);
-                }
-            }
+            if (!(RDIAG(ld) & 8) && e_g < G) rows_quad_step<TYPE>(smem + e_blk, smem + e_act, s, (RowRec *)(smem + e_rec));
             if (advance) {
                 e_g += ROWS_SB, e_blk += SLOT;
                 e_io += e_b16, e_rr += e_a16;
@@ -965,29 +849,19 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 e_rec = L.recs + wave * L.recs_stride + (__mul24(e_io, bR) + e_rr) * (int)sizeof(RowRec);
             }
         };
-        if constexpr (KQ_ROWS_SHORT_UNROLL != 0) {
-            auto copy = [&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                if (T > k) {  // uniform
-                    vm_wait<NI * k>();
-                    if (RSTAMPS(h) && T == k + 1) sw = __builtin_amdgcn_s_memrealtime();
-                    step(k > 0);
-                    if (RSTAMPS(h) && T == k + 1) sf = __builtin_amdgcn_s_memrealtime();
-                }
-            };
-            if constexpr (D > 3) copy(std::integral_constant<int, 3>{});
-            if constexpr (D > 2) copy(std::integral_constant<int, 2>{});
-            copy(std::integral_constant<int, 1>{});
-            copy(std::integral_constant<int, 0>{});
-        } else {
-#pragma unroll 1
-            for (int k = T - 1; k >= 0; --k) {
-                vm_wait_k<NI>(k);
+        auto copy = [&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if (T > k) {  // uniform
+                vm_wait<NI * k>();
                 if (RSTAMPS(h) && T == k + 1) sw = __builtin_amdgcn_s_memrealtime();
-                step(true);
+                step(k > 0);
                 if (RSTAMPS(h) && T == k + 1) sf = __builtin_amdgcn_s_memrealtime();
             }
-        }
+        };
+        if constexpr (D > 3) copy(std::integral_constant<int, 3>{});
+        if constexpr (D > 2) copy(std::integral_constant<int, 2>{});
+        copy(std::integral_constant<int, 1>{});
+        copy(std::integral_constant<int, 0>{});
         // ---- the one chain batch: lane r replays row r's records in superblock order and keeps
         // the result; the residual add and the store come from the register
         float v = 0.f;
@@ -1000,12 +874,6 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             }
             if (KQ_ROWS_DIAG) asm volatile("" : "+v"(v));  // (the stamp behind the value)
             st2 = RSTAMP();
-            if constexpr (KQ_ROWS_SHORT_LANE == 0) {  // the generic form's round trip through LDS
-                if (lane < h.nrows) outs_s[lane] = v;
-                wave_lds_fence();
-                wave_lds_fence();
-                if (lane < h.nrows) v = outs_s[lane];
-            }
             float *y = h.y + h.r0;
             if (res_p) {  // ggml_add(mul_mat, residual): the same single f32 add per element
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1025,7 +893,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 const int n4 = h.epi_n & ~3;
                 const int r = h.r0 + lane;
                 const float gv = gouts[lane], uv = v;
-                store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+                store_y(h.epi_y + r, rows_swiglu_out(gv, uv, r, n4));
             }
         }
         put_stamps();
@@ -1041,41 +909,13 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
     int bend = bR * nb < G ? bR * nb : G;  // superblock index ending the current batch
     int brow = 0;
     const uint8_t *cslot = ring;
-    int prio = -1;
 #pragma unroll 1
     for (int t = 0; t < T; ++t) {
-        if (KQ_ROWS_PRIO && (t & 3) == 0) {
-            const int64_t rem = (int64_t)(T - t) * (ROWS_SB * BSZ);
-            int p = (int)(rem * 4 / (a.prio_bytes + 1));
-            p = __builtin_amdgcn_readfirstlane(p > 3 ? 3 : p);
-            if (p != prio) {
-                prio = p;
-                if (p == 3) __builtin_amdgcn_s_setprio(3);
-                else if (p == 2) __builtin_amdgcn_s_setprio(2);
-                else if (p == 1) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        if (pf_on && t < pre0) {  // the prefetch touches sit between steps pre0-1 and pre0
-            if (T - t >= D) vm_wait<NI * (D - 1) + ROWS_PF>();
-            else vm_wait_kp<NI, ROWS_PF>(T - t - 1);
-        } else if (T - t >= D) {
-            vm_wait<NI * (D - 1)>();  // steady state: D-1 younger steps in flight
-        } else {
-            vm_wait_k<NI>(T - t - 1);
-        }
+        if (T - t >= D) vm_wait<NI * (D - 1)>();  // steady state: D-1 younger steps in flight
+        else vm_wait_k<NI>(T - t - 1);
         if (RSTAMPS(h) && t == 0) sw = __builtin_amdgcn_s_memrealtime();
-        if (!(RDIAG(ld) & 8) && ROWS_SB * t + q < G) {
-            const uint8_t *blk = cslot + mis + q * BSZ;
-            const uint8_t *ab = actq + io * Q8L_STRIDE;
-            QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
-            const int isum = quad_sum(r.isum);
-            const int imin = quad_sum(r.imin);
-            if (s == 0) {
-                const float yd = *(const float *)ab;
-                row_rec_store<TYPE>(recs + io * bR + rr, isum, imin, r.dh, yd);
-            }
-        }
+        if (!(RDIAG(ld) & 8) && ROWS_SB * t + q < G)
+            rows_quad_step<TYPE>(cslot + mis + q * BSZ, actq + io * Q8L_STRIDE, s, recs + io * bR + rr);
         cslot = cslot + SLOT == ring_end ? ring : cslot + SLOT;
         io += ROWS_SB;
         if (nb >= ROWS_SB) {
@@ -1104,11 +944,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
             wave_lds_fence();
         }
     }
-    if (KQ_ROWS_PRIO) __builtin_amdgcn_s_setprio(0);
     st2 = RSTAMPS(h) ? __builtin_amdgcn_s_memrealtime() : 0;
-    if (pf_on) {  // every touch has landed (they are older than step pre0): release the register
-        asm volatile("" ::"v"(pf_sink));
-    }
 
     // ---- flush staged results (coalesced)
     if (h.nrows > 0) {
@@ -1138,7 +974,7 @@ __device__ __forceinline__ void rows_body(const RowsArgs &a, const RowsLead &ld,
                 if (k + lane < h.nrows) {
                     const int r = h.r0 + k + lane;
                     const float gv = gouts[k + lane], uv = outs[k + lane];
-                    store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+                    store_y(h.epi_y + r, rows_swiglu_out(gv, uv, r, n4));
                 }
         }
     }
@@ -1158,17 +994,17 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows(KQ_ROWS_PARAMS) {
     auto resolve = [&]() { return rows_resolve<TMASK>(ld, gw); };
 
     if (TMASK == 1) {
-        rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 2) {
-        rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolve);
     } else if (TMASK == 4) {
-        rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolve);
+        rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolve);
     } else {  // the type is the matrix's: the entry batch first
         const RowsHot h = resolve();
         auto resolved = [&]() { return h; };
-        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
-        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
-        else rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(a, ld, smem, wave, lane, st0, resolved);
+        if (h.type == Q6_K) rows_body<Q6_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolved);
+        else if (h.type == Q5_K) rows_body<Q5_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolved);
+        else rows_body<Q4_K, FUSEDQ, PRO, TMASK, LSH, SH>(ld, smem, wave, lane, st0, resolved);
     }
 }
 
@@ -1196,9 +1032,6 @@ KQ_ROWS_INST_T(7)
 // one lane (bit-identical to the static split and to ggml_vec_dot_q4_K_q8_K row by row,
 // README.md:137). Results go to the workgroup's LDS rows and are stored coalesced, with the
 // residual ADD and the SWIGLU epilogue, after one workgroup barrier.
-#ifndef KQ_ROWS_DYN_RR
-#define KQ_ROWS_DYN_RR 0
-#endif
 namespace {
 static_assert(MI355X_MAX_FUSED == 4, "four matrices at most");
 struct DynUnit {
@@ -1245,12 +1078,12 @@ __device__ __forceinline__ RowsDynHot rows_dyn_resolve() {
 }
 
 template <int TYPE, bool FUSEDQ, int PRO, int TMASK, int LSH>
-__device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead &ld, uint8_t *smem, int wave, int lane,
+__device__ __forceinline__ void rows_dyn_body(const RowsLead &ld, uint8_t *smem, int wave, int lane,
                                               uint64_t st0) {
-    uint64_t sx = 0, sq = 0, sf = 0;  // diagnostics (KQ_ROWS_DIAG builds): x landed, quantized, first step
+    uint64_t sf = 0;  // diagnostics (KQ_ROWS_DIAG builds): first step
     constexpr int BSZ = block_bytes(TYPE);
-    constexpr int GRAN = rows_gran(TYPE);
     constexpr int NI = rows_ni(TYPE);
+    constexpr int PART = rows_gran(TYPE) - 64 * (NI - 1);  // lanes of a step's partial last DMA instruction
     constexpr int SLOT = rows_slot(TYPE);
     constexpr int D = rows_depth(TYPE);
     static_assert(D >= 2 && D <= 4, "vm_wait_k covers 3 steps in flight");
@@ -1262,7 +1095,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
     // ---- activation loads first (the leading parameters only), then the entry batch
     const float *const x = (const float *)ld.x;
     RowsPrologue<LSH> pg;
-    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, 0, 0);
+    if (FUSEDQ) pg.template load<PRO>(ld, wave, lane, 0);
     const RowsDynHot h = rows_dyn_resolve();
     // (scalars of their own: a pick among struct members becomes a pick of addresses, in scratch)
     const uint8_t *const w0 = ld.w0, *const w1 = h.w1, *const w2 = h.w2, *const w3 = h.w3;
@@ -1337,30 +1170,14 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
             return;
         }
         iwait = false;
-#if KQ_ROWS_DYN_RR  // experiment builds: the same units dealt round-robin, no claim (cost isolation)
-        const int uu = nwv * P + (k - P) * nwv + wave;
-#else
         uint32_t u = 0;
         if (lane == 0) u = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const int uu = __builtin_amdgcn_readfirstlane((int)u);
-#endif
         if (uu < units) take(uu);
         else idone = true;
     };
     auto issue = [&](bool claim_ok) {  // one step (NI DMA instructions), then the next unit if this one is done
-        const uint8_t *base = is16 + (int64_t)is * (ROWS_SB * BSZ) + 16 * lane;
-        if (is + 1 < iT) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-                if (i + 1 < NI || lane < GRAN - 64 * (NI - 1)) dma16_nt(base + 1024 * i, (LDS void *)(islot + 1024 * i));
-        } else {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const uint8_t *p = base + 1024 * i;
-                if (i + 1 < NI || lane < GRAN - 64 * (NI - 1))
-                    dma16_nt(p < il16 ? p : il16, (LDS void *)(islot + 1024 * i));
-            }
-        }
+        rows_issue_step<TYPE>(is16 + (int64_t)is * (ROWS_SB * BSZ) + 16 * lane, il16, islot, lane, is + 1 < iT);
         islot = islot + SLOT == ring_end ? ring : islot + SLOT;
         ++is;
         ++issued;
@@ -1376,15 +1193,16 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
     const int frow = row_of(f0 - fm * nr);
     uint32_t rv = 0;
 
-    // ---- prologue (the product kq_rows prologue: one step before the activation wait)
+    // ---- prologue: the first unit's first step (a wave without a unit: no step of the stream)
+    ProStamps ps;
     if (FUSEDQ) {
         rv = gload4_asm(fres && f0 < nflat && frow < N ? fres + frow : x);
-        // exactly one step's NI DMA instructions on every path (the constant wait below)
+        // exactly one step's NI DMA instructions on every path, as in rows_body
         if (ki < 0) {  // no unit: from the activation, into a slot never read
             const uint8_t *xb = (const uint8_t *)x + 16 * lane;
 #pragma unroll
             for (int i = 0; i < NI; ++i)
-                if (i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, GRAN - 64 * (NI - 1));
+                if (i + 1 == NI) dma16_nt_lanes(xb, (LDS void *)(islot + 1024 * i), lane, PART);
                 else dma16_nt(xb, (LDS void *)(islot + 1024 * i));
         } else {  // the first unit's first step, its partial DMA masked in asm
             const uint8_t *base = is16 + 16 * lane;
@@ -1394,21 +1212,13 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
                 const uint8_t *p = base + 1024 * i;
                 dma16_nt(iT > 1 || p < il16 ? p : il16, (LDS void *)(islot + 1024 * i));
             }
-            dma16_nt_lanes(lim, (LDS void *)(islot + 1024 * (NI - 1)), lane, GRAN - 64 * (NI - 1));
+            dma16_nt_lanes(lim, (LDS void *)(islot + 1024 * (NI - 1)), lane, PART);
             islot = islot + SLOT == ring_end ? ring : islot + SLOT;
             ++is;
             ++issued;
             if (is == iT) next_unit(false);
         }
-        vm_wait<NI + 1>();  // x landed; the residual load and the step's DMAs may be in flight
-        if (RSTAMPS(h)) sx = __builtin_amdgcn_s_memrealtime();
-        uint64_t sxt = 0;  // (kq_rows' stamp between transform and quantization: not taken here)
-        NormStamps ns;
-        pg.template finish<PRO>(smem + L.act, (double *)(smem + L.sums), x, h.eps, 0, false, sxt, ns);
-        if (RSTAMPS(h)) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            sq = __builtin_amdgcn_s_memrealtime();
-        }
+        rows_fused_finish<TYPE, PRO>(pg, x, smem + L.act, (double *)(smem + L.sums), h.eps, 0, RSTAMPS(h) != nullptr, ps);
     } else {
         const int ng = nb * (Q8L_STRIDE / 16);
         for (int j = wave; 64 * j < ng; j += nwv) {
@@ -1460,17 +1270,7 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
 #pragma unroll 1
     while (consumed < issued) {
         vm_wait_k<NI>(issued - consumed - 1);
-        if (ROWS_SB * cs + q < cG) {
-            const uint8_t *blk = cslot + cmis + q * BSZ;
-            const uint8_t *ab = actq + io * Q8L_STRIDE;
-            QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
-            const int isum = quad_sum(r.isum);
-            const int imin = quad_sum(r.imin);
-            if (s == 0) {
-                const float yd = *(const float *)ab;
-                row_rec_store<TYPE>(recs + io * bR + rr, isum, imin, r.dh, yd);
-            }
-        }
+        if (ROWS_SB * cs + q < cG) rows_quad_step<TYPE>(cslot + cmis + q * BSZ, actq + io * Q8L_STRIDE, s, recs + io * bR + rr);
         cslot = cslot + SLOT == ring_end ? ring : cslot + SLOT;
         ++consumed;
         ++cs;
@@ -1511,21 +1311,12 @@ __device__ __forceinline__ void rows_dyn_body(const RowsArgs &a, const RowsLead 
             const int r = row_of(f);
             if (r >= N) continue;
             const float gv = outs[f], uv = outs[nr + f];
-            store_y(h.epi_y + r, r < n4 ? v_silu(gv) * uv : (gv / (1.0f + expf(-gv))) * uv);
+            store_y(h.epi_y + r, rows_swiglu_out(gv, uv, r, n4));
         }
     }
-    if (RSTAMPS(h)) {  // the kq_rows stamp layout (tools/stamps.py); slot 7: units this wave took
-        const int64_t o = ((int64_t)blockIdx.x * ROWS_WAVES + wave) * ROWS_STAMP_SLOTS;
-        if (lane == 0 && o + ROWS_STAMP_SLOTS - 1 < h.stamps_cap) {
-            RSTAMPS(h)[o] = st0;
-            RSTAMPS(h)[o + 1] = st1;
-            RSTAMPS(h)[o + 2] = st2;
-            RSTAMPS(h)[o + 3] = __builtin_amdgcn_s_memrealtime();
-            RSTAMPS(h)[o + 4] = sx;
-            RSTAMPS(h)[o + 5] = sq;
-            RSTAMPS(h)[o + 6] = sf;
-            RSTAMPS(h)[o + 7] = (uint64_t)(ki + 1);
-        }
+    if (RSTAMPS(h)) {  // the kq_rows stamp layout (tools/stamps.py); slot 4: x landed, slot 7: units this wave took
+        const uint64_t v[ROWS_STAMP_SLOTS] = {st0, st1, st2, 0, ps.landed, ps.quantized, sf, (uint64_t)(ki + 1)};
+        rows_put_stamps(RSTAMPS(h), h.stamps_cap, wave, lane, v);
     }
 }
 template <int TMASK, bool FUSEDQ, int PRO, int LSH>
@@ -1536,7 +1327,7 @@ __global__ void __launch_bounds__(ROWS_WAVES * 64) kq_rows_dyn(KQ_ROWS_PARAMS) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int TYPE = TMASK == 1 ? Q4_K : TMASK == 2 ? Q5_K : Q6_K;
-    rows_dyn_body<TYPE, FUSEDQ, PRO, TMASK, LSH>(a, ld, smem, wave, lane, st0);
+    rows_dyn_body<TYPE, FUSEDQ, PRO, TMASK, LSH>(ld, smem, wave, lane, st0);
 }
 
 #define KQ_ROWS_DYN_INST(TM, FQ, PR, LS) template __global__ void kq_rows_dyn<TM, FQ, PR, LS>(KQ_ROWS_PARAMS);

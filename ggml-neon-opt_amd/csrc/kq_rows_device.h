@@ -363,15 +363,11 @@ __device__ __forceinline__ int quad_sum(int v) {
 
 // ---------------------------------------------------------------- kq_rows' records and chain
 // kq_rows keeps its records in LDS, written by the quad leaders and replayed by lane r for row r
-// (kq_rows.hip). CHAIN_REC (a build constant, A/B: make variant-rows, profiles/r12_chain_ab.txt;
-// 0 is the form before it): the leader stores what the chain consumes, as floats (RowRec), so
-// the conversions leave the serial chain for the leaders, where 16 of them run at once. The same
-// instruction on the same operand gives the same bits in either place.
-#ifndef KQ_ROWS_CHAIN_REC
-#define KQ_ROWS_CHAIN_REC 1
-#endif
-
-#if KQ_ROWS_CHAIN_REC
+// (kq_rows.hip). The leader stores what the chain consumes, as floats (RowRec), so the
+// conversions leave the serial chain for the leaders, where 16 of them run at once
+// (profiles/r12_chain_ab.txt). The same instruction on the same operand gives the same bits in
+// either place.
+//
 // 16 B as Rec, so the LDS layouts stand. Q4_K: a = (float)sumi, c = y.d * d, b = (float)summins,
 // e = y.d * dmin; Q5_K: a = the superblock's whole term (it does not depend on the running sum);
 // Q6_K: a = (float)(isum - 32 * isum_mins), c = d_all * y.d. Fields a type does not use are
@@ -380,14 +376,10 @@ struct RowRec {
     float a, c, b, e;
 };
 static_assert(sizeof(RowRec) == sizeof(Rec), "the record layouts of rows_layout / rows_dyn_layout");
-#else
-typedef Rec RowRec;
-#endif
 
 // The leader's record of one superblock, stored at `p` (LDS). dh: QuadOut's.
 template <int TYPE>
 __device__ __forceinline__ void row_rec_store(RowRec *p, int isum, int imin, uint32_t dh, float yd) {
-#if KQ_ROWS_CHAIN_REC
     if (TYPE == Q6_K) {
         const float a = (float)(isum - 32 * imin), c = h2f(dh) * yd;  // d_all * y.d
         *(float2 *)p = make_float2(a, c);
@@ -397,27 +389,11 @@ __device__ __forceinline__ void row_rec_store(RowRec *p, int isum, int imin, uin
         if (TYPE == Q5_K) p->a = fmaf(c, (float)isum, -(e * (float)imin));  // d*sumi - dmin*sumi_mins
         else *(float4 *)p = make_float4((float)isum, c, (float)imin, e);
     }
-#else
-    Rec rec;
-    if (TYPE == Q6_K) {
-        rec.a = isum - 32 * imin;
-        rec.b = 0;
-        rec.c = h2f(dh) * yd;  // d_all * y.d
-        rec.e = 0.f;
-    } else {
-        rec.a = isum;
-        rec.b = imin;
-        rec.c = yd * h2f(dh & 0xffffu);  // y.d * fp16(x.d)
-        rec.e = yd * h2f(dh >> 16);      // y.d * fp16(x.dmin)
-    }
-    *p = rec;
-#endif
 }
 
 // One record into registers: one LDS read instruction.
 template <int TYPE>
 __device__ __forceinline__ RowRec row_rec_load(const RowRec *p) {
-#if KQ_ROWS_CHAIN_REC
     RowRec r = {0.f, 0.f, 0.f, 0.f};
     if (TYPE == Q5_K) {
         r.a = p->a;
@@ -429,17 +405,13 @@ __device__ __forceinline__ RowRec row_rec_load(const RowRec *p) {
         r.a = v.x, r.c = v.y, r.b = v.z, r.e = v.w;
     }
     return r;
-#else
-    return *p;
-#endif
 }
 
-// The reference's per-superblock fp32 update on such a record: with CHAIN_REC its dependent
+// The reference's per-superblock fp32 update on such a record: its dependent
 // operations and nothing else. The Q4_K negation is of the float (an operand modifier of the
 // FMA), never of the integer: INT_MIN and the sign of a zero product would differ.
 template <int TYPE>
 __device__ __forceinline__ float row_chain_step(const RowRec &r, float s) {
-#if KQ_ROWS_CHAIN_REC
     if (TYPE == Q4_K) {
         s = fmaf(-r.b, r.e, s);  // sumf -= dmin * summins   (fmsub, README.md:551)
         s = fmaf(r.a, r.c, s);   // sumf += d * sumi         (fmadd, README.md:614)
@@ -449,9 +421,6 @@ __device__ __forceinline__ float row_chain_step(const RowRec &r, float s) {
         s = fmaf(r.c, r.a, s);
     }
     return s;
-#else
-    return chain_step(TYPE, r, s);
-#endif
 }
 
 // Row r's chain, in lane r: records rc[0], rc[stride], .. rc[(nb - 1) * stride] in superblock
@@ -467,6 +436,21 @@ __device__ __forceinline__ float rows_chain(const RowRec *rc, int nb, int stride
     return s;
 }
 
+// One superblock of the stream on its quad: the four lanes' dot products of the weight block at
+// `blk` (LDS, the ring) with the activation's Q8L block at `ab`, summed over the quad, and the
+// leader's record at `rec`. s: the lane within the quad. The one copy of the step that the short
+// form, the generic loop and kq_rows_dyn's loop run.
+template <int TYPE>
+__device__ __forceinline__ void rows_quad_step(const uint8_t *blk, const uint8_t *ab, int s, RowRec *rec) {
+    const QuadOut r = TYPE == Q4_K ? quad_q4K(blk, ab, s) : TYPE == Q5_K ? quad_q5K(blk, ab, s) : quad_q6K(blk, ab, s);
+    const int isum = quad_sum(r.isum);
+    const int imin = quad_sum(r.imin);
+    if (s == 0) {
+        const float yd = *(const float *)ab;
+        row_rec_store<TYPE>(rec, isum, imin, r.dh, yd);
+    }
+}
+
 // ---------------------------------------------------------------- the row stream of one wave
 struct WaveWork {
     int m, r0, nrows;
@@ -480,38 +464,25 @@ __device__ __forceinline__ void vm_wait_k(int k) {
     else if (k == 1) vm_wait<N>();
     else vm_wait<0>();
 }
-// s_waitcnt vmcnt(N * k + P): the same with P younger L2-prefetch loads still counted.
-template <int N, int P>
-__device__ __forceinline__ void vm_wait_kp(int k) {
-    if (k >= 3) vm_wait<3 * N + P>();
-    else if (k == 2) vm_wait<2 * N + P>();
-    else if (k == 1) vm_wait<N + P>();
-    else vm_wait<P>();
-}
 
-// s_waitcnt vmcnt(n) for a run-time, wave-uniform n (a scalar branch per case); above
-// the table's range it waits for the table's largest count, a stronger wait.
-__device__ __forceinline__ void vm_wait_dyn(int n) {
-#define KQ_VMW_CASE(N) \
-    case N: vm_wait<N>(); break;
-    switch (n < 0 ? 0 : n) {
-        KQ_VMW_CASE(0) KQ_VMW_CASE(1) KQ_VMW_CASE(2) KQ_VMW_CASE(3) KQ_VMW_CASE(4) KQ_VMW_CASE(5) KQ_VMW_CASE(6)
-        KQ_VMW_CASE(7) KQ_VMW_CASE(8) KQ_VMW_CASE(9) KQ_VMW_CASE(10) KQ_VMW_CASE(11) KQ_VMW_CASE(12)
-        KQ_VMW_CASE(13) KQ_VMW_CASE(14) KQ_VMW_CASE(15) KQ_VMW_CASE(16) KQ_VMW_CASE(17) KQ_VMW_CASE(18)
-        KQ_VMW_CASE(19) KQ_VMW_CASE(20) KQ_VMW_CASE(21) KQ_VMW_CASE(22) KQ_VMW_CASE(23) KQ_VMW_CASE(24)
-        KQ_VMW_CASE(25) KQ_VMW_CASE(26) KQ_VMW_CASE(27) KQ_VMW_CASE(28) KQ_VMW_CASE(29) KQ_VMW_CASE(30)
-        KQ_VMW_CASE(31) KQ_VMW_CASE(32) KQ_VMW_CASE(33) KQ_VMW_CASE(34) KQ_VMW_CASE(35) KQ_VMW_CASE(36)
-        KQ_VMW_CASE(37) KQ_VMW_CASE(38) KQ_VMW_CASE(39) KQ_VMW_CASE(40)
-        default: vm_wait<40>(); break;
+// One step's DMA instructions (rows_ni of 64 granules, the last one partial) from `base`, this
+// lane's first granule of the step, into the ring slot at `slot`. interior: every granule lies
+// inside the stream; else each is clamped to the stream's last granule `last16`.
+template <int TYPE>
+__device__ __forceinline__ void rows_issue_step(const uint8_t *base, const uint8_t *last16, uint8_t *slot, int lane,
+                                                bool interior) {
+    constexpr int NI = rows_ni(TYPE), PART = rows_gran(TYPE) - 64 * (NI - 1);  // lanes of the partial instruction
+    if (interior) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            if (i + 1 < NI || lane < PART) dma16_nt(base + 1024 * i, (LDS void *)(slot + 1024 * i));
+    } else {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const uint8_t *p = base + 1024 * i;
+            if (i + 1 < NI || lane < PART) dma16_nt(p < last16 ? p : last16, (LDS void *)(slot + 1024 * i));
+        }
     }
-#undef KQ_VMW_CASE
-}
-
-// One L2 prefetch touch: a dword load per lane into a register reserved for it
-// (tied in/out, so every touch reuses it and nothing else is allocated there while
-// the loads are in flight); the caller consumes `sink` after its covering wait.
-__device__ __forceinline__ void l2_touch(const void *p, uint32_t &sink) {
-    asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(p) : "memory");
 }
 
 }  // namespace kq

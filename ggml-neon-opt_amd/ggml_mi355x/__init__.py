@@ -511,7 +511,7 @@ def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=No
     return out
 
 
-DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_PF", "GEMV_XMODE", "GEMV_SMALL_MB", "GEMV_WPC",
+DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_SMALL_MB", "GEMV_WPC",
                "GEMV_SMALL_WG", "GEMV_FQMAX", "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY",
                "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT", "ATTN_STREAM",
                "ATTN_STREAM_TILE")

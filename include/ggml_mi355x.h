@@ -328,7 +328,7 @@ int mi355x_gemv_waves(int waves);
 /* Experiment / diagnostic knobs of A/B runs and timing tools (replaces no reference
  * interface). The library reads no environment variable; every knob holds its product
  * default until set here, process-wide: "GEMV_DIAG", "GEMV_RING", "GEMV_PRE0",
- * "GEMV_PF", "GEMV_XMODE", "GEMV_SMALL_MB", "GEMV_WPC", "GEMV_SMALL_WG", "GEMV_FQMAX",
+ * "GEMV_SMALL_MB", "GEMV_WPC", "GEMV_SMALL_WG", "GEMV_FQMAX",
  * "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY", "ATTN_OPROJ", "AO_NRB"
  * (csrc/kq_internal.h). None changes numerics: the DIAG knobs act only in the diagnostic
  * builds (make variant), the others move launch shapes of bit-exact kernels (ATTN_OPROJ: 1
