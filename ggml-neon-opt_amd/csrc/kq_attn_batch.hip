@@ -2,7 +2,7 @@
 // mask come from the graph's own inputs (ggml: SET_ROWS(k_idxs / v_idxs) + MUL_MAT(K cache, Q)
 // + SOFT_MAX(kq, mask, scale) + MUL_MAT(V cache, kq)): several sequences in one unified
 // cache, or one sequence whose cells have moved (a removed cell, a context shift, a prefix
-// reused at another offset). kq_attn_decode / kq_attn_prompt (kq_ops.hip) store a token at
+// reused at another offset). kq_attn_decode (kq_attn_decode.hip) / kq_attn_prompt (kq_ops.hip) store a token at
 // cell == pos and attend causally over [0, pos]; here nothing derives a cell or visibility
 // from the position, which only selects the rope row.
 //

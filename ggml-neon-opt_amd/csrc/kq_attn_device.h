@@ -1,5 +1,5 @@
 // kq_attn_device.h — decode attention of ONE kv group (its gsz query heads), the work
-// unit of kq_attn_group (kq_ops.hip). Same arithmetic as kq_attn_decode (one workgroup
+// unit of kq_attn_group (kq_attn_decode.hip). Same arithmetic as kq_attn_decode (one workgroup
 // per query head), op for op, so every output bit is the reference's:
 //   rope(q_h), rope(k_g) at pos -> f16; v_g -> f16; the new cell written to both caches
 //   (set_rows, V transposed); KQ = ggml_vec_dot_f16 (NEON FP16 structure) * scale,

@@ -1,6 +1,7 @@
 // kq_attn_head.h — decode attention of one query head on 256 threads (rope + f16 KV-cache
-// write + KQ + soft_max + KQV), the body of kq_attn_decode (kq_ops.hip) and of the fused
-// attention + o-proj kernel (kq_attn_oproj.hip).
+// write + KQ + soft_max + KQV), the body of kq_attn_decode (kq_attn_decode.hip), of the fused
+// attention + o-proj kernel (kq_attn_oproj.hip) and of the persistent layer (kq_layer.hip);
+// with the steps the cells-split kernels (kq_attn_decode.hip) share with it.
 #pragma once
 
 #include "kq_attn_device.h"
@@ -29,7 +30,7 @@ namespace kq {
 //  4. kqv[d] = vec_dot_f16(v_cache[g*hd+d][0..n_kv), p16): thread (d, j) runs
 //     accumulator j (8 lanes) over cells 32it+8j+l, then the f16 reduce tree.
 // A position outside the cache fails loudly: NaN output, caches untouched.
-// Caches past KQ_ATTN_BATCH_CTX cells (kq_attn_decode<HD, true, DS>, DS = 4 or 8): the head
+// Caches past ATTN_BATCH_CTX cells (kq_attn_decode<HD, true, DS>, DS = 4 or 8): the head
 // is split over DS workgroups by output; q/k/v, the rope row and the first chunk of K rows
 // arrive by LDS-DMA with the position, K whole rows per instruction into a two-slot ring
 // per wave (KDMA below), soft_max on each thread's own cells (head_dim 64), and the
@@ -39,65 +40,29 @@ namespace kq {
 #ifndef KQ_ATTN_DIAG
 #define KQ_ATTN_DIAG 0
 #endif
-// Cells whose K row / V chunk is loaded with the position, before it is known (the rest,
-// up to the position, after it): 0 = every cell of the register path (TPH) / 8 V iterations.
-#ifndef KQ_ATTN_PFC
-// 0 (all of them) -> 64: TinyLlama token +2 % (tools/ab_ao.sh); 64 -> 32: +0.5 % (tg128, three
-// interleaved rounds), 8B equal; 128: -1 % (tools/attn_pfc_ab.sh, profiles/r05_attn_pfc_ab.txt)
-#define KQ_ATTN_PFC 32
-#endif
-// a diagnostic stop's output: depends on every value it keeps live, always a float in [1, 2)
-// (garbage bits would send the next GEMV's rms_norm and soft_max down their slow paths)
-__device__ __forceinline__ float adiag_finite(uint32_t bits) { return __uint_as_float((bits & 0x007fffffu) | 0x3f800000u); }
-// Experiment build (KQ_ATTN_EARLY=1): the cells past the prefetched ones, up to the position,
-// requested as soon as the position is known (before rope, KQ and soft_max) instead of where
-// they are used: K rows up to the register path's TPH cells, V chunks of KQ_ATTN_VPOST more
-// 32-cell iterations. Measured neutral to -1 % on the TinyLlama / 8B tokens
-// (profiles/r04_attn_ab.txt), so off.
-#ifndef KQ_ATTN_EARLY
-#define KQ_ATTN_EARLY 0
-#endif
-#ifndef KQ_ATTN_VPOST
-#define KQ_ATTN_VPOST 2
-#endif
-// V-cache iterations (32 cells each) requested together in KQV, past the prefetched ones
-#ifndef KQ_ATTN_VB
-#define KQ_ATTN_VB 8
-#endif
-#ifndef KQ_ATTN_VB64  // head_dim 64: half the registers per K row, twice the batch
-#define KQ_ATTN_VB64 8
-#endif
-#ifndef KQ_ATTN_KR64
-#define KQ_ATTN_KR64 2
-#endif
-#ifndef KQ_ATTN_KR128  // head_dim 128: a K row is 64 VGPRs; two per round cost the short-context
-#define KQ_ATTN_KR128 1  // launch 0.7 us at Llama-3-8B (247 VGPRs, profiles/r05q_token8b_summary.md)
-#endif
-#ifndef KQ_ATTN_EARLYV  // 1: head_dim 64, KQV's first V batch requested with the position (measured -1 % tg1024)
-#define KQ_ATTN_EARLYV 0
-#endif
-#ifndef KQ_ATTN_VLDS  // 1: experiment build with the LDS-staged V rows (launch_attn): measured neutral
-#define KQ_ATTN_VLDS 0
-#endif
 #if KQ_ATTN_DIAG
 #define ADIAG(a) ((a).diag)
 #else
 #define ADIAG(a) 0
 #endif
-// The per-head body, shared by kq_attn_decode (one 256-thread workgroup per head) and the
-// fused attention + o-proj kernel (kq_attn_oproj.hip: several heads per workgroup, 256
-// threads each; every __syncthreads() is reached by all of them in the same order since the
-// control flow depends only on the position). t: the thread's index within the head's 256;
-// smem: this head's LDS (attn_lds bytes); out: where output d of the head goes
-// (out[d], global or LDS); may_write: this workgroup may store the new KV cell.
-// TPH: threads per head (256; 128 for head_dim 64 in the fused kernel, where 4 heads share a
-// workgroup and 256 threads each would cap it at 128 VGPRs): the register path holds one
-// cell per thread (n_kv <= TPH), KQV runs HD * 4 / TPH (d, j) items per thread.
-// VPF0: V-cache iterations (32 cells each) prefetched with the position (0: 8 / ITEMS).
-// OUT_WT: out is global memory, stored write-through (sc1) for the next launch (kq_rows'
-// outputs likewise, store_y).
-// SC1_IN: q / k / v were written in this launch by other workgroups (the persistent layer,
-// kq_layer.hip): every load of them is an agent-scope (sc1) load, as the hand-off requires.
+// a diagnostic stop's output: depends on every value it keeps live, always a float in [1, 2)
+// (garbage bits would send the next GEMV's rms_norm and soft_max down their slow paths)
+__device__ __forceinline__ float adiag_finite(uint32_t bits) { return __uint_as_float((bits & 0x007fffffu) | 0x3f800000u); }
+
+// The settled constants ("Retired build switches of the decode attention").
+// Cells whose K row / V chunk is loaded with the position, before it is known (the rest, up to
+// the position, after it). All of them -> 64: TinyLlama token +2 %; 64 -> 32: +0.5 % (tg128),
+// 8B equal; 128: -1 % (profiles/r05_attn_pfc_ab.txt)
+constexpr int ATTN_PFC = 32;
+// V-cache iterations (32 cells each) requested together in KQV, past the prefetched ones
+constexpr int ATTN_VB = 8;
+// K rows per thread per round of the batched KQ. head_dim 128: a K row is 64 VGPRs; two per
+// round cost the short-context launch 0.7 us at Llama-3-8B (247 VGPRs)
+constexpr int ATTN_KR64 = 2, ATTN_KR128 = 1;
+// K-cache ring of the split kernels (KDMA below): per wave ATTN_KD slots of 64 rows (8 KiB)
+constexpr int ATTN_KD = 2;
+constexpr int ATTN_KSLOT = 64 * 128;
+
 // One LDS-DMA instruction (default cache policy: the V cache is re-read token after token)
 // for lanes [0, n) at LDS byte address m0 (wave-uniform), the lane mask set inside the asm.
 #pragma clang diagnostic push
@@ -128,25 +93,140 @@ __device__ __forceinline__ void attn_dma16(const void *src, uint32_t m0) {
 }
 #pragma clang diagnostic pop
 
-// K-cache ring of the split head_dim-64 kernel (KDMA below): per wave KQ_ATTN_KD slots of 64
-// rows (8 KiB)
-#ifndef KQ_ATTN_KD
-#define KQ_ATTN_KD 2
-#endif
-// 1: KDMA's soft_max on the cells each thread scored (max kept from KQ, group sums across the
-// quad's lanes, every wave summing the groups itself): three barriers instead of five
-#ifndef KQ_ATTN_KSM
-#define KQ_ATTN_KSM 1
-#endif
-constexpr int ATTN_KSLOT = 64 * 128;
+// ------------------------------------------------------------ steps shared with the cells split
+// What every decode kernel derives from the position it loaded
+struct AttnPos {
+    bool bad;  // no cache cell for this position: NaN output, caches untouched
+    int pos;   // the position (0 when bad)
+    int n_kv;  // cells scored: pos + 1 rounded up to 32, at most n_ctx
+    int n_it;  // 32-cell iterations holding a cell <= pos; later ones add exact zeros
+};
+__device__ __forceinline__ AttnPos attn_pos(int pos_in, int n_ctx) {
+    AttnPos p;
+    p.bad = pos_in < 0 || pos_in >= n_ctx;
+    p.pos = p.bad ? 0 : pos_in;
+    const int n_kv = (p.pos + 1 + 31) / 32 * 32;
+    p.n_kv = n_kv < n_ctx ? n_kv : n_ctx;
+    p.n_it = (p.pos + 32) / 32;
+    return p;
+}
 
-// attn_lds (kq_ops.hip) on the device: the per-head LDS layout below, before any staged V rows
+// XCD-aware head order (speed only) of a grid of n_head * DS workgroups: workgroup b runs on
+// XCD b % 8, so XCD x takes the consecutive heads [x*n_head/8, (x+1)*n_head/8) (every slice of
+// a head on one XCD) and a KV group's cells are fetched into the L2 of 8*gsz/n_head XCDs
+// (TinyLlama: 2, Llama-3: 1) instead of all 8. A head count that is no multiple of 8: in order.
+template <int DS>
+__device__ __forceinline__ void attn_xcd_head(int n_head, unsigned block, int &h, int &ds) {
+    h = block / DS, ds = block % DS;
+    if ((n_head & 7) == 0) {
+        const int x = block & 7, i = block >> 3;
+        h = x * (n_head >> 3) + i / DS;
+        ds = i % DS;
+    }
+}
+
+// N 16-B pieces of a K row into kv: a row of the cache, the new cell's LDS copy, the row
+// prefetched into registers. One function per source, as the sites name what they read; the
+// sources stay separate branches at every site (a select among them takes the register copy's
+// address and puts it in scratch).
+template <int N>
+__device__ __forceinline__ void attn_k_row_global(uint4 (&kv)[N], const uint16_t *row) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) kv[i] = ((const uint4 *)row)[i];
+}
+template <int N>
+__device__ __forceinline__ void attn_k_row_lds(uint4 (&kv)[N], const uint16_t *k16) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) kv[i] = ((const uint4 *)k16)[i];
+}
+template <int N>
+__device__ __forceinline__ void attn_k_row_regs(uint4 (&kv)[N], const uint4 (&kpre)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) kv[i] = kpre[i];
+}
+// ... of a lane's 128 B of a ring slot, piece i at position i ^ sw
+template <int N>
+__device__ __forceinline__ void attn_k_row_ring(uint4 (&kv)[N], const uint8_t *rowp, int sw) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) kv[i] = *(const uint4 *)(rowp + 16 * (i ^ sw));
+}
+
+// soft_max's max over the block: every wave publishes its own, then (after a barrier) reads all four
+__device__ __forceinline__ void wave_fmax_publish(float *scal, int t, float wmx) {
+    if ((t & 63) == 0) scal[t >> 6] = wmx;
+}
+__device__ __forceinline__ float wave4_fmax(const float *scal) {
+    return fmaxf(fmaxf(scal[0], scal[1]), fmaxf(scal[2], scal[3]));
+}
+// the group sum of cells 4g..4g+3 (lanes 4g..4g+3, ec each) in the vaddvq order (e0 + e1) + (e2 + e3): in lane 4g
+__device__ __forceinline__ float quad_group_sum(float ec) {
+    const float s01 = ec + dpp_mov_f32<0xB1>(ec);  // lane 4g: e0 + e1, lane 4g+2: e2 + e3
+    return s01 + dpp_mov_f32<0x4E>(s01);           // lane 4g: (e0 + e1) + (e2 + e3)
+}
+
+// The group sums' double sum over a block of four waves: each wave sums its own groups (se) and
+// publishes one double with its min last-bit exponent and a non-finite flag in the caller's
+// scratch (sum[4], gmin[4], bad[4]); after the barrier the four wave sums are the total, and
+// the return value says whether it meets softmax_group_sum's exactness bound (every partial sum
+// exact: any order gives ggml's in-order bits). Where it does not, the caller sums gsum in order.
+__device__ __forceinline__ bool block_sum_exact4(const SumExact &se, int wv, int ln, double *sum, int *gmin, int *bad,
+                                                 double &total) {
+    const bool wbad = __any(se.bad);
+    const int wgmin = wave_imin(se.gmin);
+    double wsum = se.part;  // (meaningful only where exact)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
+    if (ln == 0) {
+        sum[wv] = wsum;
+        gmin[wv] = wgmin;
+        bad[wv] = wbad;
+    }
+    __syncthreads();
+    const int gm = min(min(gmin[0], gmin[1]), min(gmin[2], gmin[3]));
+    total = (sum[0] + sum[1]) + (sum[2] + sum[3]);
+    return sum_exact_ok(total, gm, (bad[0] | bad[1] | bad[2] | bad[3]) != 0);
+}
+
+// KQV's inner step: the new cell's value (*vnew, the LDS copy) in place of cell pos of the 8
+// cells c0 .. c0 + 7 of a V chunk, where it lies among them
+__device__ __forceinline__ uint4 attn_patch_new_cell(uint4 v, int pos, int c0, const uint16_t *vnew) {
+    uint32_t vw[4] = {v.x, v.y, v.z, v.w};
+    if (pos >= c0 && pos < c0 + 8) {
+        const int l = pos - c0;
+        vw[l >> 1] = (vw[l >> 1] & (0xffff0000u >> (16 * (l & 1)))) | ((uint32_t)*vnew << (16 * (l & 1)));
+    }
+    return make_uint4(vw[0], vw[1], vw[2], vw[3]);
+}
+// ... and the four packed FMAs of 8 cells into the accumulator's words
+__device__ __forceinline__ void attn_fma4(uint32_t (&acc)[4], uint4 v, uint4 p) {
+    acc[0] = pk_fma_w(v.x, p.x, acc[0]);
+    acc[1] = pk_fma_w(v.y, p.y, acc[1]);
+    acc[2] = pk_fma_w(v.z, p.z, acc[2]);
+    acc[3] = pk_fma_w(v.w, p.w, acc[3]);
+}
+
+// ------------------------------------------------------------ the per-head body
+// attn_lds (kq_attn_decode.hip) on the device: the per-head LDS layout below, before any staged V rows
 __device__ __forceinline__ int attn_lds_dev(int hd, int n_ctx) {
     const int gsum = (n_ctx / 4) * 8 <= hd * 64 ? 0 : (n_ctx / 4) * 8;
     return 6 * hd + n_ctx * 6 + hd * 64 + 16 + gsum;
 }
 
-// DS > 1 (kq_attn_decode past KQ_ATTN_BATCH_CTX cells, BATCH): the head is split over DS
+// The per-head body, shared by kq_attn_decode (one 256-thread workgroup per head) and the
+// fused kernels (kq_attn_oproj.hip, kq_layer.hip: several heads per workgroup, 256
+// TPH threads each; every __syncthreads() is reached by all of them in the same order since the
+// control flow depends only on the position). t: the thread's index within the head's 256;
+// smem: this head's LDS (attn_lds bytes); out: where output d of the head goes
+// (out[d], global or LDS); may_write: this workgroup may store the new KV cell.
+// TPH: threads per head (256; 128 for head_dim 64 in the fused kernel, where 4 heads share a
+// workgroup and 256 threads each would cap it at 128 VGPRs): the register path holds one
+// cell per thread (n_kv <= TPH), KQV runs HD * 4 / TPH (d, j) items per thread.
+// VPF0: V-cache iterations (32 cells each) prefetched with the position (0: 8 / ITEMS).
+// OUT_WT: out is global memory, stored write-through (sc1) for the next launch (kq_rows'
+// outputs likewise, store_y).
+// SC1_IN: q / k / v were written in this launch by other workgroups (the persistent layer,
+// kq_layer.hip): every load of them is an agent-scope (sc1) load, as the hand-off requires.
+// DS > 1 (kq_attn_decode past ATTN_BATCH_CTX cells, BATCH): the head is split over DS
 // workgroups by output dimension; workgroup ds computes the whole KQ and soft_max (every slice
 // needs every weight) and KQV for outputs [ds HD/DS, (ds + 1) HD/DS) only, from its slice of
 // the V rows, staged in LDS by LDS-DMA as soon as the position is known. One workgroup's
@@ -154,7 +234,7 @@ __device__ __forceinline__ int attn_lds_dev(int hd, int n_ctx) {
 // unsplit head waits for them in n_kv / (32 VB) dependent batches after soft_max. The
 // accumulation order of every output is unchanged (bit-exact).
 template <int HD, int TPH = 256, int VPF0 = 0, bool OUT_WT = false, bool SC1_IN = false, bool BATCH = false,
-          int DS = 1, bool KD1 = false>
+          int DS = 1>
 __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8_t *smem, float *out,
                                           bool may_write, int ds = 0) {
     auto ldin = [](const float *p) {
@@ -165,7 +245,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
     constexpr int KV4 = HD / 8;          // 16-B pieces of one K-cache row
     static_assert(TPH == 256 || (TPH == 128 && HD == 64), "threads per head");
     // BATCH (kq_attn_decode): the cache loads past the prefetched cells are batched (KR K rows
-    // per round, KQ_ATTN_VB V chunks); the fused kernels' register budgets keep one K row and
+    // per round, ATTN_VB V chunks); the fused kernels' register budgets keep one K row and
     // one V chunk per step (PAIR off)
     constexpr bool PAIR = BATCH && TPH == 256 && !SC1_IN;
     static_assert(DS == 1 || (PAIR && (HD / DS) % 4 == 0 && HD / DS * 4 <= TPH), "output slices");
@@ -180,20 +260,18 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
     // bank conflicts; the dot product itself is unchanged (bit-exact).
     // head_dim 128: a row is 256 B, two lanes per cell (each holding half the row; the odd
     // lane continues the even lane's accumulators: the NEON order), 128 cells per chunk.
-    // KD1 (experiment builds, KQ_ATTN_KDMA1): the unsplit head of a short cache (<= 256 cells)
-    // on the same LDS-DMA path: K ring, staged q | k | v, V rows in LDS
-    constexpr bool KDMA = PAIR && (DS > 1 || KD1);
+    constexpr bool KDMA = PAIR && DS > 1;
     constexpr int CPC = HD == 64 ? 256 : 128;  // (KDMA) cells per chunk, CPC / 4 per wave
-    // (KDMA) soft_max on each thread's own cells: head_dim 64 (one cell per lane)
-    constexpr bool KSM = KDMA && HD == 64 && KQ_ATTN_KSM != 0;
-    constexpr int VB = PAIR ? (HD == 64 ? KQ_ATTN_VB64 : KQ_ATTN_VB) : 4;
-    constexpr int KR = HD == 64 ? KQ_ATTN_KR64 : KQ_ATTN_KR128;  // K rows per thread per round (register budget)
+    // (KDMA) soft_max on the cells each thread scored (max kept from KQ, group sums across the
+    // quad's lanes, every wave summing the groups itself): head_dim 64 (one cell per lane);
+    // three barriers instead of five
+    constexpr bool KSM = KDMA && HD == 64;
+    constexpr int VB = PAIR ? ATTN_VB : 4;
+    constexpr int KR = HD == 64 ? ATTN_KR64 : ATTN_KR128;  // K rows per thread per round (register budget)
     constexpr int ITEMS = HD * 4 / TPH;  // KQV (d, j) items per thread
-    constexpr int VPF = VPF0 > 0 ? VPF0 : KQ_ATTN_PFC > 0 ? (KQ_ATTN_PFC / 32 < 8 / ITEMS ? KQ_ATTN_PFC / 32 : 8 / ITEMS)
-                                                         : 8 / ITEMS;  // prefetched 32-cell iterations per item
-    constexpr int KPF = KQ_ATTN_PFC > 0 && KQ_ATTN_PFC < TPH ? KQ_ATTN_PFC : TPH;  // K rows prefetched (thread t < KPF)
-    static_assert(VPF + (KQ_ATTN_EARLY ? KQ_ATTN_VPOST : 0) <= (BATCH && TPH == 256 && !SC1_IN ? KQ_ATTN_VB : 4),
-                  "KQV's first batch holds the prefetched V iterations");
+    constexpr int VPF = VPF0 > 0 ? VPF0 : (ATTN_PFC / 32 < 8 / ITEMS ? ATTN_PFC / 32 : 8 / ITEMS);  // prefetched 32-cell iterations per item
+    constexpr int KPF = ATTN_PFC < TPH ? ATTN_PFC : TPH;  // K rows prefetched (thread t < KPF)
+    static_assert(VPF <= VB, "KQV's first batch holds the prefetched V iterations");
     const int gsz = a.n_head / a.n_head_kv;
     const int g = h / gsz;
     const int kvw = a.n_head_kv * HD;
@@ -220,7 +298,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
     // of one (128: row ln / 2, half ln & 1), its 16-B chunk k at position k ^ ((ln >> 1) & 7)
     auto issue_k = [&](int c, int lim) {
         const int wv = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
-        const uint32_t slot = (uint32_t)(uintptr_t)(LDS void *)(kring + (wv * KQ_ATTN_KD + c % KQ_ATTN_KD) * ATTN_KSLOT);
+        const uint32_t slot = (uint32_t)(uintptr_t)(LDS void *)(kring + (wv * ATTN_KD + c % ATTN_KD) * ATTN_KSLOT);
         const int r = ln >> 3, pp = ln & 7;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -273,16 +351,13 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
     }
     uint4 kpre[KV4] = {};
     if (!KDMA && t < a.n_ctx && t < KPF && ADIAG(a) != 5) {  // (diag 5: no cache loads, stop after rope; timing only)
-        const uint4 *kr = (const uint4 *)(a.k_cache + (int64_t)t * kvw + (int64_t)g * HD);
-#pragma unroll
-        for (int i = 0; i < KV4; ++i) kpre[i] = kr[i];
+        attn_k_row_global(kpre, a.k_cache + (int64_t)t * kvw + (int64_t)g * HD);
     }
-    // V rows staged in LDS (launch_attn sets a.v_lds) only in the KQ_ATTN_VLDS build: as a run-time
-    // choice its LDS / global select turned KQV's cache loads into flat loads (tg1024 -4 %, r5t)
-    const bool vl = KDMA || (PAIR && KQ_ATTN_VLDS && a.v_lds);
+    // V rows: staged in LDS on the KDMA path, prefetched into registers on the others (a run-time
+    // choice between the two turned KQV's cache loads into flat loads: tg1024 -4 %)
     uint4 vpre[ITEMS][VPF] = {};
 #pragma unroll
-    for (int ii = 0; ii < ITEMS && !vl; ++ii) {
+    for (int ii = 0; ii < ITEMS && !KDMA; ++ii) {
         const int item = t + TPH * ii, d = item >> 2, j = item & 3;
         const uint16_t *vr = a.v_cache + (int64_t)(g * HD + d) * a.n_ctx + 8 * j;
 #pragma unroll
@@ -290,38 +365,21 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
             if (32 * it < a.n_ctx && ADIAG(a) != 5) vpre[ii][it] = *(const uint4 *)(vr + 32 * it);
     }
 
+    // (attn_pos's lines, kept here: through the helper the compiler knows pos >= 0 earlier, and
+    // the fused kernels and kq_attn_decode<HD, false> come out 1 to 5 instructions longer)
     const bool bad = pos_in < 0 || pos_in >= a.n_ctx;  // no cache cell for this position
     const int pos = bad ? 0 : pos_in;
     int n_kv = (pos + 1 + 31) / 32 * 32;
     n_kv = n_kv < a.n_ctx ? n_kv : a.n_ctx;
-    constexpr int VPOST = KQ_ATTN_EARLY ? KQ_ATTN_VPOST : 0;
-    uint4 vpost[ITEMS][VPOST > 0 ? VPOST : 1] = {};
-    if (KQ_ATTN_EARLY && ADIAG(a) != 5) {
-        if (KPF < TPH && t >= KPF && t < pos && t < a.n_ctx) {  // this thread's K row, c = t < pos
-            const uint4 *kr = (const uint4 *)(a.k_cache + (int64_t)t * kvw + (int64_t)g * HD);
-#pragma unroll
-            for (int i = 0; i < KV4; ++i) kpre[i] = kr[i];
-        }
-#pragma unroll
-        for (int ii = 0; ii < ITEMS; ++ii) {
-            const int item = t + TPH * ii, d = item >> 2, j = item & 3;
-            const uint16_t *vr = a.v_cache + (int64_t)(g * HD + d) * a.n_ctx + 8 * j;
-#pragma unroll
-            for (int k = 0; k < VPOST; ++k) {
-                const int it = VPF + k;
-                if (32 * it <= pos) vpost[ii][k] = *(const uint4 *)(vr + 32 * it);  // (32 it <= pos < n_ctx)
-            }
-        }
-    }
     // V rows of the head's kv group (DS > 1: the slice's RS rows), cells [0, n_kv), into LDS
-    // (vl): wave w takes rows [w RS / 4, (w + 1) RS / 4); local row r at vlds + r * VSTR;
+    // (KDMA): wave w takes rows [w RS / 4, (w + 1) RS / 4); local row r at vlds + r * VSTR;
     // completion: vmcnt(0) + barrier before KQV. Issued once KQ's cache loads have been used:
     // vmcnt retires in issue order, so a wait for any load issued after the DMAs (rope's inputs,
     // KQ's K rows) would wait for them too; soft_max issues no memory loads and runs under them.
     // A cell past pos holds whatever the cache holds (its weight is an exact 0); the new cell is
     // patched from v16 as on the register path.
     auto issue_v_rows = [&]() {
-        if (!vl) return;
+        if (!KDMA) return;
         // every earlier load has been used; the builtin (unlike an asm wait) tells the compiler,
         // which would otherwise wait vmcnt(0) later for loads it cannot prove consumed (a kpre
         // row on a path that skipped it) — and so for these DMAs behind them. On every path.
@@ -341,21 +399,6 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         }
     };
 
-    // EARLYV (head_dim 64, kq_attn_decode): KQV's first batch of V chunks past the prefetched
-    // ones requested as soon as the position is known, under KQ and soft_max
-    constexpr bool EARLYV = PAIR && HD == 64 && KQ_ATTN_EARLYV;
-    uint4 vb0[ITEMS][EARLYV ? VB : 1];
-    if (EARLYV && !vl) {
-        const int n_it0 = (pos + 32) / 32;
-#pragma unroll
-        for (int ii = 0; ii < ITEMS; ++ii) {
-            const int item = t + TPH * ii, d = item >> 2, j = item & 3;
-            const uint16_t *vr = a.v_cache + (int64_t)(g * HD + d) * a.n_ctx;
-#pragma unroll
-            for (int k = VPF + VPOST; k < (EARLYV ? VB : 1); ++k)
-                if (k < n_it0) vb0[ii][k] = *(const uint4 *)(vr + 32 * k + 8 * j);
-        }
-    }
     if constexpr (KDMA) {  // the staged q | k | v | rope row landed (wave 0: all but chunk 0's 8 DMAs)
         if (t < 64) __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8)
         __syncthreads();
@@ -378,6 +421,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
         }
     }
+    // ---- 1. rope(q), rope(k), v -> f16 in LDS; the writer stores the new cell
     const float *tc = a.rope_table + (a.rope_row ? 0 : (int64_t)pos * (HD / 2) * 2);
     const bool writer = may_write && !bad && (h % gsz) == 0 && ds == 0;
     if (t < HD / 2) {
@@ -398,11 +442,14 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
     }
     __syncthreads();
     if (ADIAG(a) == 1 || ADIAG(a) == 5) {  // diagnostics: stop after the loads and rope
-        vm_wait<0>();  // (staged V DMAs, vl) land before the wave ends
+        vm_wait<0>();  // (staged V DMAs, KDMA) land before the wave ends
         if (t < HD) out[t] = adiag_finite(__float_as_uint(x0) ^ kpre[0].x ^ vpre[0][0].x ^ vpre[0][VPF - 1].y);
         return;
     }
 
+    // ---- 2 + 3. KQ and soft_max, in one of four forms: in registers (n_kv <= TPH); the K ring
+    // (KDMA) with soft_max on the thread's own cells (KSM); the cache rows KR per round (PAIR) or
+    // one by one; and, for all but KSM, soft_max over w in LDS
     if ((!KDMA || HD == 64) && n_kv <= TPH) {  // one cell per thread: score, max, exp and group sum stay in registers
         const int c = t;
         float sc = -INFINITY;
@@ -410,37 +457,28 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         if (c < n_kv && c <= pos) {
             uint4 kv[KV4];
             if (c == pos) {
-#pragma unroll
-                for (int i = 0; i < KV4; ++i) kv[i] = ((const uint4 *)k16)[i];
+                attn_k_row_lds(kv, k16);
             } else if (KDMA) {  // chunk 0's ring slot of this wave: cell t at lane t & 63
-                const int ln = t & 63, sw = (ln >> 1) & 7;
-                const uint8_t *rowp = kring + (__builtin_amdgcn_readfirstlane(t >> 6) * KQ_ATTN_KD) * ATTN_KSLOT + 128 * ln;
-#pragma unroll
-                for (int i = 0; i < KV4; ++i) kv[i] = *(const uint4 *)(rowp + 16 * (i ^ sw));
-            } else if (!KQ_ATTN_EARLY && KPF < TPH && c >= KPF) {  // a cell past the prefetched ones (below the position)
-                const uint4 *kr = (const uint4 *)(a.k_cache + (int64_t)c * kvw + (int64_t)g * HD);
-#pragma unroll
-                for (int i = 0; i < KV4; ++i) kv[i] = kr[i];
-            } else {  // prefetched with the position, or (KQ_ATTN_EARLY) right after it
-#pragma unroll
-                for (int i = 0; i < KV4; ++i) kv[i] = kpre[i];
+                const int ln = t & 63;
+                attn_k_row_ring(kv, kring + (__builtin_amdgcn_readfirstlane(t >> 6) * ATTN_KD) * ATTN_KSLOT + 128 * ln, (ln >> 1) & 7);
+            } else if (KPF < TPH && c >= KPF) {  // a cell past the prefetched ones (below the position)
+                attn_k_row_global(kv, a.k_cache + (int64_t)c * kvw + (int64_t)g * HD);
+            } else {  // prefetched with the position
+                attn_k_row_regs(kv, kpre);
             }
             sc = vec_dot_f16_rows<HD>(kv, (const uint4 *)q16) * a.scale;
         }
         issue_v_rows();
-        const float wmx = wave_fmax(sc);  // max (order-free): per wave, then over the 4 waves
-        if ((t & 63) == 0) scal[t >> 6] = wmx;
+        wave_fmax_publish(scal, t, wave_fmax(sc));  // max (order-free): per wave, then over the 4 waves
         __syncthreads();
         if (ADIAG(a) == 2) {  // diagnostics: stop after KQ
-            vm_wait<0>();  // (staged V DMAs, vl) land before the wave ends
+            vm_wait<0>();  // (staged V DMAs, KDMA) land before the wave ends
             if (t < HD) out[t] = adiag_finite(__float_as_uint(sc) ^ vpre[0][0].x ^ vpre[0][VPF - 1].y);
             return;
         }
-        const float mx = TPH == 256 ? fmaxf(fmaxf(scal[0], scal[1]), fmaxf(scal[2], scal[3])) : fmaxf(scal[0], scal[1]);
+        const float mx = TPH == 256 ? wave4_fmax(scal) : fmaxf(scal[0], scal[1]);
         const float ec = c < n_kv && sc != -INFINITY ? v_expf(sc - mx) : 0.0f;
-        // group sum of cells 4g..4g+3 (lanes 4g..4g+3) in the vaddvq order (e0 + e1) + (e2 + e3)
-        const float s01 = ec + dpp_mov_f32<0xB1>(ec);   // lane 4g: e0 + e1, lane 4g+2: e2 + e3
-        const float g4 = s01 + dpp_mov_f32<0x4E>(s01);  // lane 4g: (e0 + e1) + (e2 + e3)
+        const float g4 = quad_group_sum(ec);
         if ((t & 3) == 0 && c < n_kv) gsum[t >> 2] = (double)g4;
         __syncthreads();
         // every wave computes the same sum (no barrier to publish it): ggml's in-order double
@@ -450,7 +488,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         if (c < n_kv) p16[c] = h2u(f2h_rne(ec * inv));
         __syncthreads();
         if (ADIAG(a) == 3) {  // diagnostics: stop after soft_max
-            vm_wait<0>();  // (staged V DMAs, vl) land before the wave ends
+            vm_wait<0>();  // (staged V DMAs, KDMA) land before the wave ends
             if (t < HD) out[t] = adiag_finite((uint32_t)p16[t] ^ vpre[0][0].x ^ vpre[0][VPF - 1].y);
             return;
         }
@@ -461,33 +499,22 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
             const int sw = (ln >> 1) & 7;             // this lane's 128 B: chunk k at position k ^ sw
             // head_dim 128: this lane's half of q (chunks 8 (ln & 1) + k)
             uint4 qh[8];
-            if (HD == 128) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) qh[i] = ((const uint4 *)q16)[8 * (ln & 1) + i];
-            }
+            if (HD == 128) attn_k_row_lds(qh, q16 + 64 * (ln & 1));
             // chunk 0 was issued with the position (prologue); the cache stores of the new cell,
             // issued since, are older than chunk 1 and covered by its waits
             if (n_ch > 1) issue_k(1, n_kv);
-            static_assert(KQ_ATTN_KD == 2 || KQ_ATTN_KD == 3, "the waits below cover two or three slots per wave");
-            if (KQ_ATTN_KD == 3 && n_ch > 2) issue_k(2, n_kv);
-            float mloc = -INFINITY;  // (KQ_ATTN_KSM) the max over this thread's cells
+            static_assert(ATTN_KD == 2, "the waits below cover two slots per wave");
+            float mloc = -INFINITY;  // (KSM) the max over this thread's cells
             for (int c = 0; c < n_ch; ++c) {
                 // chunk c landed: the younger chunks in flight (8 DMAs each) may still be
-                if (KQ_ATTN_KD == 3 && c + 2 < n_ch) __builtin_amdgcn_s_waitcnt(0x4F70);  // vmcnt(16)
-                else if (c + 1 < n_ch) __builtin_amdgcn_s_waitcnt(0x0F78);               // vmcnt(8)
+                if (c + 1 < n_ch) __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8)
                 else __builtin_amdgcn_s_waitcnt(0x0F70);
                 if constexpr (HD == 64) {
                 const int cell = 256 * c + t;
                 if (cell < n_kv) {
                     uint4 kv[KV4];
-                    if (cell == pos) {
-#pragma unroll
-                        for (int i = 0; i < KV4; ++i) kv[i] = ((const uint4 *)k16)[i];
-                    } else {
-                        const uint8_t *rowp = kring + (wv * KQ_ATTN_KD + c % KQ_ATTN_KD) * ATTN_KSLOT + 128 * ln;
-#pragma unroll
-                        for (int i = 0; i < KV4; ++i) kv[i] = *(const uint4 *)(rowp + 16 * (i ^ sw));
-                    }
+                    if (cell == pos) attn_k_row_lds(kv, k16);
+                    else attn_k_row_ring(kv, kring + (wv * ATTN_KD + c % ATTN_KD) * ATTN_KSLOT + 128 * ln, sw);
                     const float sc = cell <= pos ? vec_dot_f16_rows<HD>(kv, (const uint4 *)q16) * a.scale : -INFINITY;
                     w[cell] = sc;
                     mloc = fmaxf(mloc, sc);
@@ -496,14 +523,8 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                     const int cell = 128 * c + 32 * wv + (ln >> 1);
                     const bool live = cell < n_kv;  // (uniform per lane pair: both or neither)
                     uint4 kv[8];
-                    if (cell == pos) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) kv[i] = ((const uint4 *)k16)[8 * (ln & 1) + i];
-                    } else {
-                        const uint8_t *rowp = kring + (wv * KQ_ATTN_KD + c % KQ_ATTN_KD) * ATTN_KSLOT + 128 * ln;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) kv[i] = *(const uint4 *)(rowp + 16 * (i ^ sw));
-                    }
+                    if (cell == pos) attn_k_row_lds(kv, k16 + 64 * (ln & 1));
+                    else attn_k_row_ring(kv, kring + (wv * ATTN_KD + c % ATTN_KD) * ATTN_KSLOT + 128 * ln, sw);
                     // ggml_vec_dot_f16 (NEON FP16), accumulator j over chunks j, 4+j, 8+j, 12+j:
                     // every lane runs its own two chunks per accumulator from 0 (the even lane's
                     // are the first two steps), then again from the even lane's result (the odd
@@ -533,13 +554,12 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                     const float dot = f16x8_reduce(sv);
                     if (live && (ln & 1)) w[cell] = cell <= pos ? dot * a.scale : -INFINITY;
                 }
-                if (c + KQ_ATTN_KD < n_ch) issue_k(c + KQ_ATTN_KD, n_kv);  // (this slot's reads were used above)
+                if (c + ATTN_KD < n_ch) issue_k(c + ATTN_KD, n_kv);  // (this slot's reads were used above)
             }
             if constexpr (KSM) {
                 // soft_max over the thread's own cells 256 c + t (written by this thread: no
                 // barrier before reading them back). max: per wave, then over the 4 waves
-                const float wmx = wave_fmax(mloc);
-                if ((t & 63) == 0) scal[t >> 6] = wmx;
+                wave_fmax_publish(scal, t, wave_fmax(mloc));
                 issue_v_rows();
                 __syncthreads();
                 if (ADIAG(a) == 2) {  // diagnostics: stop after KQ
@@ -547,20 +567,13 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                     if (t < HD) out[t] = adiag_finite(__float_as_uint(w[t]));
                     return;
                 }
-                const float mx = fmaxf(fmaxf(scal[0], scal[1]), fmaxf(scal[2], scal[3]));
-                // the group sums' double sum: each wave sums its own groups and publishes one
-                // double with its min last-bit exponent and a non-finite flag; where the total
-                // meets softmax_group_sum's exactness bound (every partial sum exact: any order
-                // gives ggml's in-order bits) the four wave sums are the sum, else the in-order
-                // sum over gsum
+                const float mx = wave4_fmax(scal);
                 SumExact se;
                 for (int c = 0; c < n_ch; ++c) {  // (uniform trip count: every lane in the quad sums)
                     const int cell = 256 * c + t;
                     const float sv = cell < n_kv ? w[cell] : -INFINITY;
                     const float ec = sv == -INFINITY ? 0.0f : v_expf(sv - mx);
-                    // group of cells 4g..4g+3 (lanes 4g..4g+3) in the vaddvq order (e0 + e1) + (e2 + e3)
-                    const float s01 = ec + dpp_mov_f32<0xB1>(ec);
-                    const float g4 = s01 + dpp_mov_f32<0x4E>(s01);
+                    const float g4 = quad_group_sum(ec);
                     if (cell < n_kv) {
                         w[cell] = ec;
                         if ((t & 3) == 0) {
@@ -569,29 +582,11 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                         }
                     }
                 }
-                const bool wbad = __any(se.bad);
-                const int wgmin = wave_imin(se.gmin);
-                const double wsum = wave_sum_exact_f64(se.part);  // (meaningful only where exact)
-                if ((t & 63) == 0) {
-                    *(double *)(kring + 16 * wv) = wsum;  // (the K ring is free: every chunk consumed)
-                    *(int *)(kring + 16 * wv + 8) = wgmin;
-                    *(int *)(kring + 16 * wv + 12) = wbad;
-                }
-                __syncthreads();
-                bool anybad = false;
-                int gmin = 1 << 20;
-                double s4[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    s4[q] = *(const double *)(kring + 16 * q);
-                    const int gq = *(const int *)(kring + 16 * q + 8);
-                    gmin = gq < gmin ? gq : gmin;
-                    anybad = anybad || *(const int *)(kring + 16 * q + 12) != 0;
-                }
-                const double s4t = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-                const double sum = sum_exact_ok(s4t, gmin, anybad)
-                                       ? s4t
-                                       : (KQ_SEQ_SUM_WAVE ? seq_sum_wave(gsum, n_kv / 4, t & 63) : seq_sum_lds(gsum, n_kv / 4));
+                // the block's total through the K ring (free: every chunk consumed), where it is
+                // provably the in-order sum; else that sum itself, by every wave
+                double sum;
+                if (!block_sum_exact4(se, wv, ln, (double *)kring, (int *)(kring + 32), (int *)(kring + 48), sum))
+                    sum = seq_group_sum(gsum, n_kv / 4, ln);
                 const float inv = (float)(1.0 / sum);
                 for (int c = 0; c < n_ch; ++c) {
                     const int cell = 256 * c + t;
@@ -614,17 +609,9 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                 for (int r = 0; r < KR; ++r) {
                     const int c = c0 + r * TPH;
                     if (c < n_kv && c <= pos) {
-                        if (c == pos) {
-#pragma unroll
-                            for (int i = 0; i < KV4; ++i) kv[r][i] = ((const uint4 *)k16)[i];
-                        } else if (r == 0 && c == t && (KQ_ATTN_EARLY || t < KPF)) {
-#pragma unroll
-                            for (int i = 0; i < KV4; ++i) kv[r][i] = kpre[i];
-                        } else {
-                            const uint4 *kr = (const uint4 *)(a.k_cache + (int64_t)c * kvw + (int64_t)g * HD);
-#pragma unroll
-                            for (int i = 0; i < KV4; ++i) kv[r][i] = kr[i];
-                        }
+                        if (c == pos) attn_k_row_lds(kv[r], k16);
+                        else if (r == 0 && c == t && t < KPF) attn_k_row_regs(kv[r], kpre);
+                        else attn_k_row_global(kv[r], a.k_cache + (int64_t)c * kvw + (int64_t)g * HD);
                     }
                 }
 #pragma unroll
@@ -639,10 +626,12 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                 float s = -INFINITY;
                 if (c <= pos) {
                     uint4 kv[KV4];
+                    // (this site keeps its own lines: with the attn_k_row_* helpers here the
+                    // head_dim-128 fused kernels keep kpre in scratch, 256 VGPRs)
                     if (c == pos) {
 #pragma unroll
                         for (int i = 0; i < KV4; ++i) kv[i] = ((const uint4 *)k16)[i];
-                    } else if (c == t && (KQ_ATTN_EARLY || t < KPF)) {
+                    } else if (c == t && t < KPF) {
 #pragma unroll
                         for (int i = 0; i < KV4; ++i) kv[i] = kpre[i];
                     } else {
@@ -659,7 +648,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         issue_v_rows();
         __syncthreads();
         if (ADIAG(a) == 2) {  // diagnostics: stop after KQ
-            vm_wait<0>();  // (staged V DMAs, vl) land before the wave ends
+            vm_wait<0>();  // (staged V DMAs, KDMA) land before the wave ends
             if (t < HD) out[t] = adiag_finite(__float_as_uint(w[t]) ^ vpre[0][0].x ^ vpre[0][VPF - 1].y);
             return;
         }
@@ -695,17 +684,18 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         for (int c = t; c < n_kv; c += TPH) p16[c] = h2u(f2h_rne(w[c] * inv));
         __syncthreads();
         if (ADIAG(a) == 3) {  // diagnostics: stop after soft_max
-            vm_wait<0>();  // (staged V DMAs, vl) land before the wave ends
+            vm_wait<0>();  // (staged V DMAs, KDMA) land before the wave ends
             if (t < HD) out[t] = adiag_finite((uint32_t)p16[t] ^ vpre[0][0].x ^ vpre[0][VPF - 1].y);
             return;
         }
         }
     }
 
-    // KQV: thread (d, j) -> accumulator j of output d. The V chunks past the prefetched ones
-    // are requested KQ_ATTN_VB iterations at a time before any of them is used (a loop that
+    // ---- 4. KQV: thread (d, j) -> accumulator j of output d, from the V rows in LDS (KDMA), in
+    // batches (PAIR) or one chunk per step (the fused kernels). The V chunks past the prefetched ones
+    // are requested ATTN_VB iterations at a time before any of them is used (a loop that
     // loads and then uses each chunk pays one memory latency per 32 cells: tg1024 -18 %).
-    if (vl) {  // the staged V rows landed (every wave's DMAs); then the new cell patched into
+    if (KDMA) {  // the staged V rows landed (every wave's DMAs); then the new cell patched into
                // them from v16, so the loop below reads LDS only, without per-cell branches
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), seen by the compiler (no stale waits below)
         __syncthreads();
@@ -726,7 +716,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
         const int d = DS > 1 ? ds * RS + vr_l : vr_l;
         const uint16_t *vr = a.v_cache + (int64_t)(g * HD + d) * a.n_ctx;
         uint32_t acc[4] = {};  // lanes 2k, 2k+1 of accumulator j in word k
-        if (PAIR && vl) {  // V rows in LDS (new cell patched): 8 iterations' reads, then their FMAs
+        if constexpr (KDMA) {  // V rows in LDS (new cell patched): 8 iterations' reads, then their FMAs
             const uint8_t *vrow = vlds + vr_l * VSTR + 16 * j;
             const uint8_t *prow = (const uint8_t *)p16 + 16 * j;
             int it = 0;
@@ -738,35 +728,19 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                     pb[k] = *(const uint4 *)(prow + 64 * (it + k));
                 }
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    acc[0] = pk_fma_w(vb[k].x, pb[k].x, acc[0]);
-                    acc[1] = pk_fma_w(vb[k].y, pb[k].y, acc[1]);
-                    acc[2] = pk_fma_w(vb[k].z, pb[k].z, acc[2]);
-                    acc[3] = pk_fma_w(vb[k].w, pb[k].w, acc[3]);
-                }
+                for (int k = 0; k < 8; ++k) attn_fma4(acc, vb[k], pb[k]);
             }
-            for (; it < n_it; ++it) {
-                const uint4 vv = *(const uint4 *)(vrow + 64 * it), pp = *(const uint4 *)(prow + 64 * it);
-                acc[0] = pk_fma_w(vv.x, pp.x, acc[0]);
-                acc[1] = pk_fma_w(vv.y, pp.y, acc[1]);
-                acc[2] = pk_fma_w(vv.z, pp.z, acc[2]);
-                acc[3] = pk_fma_w(vv.w, pp.w, acc[3]);
-            }
+            for (; it < n_it; ++it) attn_fma4(acc, *(const uint4 *)(vrow + 64 * it), *(const uint4 *)(prow + 64 * it));
         } else if constexpr (PAIR) {
             for (int it0 = 0; it0 < n_it; it0 += VB) {
                 uint4 vb[VB];
 #pragma unroll
                 for (int k = 0; k < VB; ++k) {
                     const int it = it0 + k;
-                    if (!vl && it0 == 0 && k < VPF) {
+                    if (it0 == 0 && k < VPF) {
                         vb[k] = vpre[ii][k < VPF ? k : 0];
-                    } else if (VPOST > 0 && it0 == 0 && k < VPF + VPOST) {
-                        vb[k] = vpost[ii][k - VPF < (VPOST > 0 ? VPOST : 1) ? k - VPF : 0];
-                    } else if (EARLYV && !vl && it0 == 0) {
-                        vb[k] = vb0[ii][k < (EARLYV ? VB : 1) ? k : 0];  // requested with the position (it < n_it)
                     } else if (it < n_it) {
-                        vb[k] = vl ? *(const uint4 *)(vlds + vr_l * VSTR + 2 * (32 * it + 8 * j))
-                                   : *(const uint4 *)(vr + 32 * it + 8 * j);
+                        vb[k] = *(const uint4 *)(vr + 32 * it + 8 * j);
                     }
                 }
 #pragma unroll
@@ -774,15 +748,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
                     const int it = it0 + k;
                     if (it < n_it) {
                         const int c0 = 32 * it + 8 * j;
-                        const uint4 pp = *(const uint4 *)(p16 + c0);
-                        uint32_t vw[4] = {vb[k].x, vb[k].y, vb[k].z, vb[k].w};
-                        const uint32_t pw[4] = {pp.x, pp.y, pp.z, pp.w};
-                        if (pos >= c0 && pos < c0 + 8) {  // the new cell: LDS copy
-                            const int l = pos - c0;
-                            vw[l >> 1] = (vw[l >> 1] & (0xffff0000u >> (16 * (l & 1)))) | ((uint32_t)v16[d] << (16 * (l & 1)));
-                        }
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[q] = pk_fma_w(vw[q], pw[q], acc[q]);
+                        attn_fma4(acc, attn_patch_new_cell(vb[k], pos, c0, v16 + d), *(const uint4 *)(p16 + c0));
                     }
                 }
             }
@@ -794,13 +760,11 @@ __device__ __forceinline__ void attn_head(const AttnArgs &a, int h, int t, uint8
 #pragma unroll
                     for (int k = 0; k < VPF; ++k)
                         if (k == it) vv = vpre[ii][k];
-                } else if (VPOST > 0 && it < VPF + VPOST) {
-#pragma unroll
-                    for (int k = 0; k < (VPOST > 0 ? VPOST : 1); ++k)
-                        if (k == it - VPF) vv = vpost[ii][k];
                 } else {
                     vv = *(const uint4 *)(vr + c0);
                 }
+                // (this site keeps its own lines: with attn_patch_new_cell + attn_fma4 here
+                // kq_attn_decode<128, false> grows by 17 instructions)
                 const uint4 pp = *(const uint4 *)(p16 + c0);
                 uint32_t vw[4] = {vv.x, vv.y, vv.z, vv.w};
                 const uint32_t pw[4] = {pp.x, pp.y, pp.z, pp.w};

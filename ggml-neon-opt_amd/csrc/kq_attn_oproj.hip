@@ -222,7 +222,7 @@ KQ_AO_INST(128, Q6_K)
 
 // ------------------------------------------------------------------ host side
 size_t attn_lds16(int hd, int n_ctx) {
-    // kq_ops.hip attn_lds (the per-head layout of attn_head), rounded to 16 B
+    // kq_attn_decode.hip attn_lds (the per-head layout of attn_head), rounded to 16 B
     const size_t gsum = (size_t)(n_ctx / 4) * 8 <= (size_t)hd * 64 ? 0 : (size_t)(n_ctx / 4) * 8;
     const size_t b = (size_t)6 * hd + (size_t)n_ctx * 6 + (size_t)hd * 64 + 16 + gsum;
     return (b + 15) & ~(size_t)15;

@@ -7,7 +7,7 @@
 // fixed LDS ring. Three launches per token tile, the token index in the grid (one token: the
 // decode step; T tokens: a prompt tile, after kq_kv_store):
 //  A kq_attn_stream_scores: workgroup (64-cell chunk, kv group, token): kq_attn_cells' job
-//    (kq_ops.hip) — rope(q) of the group's heads, for the decode step rope(k) / f16(v) into both
+//    (kq_attn_decode.hip) — rope(q) of the group's heads, for the decode step rope(k) / f16(v) into both
 //    caches by the workgroup whose chunk holds the position, vec_dot_f16 * scale per (head, cell
 //    <= pos), -INF past pos — for caches that are a multiple of 32 cells (the last chunk may
 //    hold 32) and any token of a tile.

@@ -278,7 +278,7 @@ __host__ __device__ inline RowsDynLayout rows_dyn_layout(int nb, int tmask, int 
     return L;
 }
 
-// Decode attention block (kq_ops.hip): one workgroup per query head.
+// Decode attention block (kq_attn_decode.hip): one workgroup per query head.
 struct AttnArgs {
     const float *q, *k, *v;       // projections of this token (before rope)
     const int32_t *pos;           // device: the token's position (cache cell)
@@ -293,8 +293,7 @@ struct AttnArgs {
     int no_store;     // prompt batch: the KV cells are already stored (the k/v GEMM's epilogue)
     uint8_t *q8_out;  // prompt batch (kq_attn_prompt_group): also the output rows as Q8L blocks
                       // for the next GEMM (row i's superblock b at (i*nb + b)*304), or null
-    int v_lds;        // kq_attn_decode only, set by launch_attn: the head's V rows are staged in
-                      // LDS by LDS-DMA as soon as the position is known (attn_lds_v bytes)
+    int reserved0;    // unused, written as 0 (keeps the offsets attn_entry reads the struct at)
     int n_tok;        // prompt batch (kq_attn_prompt_group), set by launch_attn_prompt: its tokens
 };
 

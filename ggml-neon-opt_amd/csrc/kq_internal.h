@@ -211,20 +211,25 @@ int launch_rms_norm(const float *x, const float *w, float *y, int64_t n, int64_t
 int launch_binary(int op, const float *a, const float *b, float *y, int64_t n, hipStream_t s,
                   int64_t nb = 0);  // 0 add, 1 mul; b of nb elements repeated (0: nb = n)
 int launch_attn_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
-// long-cache attention workspace (per stream), before any capture; n_tok > 1: a prompt node
-int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok = 1);
 bool attn_prompt_q8_ok(const AttnArgs &a);  // the group kernel can write a.q8_out
 int launch_swiglu(const float *g, const float *u, float *y, int64_t n, hipStream_t s);
 int attn_args_from(const mi355x_attn_desc *d, AttnArgs &a);  // + check_attn
+// pieces the streamed path shares
+size_t attn_prompt_lds(int hd, int n_ctx);
+int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
+
+// ---------------------------------------------------------------- kq_attn_decode.hip
+// The decode attention block: its kernels, their LDS sizing, the dispatch policy, the launch.
+int attn_path(const AttnArgs &a);  // MI355X_ATTN_PATH_*: the kernel launch_attn runs (mi355x_attn_path)
 int launch_attn(const AttnArgs &a, hipStream_t s);
+int attn_impl();              // mi355x_attn_impl's selector
+int attn_impl_set(int impl);  // ... set; returns the previous
 bool attn_group_ok(const AttnArgs &a, int nwaves);      // the one-workgroup-per-kv-group path applies
 size_t attn_group_bytes(const AttnArgs &a, int nwaves);  // its LDS
-int attn_impl();  // mi355x_attn_impl (kq_ops.hip)
-// pieces the streamed path shares
-size_t attn_lds(int hd, int n_ctx);
-size_t attn_prompt_lds(int hd, int n_ctx);
+size_t attn_lds(int hd, int n_ctx);  // the per-head LDS layout (kq_attn_head.h)
+// long-cache attention workspace (per stream), before any capture; n_tok > 1: a prompt node
+int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok = 1);
 void *attn_cells_buffer(size_t bytes, hipStream_t stream, bool may_alloc);
-int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
 
 // ---------------------------------------------------------------- kq_attn_stream.hip
 // Streamed attention for caches of up to kAttnStreamMaxCtx cells (mi355x_attn_stream).

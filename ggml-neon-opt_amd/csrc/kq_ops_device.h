@@ -404,6 +404,10 @@ __device__ __forceinline__ int wave_imin(int v) {
     }
     return v;
 }
+// soft_max's in-order fallback over n LDS doubles, by one whole wave (KQ_SEQ_SUM_WAVE picks the form)
+__device__ __forceinline__ double seq_group_sum(const double *g, int n, int lane) {
+    return KQ_SEQ_SUM_WAVE ? seq_sum_wave(g, n, lane) : seq_sum_lds(g, n);
+}
 // The wave tree alone: the sum and whether it is provably ggml's in-order sum (ok; wave-uniform)
 __device__ __forceinline__ double softmax_group_tree(const double *g, int n, int lane, bool &ok) {
     SumExact se;
@@ -420,7 +424,7 @@ __device__ __forceinline__ double softmax_group_sum(const double *g, int n, int 
     bool ok;
     const double p0 = softmax_group_tree(g, n, lane, ok);
     if (ok) return p0;
-    return KQ_SEQ_SUM_WAVE ? seq_sum_wave(g, n, lane) : seq_sum_lds(g, n);
+    return seq_group_sum(g, n, lane);
 }
 
 }  // namespace kq

@@ -404,7 +404,7 @@ int mi355x_attn_decode(const mi355x_attn_desc *a, void *stream);
 #define MI355X_ATTN_PATH_SPLIT8 3     /* ... over 8 */
 #define MI355X_ATTN_PATH_CELLS 4      /* KQ split over cells: kq_attn_cells + kq_attn_cells_kqv */
 #define MI355X_ATTN_PATH_GROUP 5      /* one workgroup per KV group (MI355X_ATTN_GROUP) */
-#define MI355X_ATTN_PATH_KD1 6        /* experiment builds (KQ_ATTN_KDMA1) */
+/* 6: retired (an experiment build's path); the number stays unused */
 #define MI355X_ATTN_PATH_STREAM 7     /* streamed: kq_attn_stream_scores + _softmax + _kqv (mi355x_attn_stream) */
 int mi355x_attn_path(const mi355x_attn_desc *a);
 /* The same block for a prompt of n_tokens tokens in one graph (llama-bench pp: ggml's

@@ -15,7 +15,7 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 PRELOADED = {
     "_ZN2kq7kq_rowsI": (14, 12),
     "_ZN2kq11kq_rows_dynI": (14, 12),
-    "_ZN2kq14kq_attn_decodeI": (14, 10),
+    "_ZN2kq14kq_attn_decodeI": (14, 8),  # head_dim 64 / 128 x {<=256 cells, batched, 4 slices, 8 slices}
     "_ZN2kq11kq_get_rowsE": (14, 1),
 }
 

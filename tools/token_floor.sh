@@ -5,7 +5,7 @@
 # the attention launches empty (ATTN_DIAG=4), the GEMVs empty (GEMV_DIAG=256), and both:
 # the last is the launch chain's floor (every launch kept, each returning at entry).
 #   build: make -C ggml-neon-opt_amd variant NAME=fdiag VFLAGS="-DKQ_ROWS_DIAG=1 -DKQ_GEMV_DIAG=1 -DKQ_ATTN_DIAG=1"
-#          plus kq_ops.hip with the same flags (tools/token_floor.sh's header in DESIGN §7)
+#          plus kq_ops.hip and kq_attn_decode.hip with the same flags (tools/token_floor.sh's header in DESIGN §7)
 # LIST="tag lib knob=v ..." lines replace the default variants (e.g. the attention's
 # diagnostic stops: ATTN_DIAG=5 q/k/v + rope only, 1 + the cache loads, 2 + KQ, 3 + soft_max).
 set -u
