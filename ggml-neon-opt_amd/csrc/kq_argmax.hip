@@ -1,0 +1,224 @@
+// kq_argmax.hip — greedy sampling on the device: the argmax of an f32 vector (the logits)
+// in ONE launch over several workgroups, and, in its step-inputs form, the next decode
+// token's inputs (token id, position, the position's rope row) written where the decode
+// graph reads them, so the same captured graph is replayed token after token with no host
+// copy and no synchronization in between (LlamaDecoder.generate).
+//
+// Semantics (llama.cpp's greedy sampler; numpy.argmax(where(isnan(x), -inf, x))): the
+// smallest index whose value equals the maximum of the non-NaN entries under IEEE
+// comparison. -0.0 == +0.0, +-inf are ordinary values, a NaN never wins, all NaN -> 0; the
+// result is always in [0, n). Exact: the order is carried by an integer key, no arithmetic.
+//
+// Key. A value's bits become an ordered 32-bit key (NaN -> 0, below every number; -0.0 ->
+// +0.0 first; negative: all bits flipped, else the sign bit set), and (key << 32) | ~index is
+// a 64-bit word whose unsigned maximum is the answer: the larger value, then the smaller index.
+//
+// Decomposition. Workgroup s reduces slice [s * slice, min(n, (s + 1) * slice)) (16-B loads;
+// the vector's last, partial 16 bytes by scalar loads): each lane over its vectors in index
+// order, DPP within a row of 16 lanes, the lane swaps across rows, LDS across the waves.
+// Hand-off (kq_attn_oproj's; MI355X_MICROARCH.md, valid forms, row 1): the workgroup's word
+// is stored write-through (sc1) by one lane, that wave drains it (vmcnt(0)), workgroup
+// barrier, ONE agent-scope add on the counter; the workgroup whose add returns wgs - 1 reads
+// every word with sc1 loads behind a workgroup barrier, reduces them the same way and writes
+// the result. It stores 0 back to the counter, so every launch and every graph replay
+// starts at 0. No workgroup waits for another: nothing can deadlock, placement only changes speed.
+#include <string.h>
+
+#include "kq_internal.h"
+#include "kq_rows_device.h"
+
+namespace kq {
+
+namespace {
+
+constexpr int kArgmaxThreads = 256;
+
+struct ArgmaxArgs {
+    const float *x;
+    int n, slice, wgs;
+    unsigned long long *part;  // workspace: one word per workgroup ...
+    uint32_t *cnt;             // ... behind the arrival counter
+    int32_t *out;              // plain form: [1]; step form: the decoder's input block [2 + hd]
+    // step-inputs form (pos != null): out[0] = token, out[1] = *pos + 1, out[2 ..] = the bits of
+    // table row *pos + 1 where it exists, hist[*pos + 1] = token where it exists
+    const int32_t *pos;
+    const uint32_t *table;
+    int32_t *hist;
+    uint32_t rows, n_hist;
+    int hd;
+};
+
+__device__ __forceinline__ uint32_t ord_key(uint32_t b) {
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;  // NaN: below -inf's key (0x007fffff)
+    if (b == 0x80000000u) b = 0u;                     // -0.0 == +0.0
+    return b & 0x80000000u ? ~b : b | 0x80000000u;
+}
+
+__device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)v, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi =
+        (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(v >> 32), (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// The maximum over the wave, in every lane (every lane active): row16_reduce's DPP steps,
+// then the rows by the lane swaps (sblk_reduce's, kq_rows_device.h)
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    v = max_u64(v, dpp_u64<0xB1>(v));
+    v = max_u64(v, dpp_u64<0x4E>(v));
+    v = max_u64(v, dpp_u64<0x141>(v));
+    v = max_u64(v, dpp_u64<0x140>(v));
+    uint32_t la, lb, ha, hb;
+    swap_rows16((uint32_t)v, la, lb), swap_rows16((uint32_t)(v >> 32), ha, hb);
+    v = max_u64(((unsigned long long)ha << 32) | la, ((unsigned long long)hb << 32) | lb);
+    swap_rows32((uint32_t)v, la, lb), swap_rows32((uint32_t)(v >> 32), ha, hb);
+    return max_u64(((unsigned long long)ha << 32) | la, ((unsigned long long)hb << 32) | lb);
+}
+
+// ... over the workgroup's 4 waves, in every thread; `lds`: 4 words no other reduction uses
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long *lds) {
+    v = wave_max_u64(v);
+    if (((int)threadIdx.x & 63) == 0) lds[(int)threadIdx.x >> 6] = v;
+    __syncthreads();
+    return max_u64(max_u64(lds[0], lds[1]), max_u64(lds[2], lds[3]));
+}
+
+__global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) {
+    __shared__ unsigned long long red[2][4];
+    __shared__ int flag;
+    const int t = (int)threadIdx.x;
+    const int lo = (int)blockIdx.x * p.slice;  // (lo < n: wgs = ceil(n / slice))
+    const int hi = p.n - lo < p.slice ? p.n : lo + p.slice;
+
+    // ---- this lane's vectors lo/4 + t, + 256, ... in index order: a strict > keeps the first
+    uint32_t bestk = 0u, besti = 0xffffffffu;  // (no entry: the word 0, below every entry's)
+    const int vfull = hi >> 2;  // vectors [lo/4, vfull) are whole
+    for (int v0 = (lo >> 2) + t; v0 < vfull; v0 += 4 * kArgmaxThreads) {
+        u32x4 r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (v0 + j * kArgmaxThreads < vfull) r[j] = *(const u32x4 *)(p.x + 4 * (int64_t)(v0 + j * kArgmaxThreads));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (v0 + j * kArgmaxThreads >= vfull) break;
+            const uint32_t i0 = 4u * (uint32_t)(v0 + j * kArgmaxThreads);
+            const uint32_t k0 = ord_key(r[j].x), k1 = ord_key(r[j].y), k2 = ord_key(r[j].z), k3 = ord_key(r[j].w);
+            if (k0 > bestk) bestk = k0, besti = i0;
+            if (k1 > bestk) bestk = k1, besti = i0 + 1;
+            if (k2 > bestk) bestk = k2, besti = i0 + 2;
+            if (k3 > bestk) bestk = k3, besti = i0 + 3;
+        }
+    }
+    // the vector's last n % 4 entries (the last slice only), after every whole vector of the slice
+    if (t == kArgmaxThreads - 1)
+        for (int i = 4 * vfull; i < hi; ++i) {
+            const uint32_t k = ord_key(__float_as_uint(p.x[i]));
+            if (k > bestk) bestk = k, besti = (uint32_t)i;
+        }
+    unsigned long long w = block_max_u64(((unsigned long long)bestk << 32) | (uint32_t)~besti, red[0]);
+
+    // ---- hand-off: the word write-through, drained, barrier, one add; the last arriver goes on
+    if (t == 0) __hip_atomic_store(p.part + blockIdx.x, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+        const uint32_t old = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = old == (uint32_t)(p.wgs - 1);
+        if (last) __hip_atomic_store(p.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch starts at 0
+        flag = last;
+    }
+    __syncthreads();
+    if (!flag) return;
+
+    // ---- the last arriver: every workgroup's word (wgs <= 256: one per thread), sc1 loads
+    w = t < p.wgs ? __hip_atomic_load(p.part + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    w = block_max_u64(w, red[1]);
+    const uint32_t idx = ~(uint32_t)w;
+    const int32_t token = idx < (uint32_t)p.n ? (int32_t)idx : 0;  // (all NaN: the word 0)
+    if (!p.pos) {
+        if (t == 0) p.out[0] = token;
+        return;
+    }
+    // step inputs. pos may be out[1]: every thread's load of it has returned (the barrier alone
+    // waits for no counter) before one of them writes it
+    uint32_t next = (uint32_t)*p.pos + 1u;
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(next)::"memory");
+    __syncthreads();
+    if (t == 0) {
+        p.out[0] = token;
+        p.out[1] = (int32_t)next;
+        if (next < p.n_hist) p.hist[next] = token;
+    }
+    if (next < p.rows)
+        for (int k = t; k < p.hd; k += kArgmaxThreads) p.out[2 + k] = (int32_t)p.table[(size_t)next * p.hd + k];
+}
+
+constexpr int kArgmaxSlice = 1024;  // entries per workgroup up to 256 workgroups (ARGMAX_SLICE: A/B)
+constexpr int kArgmaxMaxWgs = 256;  // the last arriver reads one word per thread
+constexpr size_t kArgmaxCounterBytes = 128;  // the counter on a line of its own, then the words
+
+}  // namespace
+
+int argmax_plan(int64_t n, int *workgroups, int64_t *slice) {
+    if (n < 1 || n > kArgmaxMaxN) return MI355X_E_INVAL;
+    int64_t s = (int64_t)knob(KNOB_ARGMAX_SLICE);
+    s = s > 0 ? (s + 3) & ~(int64_t)3 : kArgmaxSlice;
+    if ((n + s - 1) / s > kArgmaxMaxWgs) s = ((n + kArgmaxMaxWgs - 1) / kArgmaxMaxWgs + 3) & ~(int64_t)3;
+    if (workgroups) *workgroups = (int)((n + s - 1) / s);
+    if (slice) *slice = s;
+    return MI355X_OK;
+}
+
+size_t argmax_workspace(int64_t n) {
+    int wgs = 0;
+    if (argmax_plan(n, &wgs, nullptr) != MI355X_OK) return 0;
+    // (the words of every split a knob can select: the size depends on n alone)
+    return kArgmaxCounterBytes + 8 * (size_t)(n < kArgmaxMaxWgs ? n : kArgmaxMaxWgs);
+}
+
+int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *step, void *ws, size_t ws_size,
+                  hipStream_t stream) {
+    int wgs = 0;
+    int64_t slice = 0;
+    if (!x || !out || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
+    if (step && (!step->pos || !step->table || !step->hist || step->hd <= 0 || step->rows < 0 || step->n_hist < 0))
+        return MI355X_E_INVAL;
+    if (!ws || ((uintptr_t)ws & 7u) || ws_size < argmax_workspace(n)) return MI355X_E_WORKSPACE;
+    if (!device_ok()) return MI355X_E_NODEVICE;
+    ArgmaxArgs p;
+    memset(&p, 0, sizeof(p));
+    p.x = x;
+    p.n = (int)n;
+    p.slice = (int)slice;
+    p.wgs = wgs;
+    p.cnt = (uint32_t *)ws;
+    p.part = (unsigned long long *)((uint8_t *)ws + kArgmaxCounterBytes);
+    p.out = out;
+    if (step) {
+        p.pos = step->pos;
+        p.table = (const uint32_t *)step->table;
+        p.hist = step->hist;
+        p.rows = (uint32_t)step->rows;
+        p.n_hist = (uint32_t)step->n_hist;
+        p.hd = step->hd;
+    }
+    return timed_launch("kq::kq_argmax", (double)n * 4.0, kq_argmax, dim3((unsigned)wgs), dim3(kArgmaxThreads), 0, stream,
+                        p);
+}
+
+}  // namespace kq
+
+extern "C" {
+
+int mi355x_argmax_plan(int64_t n, int *workgroups, int64_t *slice) { return kq::argmax_plan(n, workgroups, slice); }
+
+size_t mi355x_argmax_workspace_size(int64_t n) { return kq::argmax_workspace(n); }
+
+int mi355x_argmax(const float *x, int64_t n, int32_t *out, void *workspace, size_t workspace_size, void *stream) {
+    return kq::launch_argmax(x, n, out, nullptr, workspace, workspace_size, (hipStream_t)stream);
+}
+
+}  // extern "C"

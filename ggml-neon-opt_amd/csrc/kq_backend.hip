@@ -51,6 +51,8 @@ struct mi355x_backend {
     void *fx = nullptr;      // its arrival counters (zeroed at allocation) and records
     size_t fx_size = 0;
     int fx_nsb = 0;          // the superblock count the counters' rounds are aligned to
+    void *am = nullptr;      // the ARGMAX nodes' arrival counter and partials (kq_argmax.hip), zeroed at
+    size_t am_size = 0;      // allocation; every launch leaves them ready for the next
     bool layer_engine = false;  // each decode layer as one persistent launch (kq_layer.hip)
     uint32_t *ly_sync = nullptr;  // the persistent layers' counter blocks (zeroed at allocation), then err
     int ly_blocks = 0;
@@ -333,6 +335,16 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             a.rope_row = t->src[6]->ne[1] == 1 ? 1 : 0;  // the position's row, staged with pos
             return mi355x_attn_decode(&a, st);
         }
+        case MI355X_OP_ARGMAX: {
+            const int64_t n = t->src[0]->ne[0];
+            if (t->op_params[0] == 0)
+                return kq::launch_argmax((const float *)t->src[0]->data, n, (int32_t *)t->data, nullptr, b->am,
+                                         b->am_size, st);
+            const mi355x_tensor *tab = t->src[2];
+            const kq::ArgmaxStep step = {(const int32_t *)t->src[1]->data, (const float *)tab->data,
+                                         (int32_t *)t->src[3]->data, tab->ne[1], t->src[3]->ne[0], (int)tab->ne[0]};
+            return kq::launch_argmax((const float *)t->src[0]->data, n, (int32_t *)t->data, &step, b->am, b->am_size, st);
+        }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(t, d);
@@ -555,6 +567,25 @@ int ensure_attn_oproj_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, con
     return MI355X_OK;
 }
 
+// the ARGMAX nodes' counter and partials: sized for the longest vector, zeroed when (re)allocated.
+// The nodes of a graph run one after the other on the backend stream, so they share it.
+int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
+    size_t need = 0;
+    for (int i = 0; i < n_nodes; ++i)
+        if (nodes[i]->op == MI355X_OP_ARGMAX) need = std::max(need, kq::argmax_workspace(nodes[i]->src[0]->ne[0]));
+    if (need <= b->am_size) return MI355X_OK;
+    hipStreamSynchronize(b->stream);
+    drop_graph(b);
+    if (b->am) hipFree(b->am);
+    b->am = nullptr;
+    b->am_size = 0;
+    if (hipMalloc(&b->am, need) != hipSuccess) return MI355X_E_WORKSPACE;
+    b->am_size = need;
+    if (hipMemsetAsync(b->am, 0, need, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
+        return MI355X_E_WORKSPACE;
+    return MI355X_OK;
+}
+
 // The persistent layers' counter blocks: one per Layer launch, zeroed whenever they are
 // (re)allocated. A launch's counters are monotonic over its launches with ITS producer
 // counts, so a block is keyed by (layer index in the graph, producers per edge and shard):
@@ -755,6 +786,7 @@ void mi355x_backend_free(mi355x_backend_t b) {
     drop_graph(b);
     if (b->workspace) hipFree(b->workspace);
     if (b->fx) hipFree(b->fx);
+    if (b->am) hipFree(b->am);
     if (b->ly_sync) hipFree(b->ly_sync);
     for (auto &t : b->ly_tabs)
         if (t.dev) hipFree(t.dev);
@@ -923,6 +955,7 @@ int mi355x_backend_graph_compute(mi355x_backend_t b, mi355x_tensor *const *nodes
     if (rc) return rc;
     const std::vector<Launch> launches = kq::plan_launches(plan_opts(b), nodes, n_nodes);
     if ((rc = ensure_attn_oproj_buffer(b, nodes, launches))) return rc;
+    if ((rc = ensure_argmax_buffer(b, nodes, n_nodes))) return rc;
     if ((rc = ensure_layer_blocks(b, launches))) return rc;
     if ((rc = ensure_layer_tables(b, launches))) return rc;
     if ((rc = reserve_attn_cells(b, nodes, launches))) return rc;

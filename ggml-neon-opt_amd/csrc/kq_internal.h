@@ -43,6 +43,7 @@ enum Knob {
     KNOB_GEMV_SHORT,       // kq_rows short-stream form where the plan allows it (1); 0: the generic form (A/B)
     KNOB_ATTN_STREAM,      // 0 / 1 / 2: overrides mi355x_attn_stream's mode (-1: the selector's own value)
     KNOB_ATTN_STREAM_TILE, // streamed prompt attention: tokens per tile (0: by the workspace cap)
+    KNOB_ARGMAX_SLICE,     // kq_argmax: entries per workgroup (0: kArgmaxSlice; A/B, and the tests of the longer slices)
     KNOB_COUNT
 };
 double knob(Knob k);
@@ -255,6 +256,25 @@ size_t attn_oproj_buffer(int hd, int n_head, int n_head_kv, int n_ctx, int type,
 int launch_attn_oproj(const AttnArgs &a, int type, const void *w, int64_t n_rows, size_t row_stride, const float *res,
                       float *y, uint8_t *buf, size_t buf_size, hipStream_t stream);
 size_t attn_lds16(int hd, int n_ctx);  // attn_head's LDS per head, 16-B multiple (kq_attn_oproj.hip)
+
+// ---------------------------------------------------------------- kq_argmax.hip
+// The argmax of an f32 vector in one launch (greedy sampling). argmax_plan is the one place
+// that decides the split (mi355x_argmax_plan); argmax_workspace: the bytes of the arrival
+// counter and the workgroups' words (zeroed once by the owner, left ready by every launch).
+// step: the step-inputs form (the ARGMAX node's op_params[0] == 1): `out` is the decoder's
+// input block [2 + hd] and receives the token, *pos + 1 and the rope row of that position.
+constexpr int64_t kArgmaxMaxN = 1 << 24;
+struct ArgmaxStep {
+    const int32_t *pos;   // may be out + 1
+    const float *table;   // [rows][hd]
+    int32_t *hist;        // [n_hist]
+    int64_t rows, n_hist;
+    int hd;
+};
+int argmax_plan(int64_t n, int *workgroups, int64_t *slice);
+size_t argmax_workspace(int64_t n);
+int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *step, void *ws, size_t ws_size,
+                  hipStream_t stream);
 
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from

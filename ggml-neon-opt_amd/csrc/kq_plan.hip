@@ -637,6 +637,24 @@ bool supports_op(const mi355x_tensor *op) {
             return contig_f32(op) && op->ne[0] == (int64_t)nh * hd && op->ne[1] == T &&
                    (T == 1 || op->nb[1] == (size_t)nh * hd * 4);
         }
+        case MI355X_OP_ARGMAX: {
+            // a packed, 16-B aligned f32 vector of mi355x_argmax's sizes -> I32 [1]; the
+            // step-inputs form: pos [1], the rope table [hd, rows], the history -> I32 [2 + hd]
+            const mi355x_tensor *x = op->src[0];
+            if (!x || x->ne[0] < 1 || x->ne[0] > kArgmaxMaxN || !f32_vec(x, x->ne[0], true)) return false;
+            if (op->type != MI355X_TYPE_I32 || !op->data || op->nb[0] != 4 || nelem(op) != op->ne[0]) return false;
+            if (op->op_params[0] == 0) return op->ne[0] == 1;
+            if (op->op_params[0] != 1) return false;
+            const mi355x_tensor *pos = op->src[1], *tab = op->src[2], *hist = op->src[3];
+            auto i32_vec = [](const mi355x_tensor *t) {
+                return t && t->type == MI355X_TYPE_I32 && t->data && t->nb[0] == 4 && t->ne[0] >= 1 && nelem(t) == t->ne[0];
+            };
+            if (!i32_vec(pos) || pos->ne[0] != 1 || !i32_vec(hist) || hist->ne[0] > 0x7fffffff) return false;
+            if (!contig_f32(tab) || tab->ne[0] < 1 || tab->ne[1] < 1 || tab->ne[1] > 0x7fffffff || tab->ne[2] != 1 ||
+                tab->ne[3] != 1 || tab->nb[1] != (size_t)tab->ne[0] * 4)
+                return false;
+            return op->ne[0] == 2 + tab->ne[0];
+        }
         default:
             return false;
     }

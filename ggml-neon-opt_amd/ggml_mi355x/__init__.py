@@ -26,6 +26,8 @@ MAX_FUSED = 4
 OP_NONE, OP_MUL_MAT, OP_GET_ROWS, OP_RMS_NORM, OP_MUL, OP_ADD, OP_SWIGLU, OP_ROPE, OP_ATTN_DECODE, OP_ALL_GATHER, \
     OP_ALL_REDUCE = range(11)
 OP_ATTN_BATCH = 11
+OP_ARGMAX = 12  # op_params[0]: ARGMAX_PLAIN / ARGMAX_STEP_INPUTS
+ARGMAX_PLAIN, ARGMAX_STEP_INPUTS = 0, 1
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -70,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_attn_batch", "mi355x_attn_batch_path",
     "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
     "mi355x_debug_rows_plan",
+    "mi355x_argmax_plan", "mi355x_argmax_workspace_size", "mi355x_argmax",
 )
 
 
@@ -248,6 +251,13 @@ def lib():
     L.mi355x_attn_batch.restype = i32
     L.mi355x_attn_batch_path.argtypes = [ctypes.POINTER(AttnBatchDesc)]
     L.mi355x_attn_batch_path.restype = i32
+    if hasattr(L, "mi355x_argmax"):  # (an older library under MI355X_LIB, A/B runs: without it)
+        L.mi355x_argmax_plan.argtypes = [i64, ctypes.POINTER(i32), ctypes.POINTER(i64)]
+        L.mi355x_argmax_plan.restype = i32
+        L.mi355x_argmax_workspace_size.argtypes = [i64]
+        L.mi355x_argmax_workspace_size.restype = sz
+        L.mi355x_argmax.argtypes = [vp, i64, vp, vp, sz, vp]
+        L.mi355x_argmax.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -514,7 +524,7 @@ def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=No
 DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_SMALL_MB", "GEMV_WPC",
                "GEMV_SMALL_WG", "GEMV_FQMAX", "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY",
                "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT", "ATTN_STREAM",
-               "ATTN_STREAM_TILE")
+               "ATTN_STREAM_TILE", "ARGMAX_SLICE")
 
 
 def debug_knob(name, value=float("nan")):
@@ -708,6 +718,48 @@ def attn_batch_path(n_ctx, n_head, n_head_kv, head_dim, n_kv):
                  base + (1 << 14), n_ctx, n_head, n_head_kv, head_dim, 1.0 / float(head_dim) ** 0.5, 0)
     d = AttnBatchDesc(a, base + 128, TYPE_I32, base + 256, TYPE_F32, 4 * n_kv, n_kv, 1)
     return int(lib().mi355x_attn_batch_path(ctypes.byref(d)))
+
+
+def _argmax_lib():
+    L = lib()
+    if not hasattr(L, "mi355x_argmax"):
+        raise Mi355xError(f"{LIB_PATH} has no mi355x_argmax (a library built before it)")
+    return L
+
+
+def argmax_plan(n):
+    """(workgroups, slice) of mi355x_argmax over n entries (mi355x_argmax_plan: the host's choice,
+    no device): slice s is [s * slice, min(n, (s + 1) * slice)); or the error code."""
+    wgs, slice_ = ctypes.c_int(0), ctypes.c_int64(0)
+    rc = int(_argmax_lib().mi355x_argmax_plan(n, ctypes.byref(wgs), ctypes.byref(slice_)))
+    return (wgs.value, slice_.value) if rc == 0 else rc
+
+
+def argmax_workspace_size(n):
+    """Bytes of mi355x_argmax's workspace for n entries (0: n outside 1 .. 2^24)."""
+    return int(_argmax_lib().mi355x_argmax_workspace_size(n))
+
+
+def argmax(x, out=None, workspace=None, stream=None):
+    """Greedy sampling (mi355x_argmax): the smallest index of the maximum of the non-NaN entries
+    of x, a contiguous f32 cuda vector, as an int32 cuda tensor [1] (no synchronization).
+    workspace: a uint8 cuda tensor of argmax_workspace_size(n) bytes, zeroed once by its owner and
+    reusable call after call on one stream; None: a fresh zeroed one."""
+    torch = _torch()
+    _require_device()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+        raise Mi355xError("argmax: x must be a contiguous float32 cuda vector")
+    n = x.numel()
+    out = torch.empty(1, dtype=torch.int32, device=x.device) if out is None else out
+    if not (out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1):
+        raise Mi355xError("argmax: out must be an int32 cuda tensor")
+    if workspace is None:
+        workspace = torch.zeros(argmax_workspace_size(n) or 1, dtype=torch.uint8, device=x.device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
+    _check(_argmax_lib().mi355x_argmax(x.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       _stream(stream)), "mi355x_argmax")
+    return out
 
 
 def block_partials(type_, w, K, q8_row, stream=None):

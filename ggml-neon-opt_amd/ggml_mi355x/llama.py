@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
+from . import (ARGMAX_STEP_INPUTS, FLAG_OUTPUT, OP_ADD, OP_ARGMAX, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
                OP_MUL_MAT,
                OP_RMS_NORM,
                OP_SWIGLU, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table)
@@ -459,8 +459,8 @@ class LlamaDecoder:
             raise Mi355xError(f"graph_compute failed ({rc})")
         return g["logits"]
 
-    def step(self, token: int, pos: int, use_graph: bool = True):
-        """Enqueue one token (no synchronization); returns the device logits tensor."""
+    def _stage_inputs(self, token: int, pos: int):
+        """(token, pos, the position's rope row) from a pinned slot into the input block."""
         if not 0 <= pos < self.n_ctx:
             raise Mi355xError(f"position {pos} outside the KV cache (n_ctx {self.n_ctx})")
         if not 0 <= token < self.hp["n_vocab"]:
@@ -479,7 +479,84 @@ class LlamaDecoder:
         rc = L.mi355x_backend_set_tensor(self.b.h, self.inp.data_ptr(), hp, 4 * row.numel())
         if rc:
             raise Mi355xError(f"set_tensor failed ({rc})")
+        return L
+
+    def step(self, token: int, pos: int, use_graph: bool = True):
+        """Enqueue one token (no synchronization); returns the device logits tensor."""
+        L = self._stage_inputs(token, pos)
         rc = L.mi355x_backend_graph_compute(self.b.h, self._arr, len(self.nodes), 1 if use_graph else 0)
         if rc:
             raise Mi355xError(f"graph_compute failed ({rc})")
         return self.logits
+
+    # ------------------------------------------------------------ greedy generation on the device
+    def _generate_graph(self):
+        """The decode token's nodes plus one step-inputs ARGMAX on the logits: it ends the token
+        by writing the next one's (token, pos, rope row) into the input block and the token into
+        self.history[pos + 1], so the one captured graph is replayed with no host copy."""
+        import torch
+        g = getattr(self, "_gen", None)
+        if g is not None:
+            return g
+        hd = self.hp["head_dim"]
+        self.history = torch.zeros(self.n_ctx, dtype=torch.int32, device=self.inp.device)
+        srcs = [self.nodes[-1],
+                make_tensor(TYPE_I32, 1, 1, self.pos.data_ptr()),
+                make_tensor(TYPE_F32, hd, self.n_ctx, self.table.data_ptr()),
+                make_tensor(TYPE_I32, self.n_ctx, 1, self.history.data_ptr())]
+        am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_ARGMAX, srcs=srcs,
+                         op_params=[ARGMAX_STEP_INPUTS], flags=FLAG_OUTPUT)
+        nodes = self.nodes + [am]
+        g = dict(nodes=nodes, keep=srcs + [am],
+                 arr=(ctypes.POINTER(type(am)) * len(nodes))(*[ctypes.pointer(n) for n in nodes]),
+                 host=torch.zeros(self.n_ctx + 1, dtype=torch.int32).pin_memory())
+        self._gen = g
+        torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
+        return g
+
+    def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True):
+        """Greedy decoding of n tokens at positions pos .. pos + n - 1, starting from `token` at
+        `pos`: returns the generated tokens as a list of ints (the token picked after position p
+        is the argmax of that step's logits, mi355x_argmax's rule). The inputs are staged from the
+        host once; then the graph runs `chunk` times back to back, each step's ARGMAX node staging
+        the next, and only after a chunk the host synchronizes and reads its tokens with one copy.
+        eos: stop at the first such token, which is returned as the last one (the device may have
+        run on to the end of that chunk: its later cells and history entries are then written
+        too). A following step() works as ever: it restages the whole input block."""
+        if self.split is not None:
+            raise Mi355xError("generate runs on one GPU (no row split)")
+        if n < 0 or chunk < 1:
+            raise Mi355xError(f"generate: n {n} and chunk {chunk} must be >= 0 and >= 1")
+        if not 0 <= pos < self.n_ctx or n > self.n_ctx - pos:
+            raise Mi355xError(f"generate: {n} tokens from position {pos} outside the KV cache (n_ctx {self.n_ctx})")
+        if n == 0:
+            return []
+        g = self._generate_graph()
+        L = self._stage_inputs(token, pos)
+        host, out, done = g["host"], [], 0
+        while done < n:
+            c = min(chunk, n - done)
+            for _ in range(c):
+                rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
+                if rc:
+                    raise Mi355xError(f"graph_compute failed ({rc})")
+            # the chunk's tokens: history[p + 1] for the step at p; the step on the last cell has
+            # no history entry, its token is the input block's
+            lo, hi = pos + done + 1, pos + done + c + 1
+            in_hist = min(hi, self.n_ctx) - lo
+            if in_hist > 0:
+                rc = L.mi355x_backend_get_tensor(self.b.h, host[lo:].data_ptr(), self.history[lo:].data_ptr(),
+                                                 4 * in_hist)
+                if rc:
+                    raise Mi355xError(f"get_tensor failed ({rc})")
+            if hi > self.n_ctx:
+                rc = L.mi355x_backend_get_tensor(self.b.h, host[self.n_ctx:].data_ptr(), self.inp.data_ptr(), 4)
+                if rc:
+                    raise Mi355xError(f"get_tensor failed ({rc})")
+            self.b.synchronize()
+            for t in host[lo:hi].tolist():
+                out.append(t)
+                if eos is not None and t == eos:
+                    return out
+            done += c
+        return out

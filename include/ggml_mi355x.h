@@ -478,6 +478,25 @@ int mi355x_attn_batch(const mi355x_attn_batch_desc *d, void *stream);
  * token), or the MI355X_E_* mi355x_attn_batch would return. No launch, no device access. */
 int mi355x_attn_batch_path(const mi355x_attn_batch_desc *d);
 
+/* Greedy sampling: *out = the smallest index i whose x[i] equals the maximum of the non-NaN
+ * entries of x[0 .. n) under IEEE comparison (llama.cpp's greedy sampler;
+ * numpy.argmax(where(isnan(x), -inf, x))). Ties go to the smallest index, -0.0 == +0.0, +-inf
+ * are ordinary values, a NaN entry never wins, all NaN gives 0; the result is always in [0, n).
+ * Exact, no tolerance. (ggml's own GGML_OP_ARGMAX leaves ties to the backend [U]: the ggml-graph
+ * lowering does not map it here.) One launch over several workgroups (csrc/kq_argmax.hip): each
+ * reduces a contiguous slice, the workgroup that arrives last combines the slices' results.
+ * mi355x_argmax_plan: the split for n entries, no device: slice s is [s * slice, min(n,
+ * (s + 1) * slice)), the slices cover [0, n) exactly, slice % 4 == 0; MI355X_E_INVAL outside
+ * 1 <= n <= 2^24. mi355x_argmax_workspace_size: the bytes of the workgroups' results and the
+ * arrival counter (0 for an n outside the range). The caller owns the workspace (8-B aligned)
+ * and zeroes it once before the first call; every call leaves it ready for the next; two calls
+ * that can run concurrently must not share one. x: contiguous, 16-B aligned. Returns
+ * MI355X_E_INVAL (null or misaligned x, null out, n outside the range), MI355X_E_WORKSPACE
+ * (missing or too small) or MI355X_E_NODEVICE, in that order. */
+int mi355x_argmax_plan(int64_t n, int *workgroups, int64_t *slice);
+size_t mi355x_argmax_workspace_size(int64_t n);
+int mi355x_argmax(const float *x, int64_t n, int32_t *out, void *workspace, size_t workspace_size, void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -523,12 +542,23 @@ int mi355x_attn_batch_path(const mi355x_attn_batch_desc *d);
  *                (captured in the hipGraph). The exchange step of the K-split ("Megatron")
  *                pairing of SURVEY.md §8e: o-proj and ffn_down split along K at 256-element
  *                superblock boundaries, 2 collectives per layer. The sum re-associates the
- *                row's fp32 chain: within SURVEY.md §8c's fp32 bound, not bit-exact. */
+ *                row's fp32 chain: within SURVEY.md §8c's fp32 bound, not bit-exact.
+ *   ARGMAX       mi355x_argmax of src0, a packed f32 vector of 1 .. 2^24 entries, 16-B aligned;
+ *                one launch, never fused or elided; its counter and partials belong to the
+ *                backend. op_params[0] = 0: -> I32 [1], the index. op_params[0] = 1, the
+ *                step-inputs form (greedy decoding without the host, LlamaDecoder.generate):
+ *                src1 I32 pos [1] (may be dst + 1), src2 f32 rope table [head_dim, rows], src3
+ *                I32 history [n_hist] -> I32 [2 + head_dim], the decode graph's input block:
+ *                dst[0] = the index, dst[1] = pos + 1, dst[2 ..] = the bits of table row
+ *                pos + 1 if pos + 1 < rows (else left alone), history[pos + 1] = the index if
+ *                pos + 1 < n_hist (unsigned compares). pos + 1 is written even at the end of
+ *                the cache: a further replay meets ATTN_DECODE's position outside the cache
+ *                (NaN output, caches untouched). */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
-    MI355X_OP_ATTN_BATCH = 11,
+    MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */

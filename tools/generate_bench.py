@@ -1,0 +1,168 @@
+"""Greedy generation on the device against the loops on the host, on one box, interleaved: the
+bench's TinyLlama-1.1B Q4_K_M decode token (synthetic weights of the real shapes), 128 tokens
+after 8 warm-up tokens from an empty cache, wall time between two synchronizations.
+
+  a  step loop with tokens known beforehand (bench.py's headline path)
+  b  LlamaDecoder.generate (the ARGMAX node stages the next token on the device)
+  c  what a user wrote before generate: step, synchronize, logits to the host, numpy argmax
+
+Prints one JSON line: ms per token of every round, the run-to-run spread of (a) (max - min over
+the rounds), the gate (median c - median b > that spread), b against a, and kq_argmax's own
+launch time (event timing, the vector written by the launch just before) at 32000 and 128256
+entries for every --slices value (ARGMAX_SLICE; 0: the library's default).
+
+    python tools/generate_bench.py [--rounds 5] [--variants a,b,c] [--chunk 32]
+                                   [--slices 0,512,1024,2048,4096]
+
+`in_token_us`: the launches of one eager generated token by event timing (kq_argmax behind the
+head GEMV that wrote its logits, and the whole token's launches summed).
+
+With an older library under MI355X_LIB only --variants a runs (no generate in it).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "ggml-neon-opt_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+import ggml_mi355x as g  # noqa: E402
+
+WARM, STEPS = 8, 128
+
+
+def timed(be, fn):
+    be.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    be.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / STEPS
+
+
+def run_a(tk, be):
+    tk.dec.reset()
+    torch.cuda.synchronize()
+    for i in range(WARM):
+        tk.dec.step(tk.tokens[i], i)
+
+    def body():
+        for i in range(WARM, WARM + STEPS):
+            tk.dec.step(tk.tokens[i], i)
+    return timed(be, body)
+
+
+def run_b(tk, be, chunk=32):
+    tk.dec.reset()
+    torch.cuda.synchronize()
+    tok = tk.dec.generate(tk.tokens[0], 0, WARM)[-1]
+    return timed(be, lambda: tk.dec.generate(tok, WARM, STEPS, chunk=chunk))
+
+
+def host_loop(tk, be, tok, pos, n):
+    for p in range(pos, pos + n):
+        tk.dec.step(tok, p)
+        be.synchronize()
+        x = tk.dec.logits.cpu().numpy()
+        tok = int(np.argmax(np.where(np.isnan(x), -np.inf, x)))
+    return tok
+
+
+def run_c(tk, be):
+    tk.dec.reset()
+    torch.cuda.synchronize()
+    tok = host_loop(tk, be, tk.tokens[0], 0, WARM)
+    return timed(be, lambda: host_loop(tk, be, tok, WARM, STEPS))
+
+
+def in_token_us(tk, be, reps=20):
+    """Event times of one eager generated token's launches: kq_argmax's median and the token's sum."""
+    tk.dec.reset()
+    torch.cuda.synchronize()
+    tk.dec.generate(tk.tokens[0], 0, 2, use_graph=False)
+    am, tot = [], []
+    for i in range(reps):
+        g.timing_enable(True)
+        tk.dec.generate(tk.tokens[i], 2 + i, 1, use_graph=False)
+        rows = g.timing_read()
+        g.timing_enable(False)
+        am += [r[2] for r in rows if "argmax" in r[0]]
+        tot.append(sum(r[2] for r in rows))
+    return {"kq_argmax_p50": round(statistics.median(am) * 1e3, 2), "launches_sum_p50": round(statistics.median(tot) * 1e3, 1)}
+
+
+def argmax_launch_us(dev, n, slice_, reps=200):
+    """Median event time of the kq_argmax launch; an elementwise launch writes x just before."""
+    prev = g.debug_knob("ARGMAX_SLICE", slice_)
+    try:
+        a = torch.randn(n, device=dev)
+        b = torch.randn(n, device=dev)
+        x = torch.empty(n, device=dev)
+        ws = torch.zeros(g.argmax_workspace_size(n), dtype=torch.uint8, device=dev)
+        out = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        for _ in range(10):
+            g.add(a, b, out=x)
+            g.argmax(x, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        g.timing_enable(True)
+        for _ in range(reps):
+            g.add(a, b, out=x)
+            g.argmax(x, out=out, workspace=ws)
+        rows = g.timing_read()
+        g.timing_enable(False)
+        ms = [r[2] for r in rows if "argmax" in r[0]]
+        assert len(ms) == reps and int(out.cpu()[0]) == int(torch.argmax(x).cpu())
+        return {"slice": g.argmax_plan(n)[1], "workgroups": g.argmax_plan(n)[0],
+                "us_p50": round(statistics.median(ms) * 1e3, 2), "us_min": round(min(ms) * 1e3, 2)}
+    finally:
+        g.debug_knob("ARGMAX_SLICE", prev if prev else float("nan"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--variants", default="a,b,c")
+    ap.add_argument("--slices", default="0,512,1024,2048,4096")
+    ap.add_argument("--chunk", type=int, default=32, help="generate's steps between two synchronizations")
+    args = ap.parse_args()
+    variants = args.variants.split(",")
+    dev = torch.device("cuda:0")
+    be = g.Backend(0)
+    tk = bench.Token("tinyllama-1.1b", dev, 0x51A7, be, 160)
+    fns = {"a": run_a, "b": lambda t, b: run_b(t, b, args.chunk), "c": run_c}
+    for v in variants:  # capture + warm
+        fns[v](tk, be)
+    res = {v: [] for v in variants}
+    for _ in range(args.rounds):
+        for v in variants:
+            res[v].append(fns[v](tk, be))
+    med = {v: statistics.median(x) for v, x in res.items()}
+    out = {"model": "tinyllama-1.1b", "tokens": STEPS, "warmup": WARM, "rounds": args.rounds, "chunk": args.chunk,
+           "lib": os.path.relpath(g.LIB_PATH, ROOT),
+           "ms_per_token": {v: [round(x, 4) for x in r] for v, r in res.items()},
+           "median_ms_per_token": {v: round(m, 4) for v, m in med.items()}}
+    if "a" in res:
+        out["spread_a_ms"] = round(max(res["a"]) - min(res["a"]), 4)
+    if all(v in res for v in "abc"):
+        out["c_minus_b_ms"] = round(med["c"] - med["b"], 4)
+        out["b_minus_a_ms"] = round(med["b"] - med["a"], 4)
+        out["gate_b_faster_than_c_by_more_than_spread_a"] = bool(med["c"] - med["b"] > out["spread_a_ms"])
+    if "b" in res:
+        out["in_token_us"] = in_token_us(tk, be)
+    if "b" in res and args.slices:
+        out["kq_argmax_us"] = {str(n): [argmax_launch_us(dev, n, int(s)) for s in args.slices.split(",")]
+                               for n in (32000, 128256)}
+    print(json.dumps(out))
+    be.close()
+
+
+if __name__ == "__main__":
+    main()
