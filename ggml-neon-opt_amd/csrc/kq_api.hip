@@ -532,7 +532,7 @@ int mi355x_debug_knob(const char *name, double value, double *previous) {
 }
 
 int mi355x_mmq_impl(int impl) {
-    if (impl < MI355X_MMQ_AUTO || impl > MI355X_MMQ_TILE192) return MI355X_E_INVAL;
+    if (impl < MI355X_MMQ_AUTO || impl > MI355X_MMQ_TILE192 || impl == 5) return MI355X_E_INVAL;  // 5: retired
     const int prev = mmq_impl();
     mmq_impl_set(impl);
     return prev;

@@ -183,39 +183,19 @@ constexpr int ROWS_PRO_NONE = 0, ROWS_PRO_NORM = 1, ROWS_PRO_SWIGLU = 2;
 // LDS-DMA instructions. Ring depth per type keeps 6.8-8.5 KB in flight per wave,
 // ~80-100 KB per CU (measured ceiling: 2-3 KB steps, ~96 KB per CU, nt -> 7.1 TB/s).
 constexpr int ROWS_SB = 16;     // superblocks per step (4 lanes each)
-#ifndef KQ_MMQ_PF
-#define KQ_MMQ_PF 0  // kq_mmq tiles: L2 warm-up distance of the weight tile in superblocks (0 off; 2, 3 measured neutral to -5 %)
-#endif
-constexpr int MMQ_PF_LDS = KQ_MMQ_PF ? 1024 : 0;  // its scratch: 256 B per wave
 constexpr int Q8L_STRIDE = 304; // LDS/workspace Q8_K block: d @0, qs @16, bsums @272 (16-B aligned)
-#ifndef KQ_MMQ_NBUF
-#define KQ_MMQ_NBUF 2  // kq_mmq superblock buffers in LDS (experiment: 3 on the one-workgroup-per-CU tiles)
-#endif
-// Superblock buffers of a kq_mmq tile (RT weight rows x 64*CW columns): KQ_MMQ_NBUF where the
-// tile already runs one workgroup per CU (128 x 64 at two waves per SIMD, 64 x 128) and the
-// buffers fit the CU's LDS; else 2.
-// Column groups of waves: 2 (a wave takes 32 x CW of the tile's 64 x CW columns), or 1 for
-// CW = 4 (the 4-wave 128 x 128 tile: every wave all 128 columns of its 32 rows, one wave per
-// SIMD with every register: each weight operand feeds four MFMA column tiles).
-__host__ __device__ constexpr int mmq_cgroups(int cw) { return cw == 4 ? 1 : 2; }
-__host__ __device__ constexpr int mmq_cols(int cw) { return 32 * cw * mmq_cgroups(cw); }
-__host__ __device__ constexpr int mmq_waves(int rt, int cw) { return rt / 32 * mmq_cgroups(cw); }
-// Q6_K rows staged at KQ_MMQ_Q6_STRIDE bytes: the 14 granules of a 210-B block (fetched from
+// kq_mmq tiles (RT weight rows x 64*CW columns), two superblock buffers in LDS each.
+// The waves form two column groups: a wave takes 32 rows x 32 * CW of the tile's 64 * CW columns.
+__host__ __device__ constexpr int mmq_cols(int cw) { return 64 * cw; }
+__host__ __device__ constexpr int mmq_waves(int rt, int cw) { return rt / 16; }
+// Q6_K rows staged at MMQ_Q6_STRIDE bytes: the 14 granules of a 210-B block (fetched from
 // the 16-B boundary below it, 224 B) plus one padding granule at 240, so consecutive rows start
 // 60 dwords apart (16 bank offsets) instead of 56 (8): the tile's realigned row reads
 // conflicted for 71 % of the LDS's active cycles at 224 (profiles/r06_prefill_stall.md).
-#ifndef KQ_MMQ_Q6_STRIDE
-#define KQ_MMQ_Q6_STRIDE 240
-#endif
-static_assert(KQ_MMQ_Q6_STRIDE % 16 == 0 && KQ_MMQ_Q6_STRIDE >= 224, "whole granules");
+constexpr int MMQ_Q6_STRIDE = 240;
+static_assert(MMQ_Q6_STRIDE % 16 == 0 && MMQ_Q6_STRIDE >= 224, "whole granules");
 __host__ __device__ constexpr int mmq_buf_bytes(int type, int rt, int cw) {
-    return mmq_cols(cw) * Q8L_STRIDE + rt * (type == Q6_K ? KQ_MMQ_Q6_STRIDE : block_bytes(type));
-}
-__host__ __device__ constexpr int mmq_nbuf(int type, int rt, int cw) {
-    return KQ_MMQ_NBUF == 1 ? 1 : KQ_MMQ_NBUF >= 3 && ((rt == 128 && cw == 1) || (rt == 64 && cw == 2)) &&
-                   3 * mmq_buf_bytes(type, rt, cw) + 16 + MMQ_PF_LDS <= 160 * 1024
-               ? 3
-               : 2;
+    return mmq_cols(cw) * Q8L_STRIDE + rt * (type == Q6_K ? MMQ_Q6_STRIDE : block_bytes(type));
 }
 constexpr int ROWS_RECS = 64;   // chain records per wave per batch (soft cap)
 __host__ __device__ constexpr int rows_gran(int type) { return block_bytes(type) + 1; }
@@ -359,7 +339,7 @@ struct LayerArgs {
 };
 
 // ---------------------------------------------------------------- batched (prefill) MFMA GEMM
-// kq_mmq (M > 1): 64 x 64 output tiles, Q8L activations in a workspace.
+// kq_mmq (M > 1): RT x 64 * CW output tiles (RT 64 / 128 rows, CW 1 / 2), Q8L activations in a workspace.
 struct MmqArgs {
     const uint8_t *w;        // weight rows (16-B aligned, row_stride % 16 == 0)
     int64_t row_stride;      // bytes
@@ -372,12 +352,12 @@ struct MmqArgs {
     int nb;
     const float *res;        // ADD epilogue (null: none): y = mul_mat + res, res column j at
     int64_t res_col_stride;  //   res + j * res_col_stride (the one f32 add of ggml_add)
-    // kq_mmq (64 x 64 tiles) over up to 4 matrices of one type sharing the activation
+    // kq_mmq over up to 4 matrices of one type sharing the activation
     // (q/k/v of a prompt batch): row tiles [tile0[d], tile0[d+1]) are matrix d's; n_mat 1:
     // the fields above only
     int n_mat;
     int tile0[5];
-    int mtype[4];  // kq_mmq_mixed: each matrix's type (Q4_K / Q6_K)
+    int mtype[4];  // kq_mmq_mixed: each matrix's type (Q4_K / Q5_K / Q6_K)
     // KV-cache store epilogue of a prompt's k / v projections (kv_kind[d]: 1 k -> rope ->
     // f16 cache rows, 2 v -> f16 transposed cache; 0 none); kv_cur: this tile's matrix
     int kv_kind[4], kv_cur;

@@ -170,7 +170,6 @@ bool mmq_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t 
 int launch_mmq(int type, const void *w, int64_t K, int64_t N, size_t row_stride, const uint8_t *xq, int64_t M,
                float *y, int64_t y_col_stride, hipStream_t stream, const float *res = nullptr,
                int64_t res_col_stride = 0);  // res: ADD epilogue
-bool mmq_tile64(int type, int64_t N, int64_t M);  // launch_mmq would use the 64 x 64 tile kernel
 // f16 prefill path (mi355x_prefill_precision F16, csrc/kq_mmf.hip): the activation image
 // (kq_quantize_f16img) at the workspace start, then the GEMM (its split-K slabs after the
 // image); res: ADD epilogue

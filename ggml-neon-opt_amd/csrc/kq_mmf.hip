@@ -26,16 +26,11 @@
 // (each weight byte is read by one wave only), so only the activation goes through LDS.
 #include "kq_device.h"
 
-// Pin the one-step-ahead activation reads with a scheduling barrier (hipcc otherwise
-// moves each read next to its MFMA).
 // Timing-only ablations (experiment builds, make variant-mmf NAME=d1 VFLAGS=-DKQ_MMF_DIAG=1):
 // 1 no activation refill after the first step, 8 no workgroup barrier (round 3, RR = 1:
 // the 8B ffn_up 79 -> 69 us without the refill, 66 us without both).
 #ifndef KQ_MMF_DIAG
 #define KQ_MMF_DIAG 0
-#endif
-#ifndef KQ_MMF_PIN
-#define KQ_MMF_PIN 1
 #endif
 
 namespace kq {
@@ -356,7 +351,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
             for (int sl = 0; sl < 8; ++sl) {
                 if (sl < 7) act(av[(sl + 1) & 1], sl + 1);
-                if (KQ_MMF_PIN) __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead
+                __builtin_amdgcn_sched_barrier(0);  // pin the reads one step ahead (hipcc otherwise moves each next to its MFMA)
 #pragma unroll
                 for (int rr = 0; rr < RR; ++rr) {
                     const f16x8 wf = mmf_frag<TYPE>(wc[rr], s[rr], 2 * hf + (sl >> 2), sl & 3);

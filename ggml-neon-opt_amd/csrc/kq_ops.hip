@@ -350,9 +350,6 @@ __global__ void __launch_bounds__(256) kq_attn_prompt(const AttnArgs a) {
 // the cache reads of kq_attn_prompt) and every barrier; each (token, head) row keeps its own
 // scores, soft_max and accumulators.
 constexpr int PROMPT_GMAX = 8;  // query heads per kv group handled by kq_attn_prompt_group
-#ifndef KQ_PROMPT_SUMLANES
-#define KQ_PROMPT_SUMLANES 1  // soft_max's in-order fallback sums: one lane per row, all rows at once
-#endif
 #ifndef KQ_PROMPT_TPW
 #define KQ_PROMPT_TPW 1  // tokens per workgroup where the LDS holds them (2: measured 1.37x slower, profiles/r06_prompt_ab.txt)
 #endif
@@ -493,19 +490,7 @@ __global__ void __launch_bounds__(256) kq_attn_prompt_group(const AttnArgs a) {
         int ngr = 0;  // row t's groups (t < R)
 #pragma unroll
         for (int tt = 0; tt < TPW; ++tt) ngr = t / gsz == tt ? nkv[tt] / 4 : ngr;
-        if (KQ_PROMPT_SUMLANES) {
-            if (t < R && !((const int *)scal)[4 * t + 2]) scal[4 * t + 1] = (float)(1.0 / seq_sum_lds(gsum + t * (nc / 4), ngr));
-        } else {  // (A/B builds: a wave per row, in turn)
-#pragma unroll
-            for (int tt = 0; tt < TPW; ++tt)
-                for (int hh = t >> 6; hh < gsz; hh += 4) {
-                    const int r = tt * gsz + hh;
-                    if (!((const int *)scal)[4 * r + 2]) {
-                        const double s = seq_sum_lds(gsum + r * (nc / 4), nkv[tt] / 4);
-                        if ((t & 63) == 0) scal[4 * r + 1] = (float)(1.0 / s);
-                    }
-                }
-        }
+        if (t < R && !((const int *)scal)[4 * t + 2]) scal[4 * t + 1] = (float)(1.0 / seq_sum_lds(gsum + t * (nc / 4), ngr));
     }
     __syncthreads();
 #pragma unroll

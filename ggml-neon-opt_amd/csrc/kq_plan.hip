@@ -421,8 +421,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                 i += 1;
                 continue;
             }
-            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= 16 && batched_mm_shares(po, t) &&
-                mmq_tile64(t->src[0]->type, t->src[0]->ne[1], t->src[1]->ne[1])) {
+            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= 16 && batched_mm_shares(po, t)) {
                 // (the f16 GEMM: one weight type per launch)
                 int run = 1;
                 while (i + run < n && run < 4) {
@@ -430,8 +429,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                     if (u->op != MI355X_OP_MUL_MAT || u->src[1] != t->src[1] ||
                         !(mm_exact(t) ? multi_types_ok(t->src[0]->type, u->src[0]->type)
                                       : t->src[0]->type == u->src[0]->type) ||
-                        u->src[0]->ne[0] != t->src[0]->ne[0] || !batched_mm_shares(po, u) ||
-                        !mmq_tile64(u->src[0]->type, u->src[0]->ne[1], u->src[1]->ne[1]))
+                        u->src[0]->ne[0] != t->src[0]->ne[0] || !batched_mm_shares(po, u))
                         break;
                     ++run;
                 }

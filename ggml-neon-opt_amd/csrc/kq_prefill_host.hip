@@ -28,10 +28,9 @@ std::atomic<int> g_prefill{MI355X_PREFILL_EXACT};
 }  // namespace
 
 // ------------------------------------------------------------ batched MFMA path
-// Prefill kernel selector (mi355x_mmq_impl): -1 until first read from MI355X_MMQ_IMPL.
-// Round 3 removed the streamed Q4_K kernel (kq_mmq_k4): equal to the 64 x 64 tiles
-// within the box spread at pp512, 17-40 % slower on every shape forced onto it
-// (profiles/r02_mmq_impl_ab.txt); AUTO and TILE64 now both select the 64 x 64 tiles.
+// Prefill tile selector, set only through mi355x_mmq_impl (the library reads no environment):
+// AUTO (mmq_shape's choice by grid) or one tile shape forced (the four AUTO chooses among, or
+// the selector-only 192 x 64).
 int mmq_impl() { return g_mmq_impl.load(); }
 void mmq_impl_set(int impl) { g_mmq_impl.store(impl); }
 
@@ -58,7 +57,6 @@ MmqShape mmq_shape(int type, int64_t rows, int64_t M) {
     if (impl == MI355X_MMQ_TILE128W) return {128, 2};
     if (impl == MI355X_MMQ_TILE64W) return {64, 2};
     if (impl == MI355X_MMQ_TILE64) return {64, 1};
-    if (impl == MI355X_MMQ_TILE128X) return {128, type == Q6_K ? 2 : 4};
     if (impl == MI355X_MMQ_TILE192) return type == Q6_K ? MmqShape{128, 1} : MmqShape{192, 1};
     const int64_t rt128 = (rows + 127) / 128;
     const int64_t g128x128 = rt128 * ((M + 127) / 128), g128x64 = rt128 * ((M + 63) / 64);
@@ -80,51 +78,15 @@ const void *mmq_fn(int type, bool mixed, MmqShape sh) {
                         : (const void *)kq_mmq<Q4_K, RT, CW>;
     if (sh.rt == 192 && !mixed && type != Q6_K)
         return type == Q5_K ? (const void *)kq_mmq<Q5_K, 192, 1> : (const void *)kq_mmq<Q4_K, 192, 1>;
-    if (sh.rt == 128 && sh.cw == 4 && !mixed && type != Q6_K)
-        return type == Q5_K ? (const void *)kq_mmq<Q5_K, 128, 4> : (const void *)kq_mmq<Q4_K, 128, 4>;
     if (sh.rt == 128 && sh.cw == 2) KQ_MMQ_PICK(128, 2)
     if (sh.rt == 64 && sh.cw == 2) KQ_MMQ_PICK(64, 2)
     if (sh.rt == 128) KQ_MMQ_PICK(128, 1)
     KQ_MMQ_PICK(64, 1)
 #undef KQ_MMQ_PICK
 }
-// two superblock buffers: mmq_cols(cw) Q8L columns + rt weight rows (Q6_K: KQ_MMQ_Q6_STRIDE, the 224-B granule span + padding),
-// +16 B for the Q6_K realign reads past the last row
-size_t mmq_lds(int type, MmqShape sh) {
-    return (size_t)mmq_nbuf(type, sh.rt, sh.cw) * (size_t)mmq_buf_bytes(type, sh.rt, sh.cw) + 16 + MMQ_PF_LDS;
-}
-
-int launch_mmq(int type, const void *w, int64_t K, int64_t N, size_t row_stride, const uint8_t *xq, int64_t M,
-               float *y, int64_t y_col_stride, hipStream_t stream, const float *res, int64_t res_col_stride) {
-    MmqArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_mat = 1;
-    a.res = res;
-    a.res_col_stride = res_col_stride;
-    a.w = (const uint8_t *)w;
-    a.row_stride = (int64_t)row_stride;
-    a.n_rows = (int)N;
-    a.xq = xq;
-    a.nb = (int)(K / QK);
-    a.xq_col_stride = (int64_t)a.nb * Q8L_STRIDE;
-    a.m_cols = (int)M;
-    a.y = y;
-    a.y_col_stride = y_col_stride;
-    const MmqShape sh = mmq_shape(type, N, M);
-    const void *fn = mmq_fn(type, false, sh);
-    const size_t lds = mmq_lds(type, sh);
-    const int cols = mmq_cols(sh.cw);
-    dim3 grid((unsigned)((M + cols - 1) / cols), (unsigned)((N + sh.rt - 1) / sh.rt), 1);
-    dim3 block((unsigned)(64 * mmq_waves(sh.rt, sh.cw)));
-    allow_lds(fn, lds);
-    void *args[] = {&a};
-    return timed_launch_args(
-        [&] {
-            return LaunchInfo{std::string("kq::kq_mmq<") + std::to_string(type) + ">",
-                              (double)N * a.nb * block_bytes(type) + (double)M * a.nb * Q8L_STRIDE + (double)M * N * 4.0};
-        },
-        fn, grid, block, lds, stream, args);
-}
+// two superblock buffers: mmq_cols(cw) Q8L columns + rt weight rows (Q6_K: MMQ_Q6_STRIDE, the 224-B
+// granule span + padding), +16 B for the Q6_K realign reads past the last row
+size_t mmq_lds(int type, MmqShape sh) { return 2 * (size_t)mmq_buf_bytes(type, sh.rt, sh.cw) + 16; }
 
 // ------------------------------------------- prefill on the f16 matrix core (stated tolerance)
 // mi355x_prefill_precision: MI355X_PREFILL_EXACT (kq_mmq, bit-exact, the default) or
@@ -291,20 +253,15 @@ int launch_mmf_gemm(int type, const void *w, int64_t K, int64_t N, size_t row_st
                             stream, res, res_col_stride);
 }
 
-// Whether launch_mmq would run this GEMM on the 64 x 64 tile kernel: every GEMM since the
-// streamed kernel was removed (kept as the backend's batching test).
-bool mmq_tile64(int type, int64_t N, int64_t M) {
-    (void)type, (void)N, (void)M;
-    return true;
-}
-
-// Up to 4 matrices of one type on one Q8L activation in ONE 64 x 64-tile launch (a prompt
-// batch's q/k/v: the small k/v GEMMs no longer run as half-empty launches of their own).
-// Mixed Q4_K / Q6_K matrices run on kq_mmq_mixed (each row tile its matrix's body).
-int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
+// Up to 4 matrices on one Q8L activation in ONE launch (a prompt batch's q/k/v: the small k/v
+// GEMMs do not run as half-empty launches of their own), on the tile mmq_shape picks for their
+// rows together. Matrices of different K-quant types run on kq_mmq_mixed (each row tile its
+// matrix's body). res: the ADD epilogue of a single matrix; kv: the KV-cache epilogue.
+namespace {
+int launch_mmq_tiles(const int *types, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
                      float *const *y, const int64_t *y_col_stride, int64_t K, const uint8_t *xq, int64_t M,
-                     hipStream_t stream, const MmqKv *kv) {
-    if (n_mat < 1 || n_mat > 4) return MI355X_E_INVAL;
+                     hipStream_t stream, const MmqKv *kv, const float *res, int64_t res_col_stride) {
+    if (n_mat < 1 || n_mat > 4 || (res && n_mat > 1)) return MI355X_E_INVAL;
     const int type = types[0];
     bool mixed = false;
     for (int d = 1; d < n_mat; ++d) mixed |= types[d] != type;
@@ -317,12 +274,13 @@ int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const in
     bool has_q5 = false;
     for (int d = 0; d < n_mat; ++d) has_q5 |= types[d] == Q5_K;
     if (mixed && has_q5 && sh.rt == 128 && sh.cw == 2) sh = {128, 1};  // kq_mmq_mixed<128, 2> has no Q5_K body
-    if (sh.cw == 4 && (mixed || type == Q6_K)) sh = {128, 2};  // the 4-wave 128 x 128 tile: Q4_K / Q5_K only
     if (sh.rt == 192 && (mixed || type == Q6_K)) sh = {128, 1};  // the 12-wave 192-row tile: Q4_K / Q5_K only
     const int rt = sh.rt;
     MmqArgs a;
     memset(&a, 0, sizeof(a));
     a.n_mat = n_mat;
+    a.res = res;
+    a.res_col_stride = res_col_stride;
     a.xq = xq;
     a.nb = (int)(K / QK);
     a.xq_col_stride = (int64_t)a.nb * Q8L_STRIDE;
@@ -368,6 +326,19 @@ int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const in
                               wbytes + (double)M * a.nb * Q8L_STRIDE + ybytes};
         },
         fn, grid, dim3((unsigned)(64 * mmq_waves(rt, sh.cw))), lds, stream, args);
+}
+}  // namespace
+
+int launch_mmq(int type, const void *w, int64_t K, int64_t N, size_t row_stride, const uint8_t *xq, int64_t M,
+               float *y, int64_t y_col_stride, hipStream_t stream, const float *res, int64_t res_col_stride) {
+    return launch_mmq_tiles(&type, 1, &w, &N, &row_stride, &y, &y_col_stride, K, xq, M, stream, nullptr, res,
+                            res_col_stride);
+}
+
+int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const int64_t *N, const size_t *row_stride,
+                     float *const *y, const int64_t *y_col_stride, int64_t K, const uint8_t *xq, int64_t M,
+                     hipStream_t stream, const MmqKv *kv) {
+    return launch_mmq_tiles(types, n_mat, w, N, row_stride, y, y_col_stride, K, xq, M, stream, kv, nullptr, 0);
 }
 
 bool mmq_applies(int type, const void *w, int64_t N, size_t row_stride, int64_t M) {

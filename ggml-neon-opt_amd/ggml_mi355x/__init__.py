@@ -37,7 +37,7 @@ ATTN_GROUP, ATTN_HEAD, ATTN_SPLIT = 0, 1, 2
 # mi355x_attn_path: the decode attention kernel a descriptor takes
 ATTN_PATH_HEAD, ATTN_PATH_HEAD_BATCH, ATTN_PATH_SPLIT4, ATTN_PATH_SPLIT8, ATTN_PATH_CELLS, ATTN_PATH_GROUP, _ = range(7)  # (6: retired)
 ATTN_PATH_STREAM = 7  # the streamed kernels (attn_stream)
-MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE128X, MMQ_TILE192 = 0, 1, 2, 3, 4, 5, 6
+MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE192 = 0, 1, 2, 3, 4, 6
 PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
 
 # Every symbol include/ggml_mi355x.h declares (checked by tests/test_abi.py).

@@ -291,17 +291,20 @@ int mi355x_gemv_impl(int impl);
 /* Prefill (ne11 >= 16) GEMM selector for the int8-MFMA tile kernel: MI355X_MMQ_TILE64
  * (64 weight rows x 64 activation columns per workgroup), MI355X_MMQ_TILE128 (128 rows x
  * 64 columns, 8 waves: the activation tile fetched once per 128 rows), MI355X_MMQ_TILE128W
- * (128 rows x 128 columns: each wave's weight operands feed two MFMA column tiles) or
- * MI355X_MMQ_AUTO (the library's choice by shape). Same numerics in all. Returns the
- * previous value, or MI355X_E_INVAL. */
+ * (128 rows x 128 columns: each wave's weight operands feed two MFMA column tiles),
+ * MI355X_MMQ_TILE64W, MI355X_MMQ_TILE192 (both below) or MI355X_MMQ_AUTO (the library's
+ * choice by shape, among the first four). Same numerics in all. Returns the previous value, or
+ * MI355X_E_INVAL for any other value, the retired 5 included (the selector then stays as it
+ * was). */
 #define MI355X_MMQ_AUTO 0
 #define MI355X_MMQ_TILE64 1
 #define MI355X_MMQ_TILE128 2
 #define MI355X_MMQ_TILE128W 3
 #define MI355X_MMQ_TILE64W 4 /* 64 rows x 128 columns, 4 waves (two column tiles per wave) */
-#define MI355X_MMQ_TILE128X 5 /* 128 rows x 128 columns, 4 waves (each wave 32 rows x all 128 columns,
-                                 one wave per SIMD); Q4_K / Q5_K (Q6_K takes TILE128W) */
-#define MI355X_MMQ_TILE192 6 /* 192 rows x 64 columns, 12 waves (three per SIMD); Q4_K / Q5_K (Q6_K takes TILE128) */
+/* 5 is not reused: it was MI355X_MMQ_TILE128X (128 x 128, 4 waves), retired after measuring
+ * 20-30 % slower (profiles/r05_mmq_tile128x_ab.txt). */
+#define MI355X_MMQ_TILE192 6 /* 192 rows x 64 columns, 12 waves (three per SIMD); Q4_K / Q5_K (Q6_K takes TILE128);
+                                a selector only, AUTO never chooses it (profiles/r05_mmq_tile192_ab.txt) */
 int mi355x_mmq_impl(int impl);
 /* Prefill (ne11 >= 16) precision: MI355X_PREFILL_EXACT (kq_mmq, int8 MFMA, bit-exact
  * against ggml's per-(row, column) vec_dot loop; the default), MI355X_PREFILL_F16 (within

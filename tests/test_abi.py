@@ -92,6 +92,15 @@ def test_argument_validation_without_device():
     prev = L.mi355x_gemv_impl(3)  # GEMV_DYN (claimed rows)
     assert L.mi355x_gemv_impl(prev) == 3
     assert L.mi355x_gemv_impl(4) == -1
+    # the prefill tile selector takes 0..4 and 6; 5 (the retired TILE128X) is refused like any
+    # other value and leaves the selector as it was
+    prev = L.mi355x_mmq_impl(3)  # MMQ_TILE128W
+    try:
+        for bad in (5, 7, -1):
+            assert L.mi355x_mmq_impl(bad) == -1  # MI355X_E_INVAL
+        assert L.mi355x_mmq_impl(3) == 3
+    finally:
+        L.mi355x_mmq_impl(prev)
     # no device here -> the HIP path reports it instead of falling back
     descs = (g.GemvDesc * 1)(g.GemvDesc(12, 0x1000, 4, 144, 0x3000))
     rc = L.mi355x_gemv_fused(descs, 1, 0x2000, 256, None, 0, None)

@@ -597,10 +597,9 @@ def prompt_impl(request):
     g.attn_prompt_impl(prev)
 
 
-@pytest.fixture(params=[0, 2, 3, 5], ids=["mmq_auto", "mmq_tile128", "mmq_tile128w", "mmq_tile128x"])
+@pytest.fixture(params=[0, 2, 3, 4], ids=["mmq_auto", "mmq_tile128", "mmq_tile128w", "mmq_tile64w"])
 def prompt_mmq(request):
-    """The prompt's GEMMs on the default choice and on the 128-row tiles (the streamed
-    Q4_K kernel was removed in round 3)."""
+    """The prompt's GEMMs on the default choice, on the 128-row tiles and on the 64 x 128 tile."""
     import ggml_mi355x as g
     prev = g.mmq_impl(request.param)
     yield request.param
