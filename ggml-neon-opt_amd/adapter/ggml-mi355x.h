@@ -36,8 +36,9 @@ GGML_BACKEND_API void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, 
 // off (the default), a graph over such a cache is refused (GGML_STATUS_FAILED); on, its
 // attention runs on the library's streamed kernels (mi355x_attn_stream mode 1, same bits).
 // Process-wide, like the library's selector; caches that run today keep their kernels either
-// way. Not covered: multi-sequence graphs (ATTN_BATCH) over such caches. Also returned by the
-// registry's get_proc_address under this name.
+// way. With ggml_backend_mi355x_set_multi_seq on as well, multi-sequence graphs (ATTN_BATCH)
+// over such caches run on the streamed kernels too. Also returned by the registry's
+// get_proc_address under this name.
 GGML_BACKEND_API void ggml_backend_mi355x_set_long_context(bool enable);
 
 #ifdef __cplusplus

@@ -42,6 +42,10 @@
 //    order exactly. Every other thread's lanes are ggml's bit for bit.
 //  Visible cells are never compacted: the groups of four and the accumulator lane cell % 32
 //  are positional, so a skipped block keeps its place. Nothing at or past cell n_kv is read.
+//
+// Caches past this kernel's sizes (attn_size_refused, or neither LDS form fits) run, under
+// mi355x_attn_stream, kq_kv_store_batch and then the batch form of the streamed kernels
+// (kq_attn_stream.hip; attn_batch_form returns MI355X_ATTN_PATH_STREAM), with the same bits.
 #include <math.h>
 #include <stdint.h>
 
@@ -262,7 +266,7 @@ constexpr size_t kBatchLdsMax = 160 * 1024;
 // MI355X_ATTN_GROUP (one workgroup per kv group and token), MI355X_ATTN_HEAD (one per query
 // head and token: where the group's rows do not fit, the group has more than BATCH_GMAX heads,
 // or mi355x_attn_prompt_impl asks for it), or MI355X_E_UNSUPPORTED where neither form's LDS fits.
-int attn_batch_form(const AttnBatchArgs &b) {
+static int attn_batch_lds_form(const AttnBatchArgs &b) {
     const int gsz = b.a.n_head / b.a.n_head_kv;
     if (gsz <= BATCH_GMAX && attn_batch_lds(b.a.head_dim, b.n_kv, gsz) <= kBatchLdsMax &&
         g_prompt_impl.load() == MI355X_ATTN_GROUP)
@@ -271,14 +275,23 @@ int attn_batch_form(const AttnBatchArgs &b) {
     return MI355X_E_UNSUPPORTED;
 }
 
+// ... or MI355X_ATTN_PATH_STREAM, the streamed form (kq_attn_stream.hip), under mi355x_attn_stream:
+// mode 1 where kq_attn_batch refuses the descriptor for its size alone (the cache's, as the
+// per-head kernels do, or neither LDS form fits), mode 2 for every shape the streamed kernels take.
+int attn_batch_form(const AttnBatchArgs &b) {
+    const int form = attn_batch_lds_form(b);
+    const bool refused = attn_size_refused(b.a) || form < 0;
+    if (attn_batch_stream_applies(b, refused)) return MI355X_ATTN_PATH_STREAM;
+    return refused ? MI355X_E_UNSUPPORTED : form;
+}
+
 int check_attn_batch(const AttnBatchArgs &b) {
     if (!b.cells || !b.mask || b.n_tok <= 0) return MI355X_E_INVAL;
     if (b.n_kv < 32 || b.n_kv % 32 || b.n_kv > b.a.n_ctx || b.n_pos <= 0) return MI355X_E_INVAL;
     if (b.mask_row_bytes < (int64_t)b.n_kv * (b.mask_f16 ? 2 : 4)) return MI355X_E_INVAL;
     if (b.a.rope_row) return MI355X_E_INVAL;  // per-token positions: the whole rope table
     if (b.n_tok > 65535) return MI355X_E_UNSUPPORTED;  // one grid row per token
-    if (attn_size_refused(b.a)) return MI355X_E_UNSUPPORTED;  // (mi355x_attn_stream lifts the size limit for decode / prompt only)
-    const int form = attn_batch_form(b);
+    const int form = attn_batch_form(b);  // (past the cache sizes of kq_attn_batch: the streamed form, or refused)
     return form < 0 ? form : MI355X_OK;
 }
 
@@ -288,7 +301,16 @@ int launch_attn_batch(const AttnBatchArgs &b0, hipStream_t s) {
     AttnBatchArgs b = b0;
     const AttnArgs &a = b.a;
     const int gsz = a.n_head / a.n_head_kv;
-    b.per_head = attn_batch_form(b) == MI355X_ATTN_HEAD ? 1 : 0;
+    const int form = attn_batch_form(b);
+    if (form == MI355X_ATTN_PATH_STREAM) {  // the store, then three launches per token tile
+        void *ws = attn_batch_stream_buffer(b, s);
+        if (!ws) return MI355X_E_WORKSPACE;  // captured without a reservation: nothing was stored
+        const dim3 gs((unsigned)b.n_tok, (unsigned)a.n_head_kv);
+        rc = a.head_dim == 64 ? timed_launch("kq::kq_kv_store_batch<64>", 0.0, kq_kv_store_batch<64>, gs, dim3(256), 0, s, b)
+                              : timed_launch("kq::kq_kv_store_batch<128>", 0.0, kq_kv_store_batch<128>, gs, dim3(256), 0, s, b);
+        return rc ? rc : launch_attn_batch_stream(b, ws, s);
+    }
+    b.per_head = form == MI355X_ATTN_HEAD ? 1 : 0;
     const int rows = b.per_head ? 1 : gsz;
     const size_t lds = attn_batch_lds(a.head_dim, b.n_kv, rows);
     const dim3 gs((unsigned)b.n_tok, (unsigned)a.n_head_kv);

@@ -25,6 +25,17 @@
 // theirs. Loops run to the n_kv / n_it of the device-read position, never to n_ctx. A position
 // outside [0, n_ctx) gives a NaN row and leaves the caches untouched. Every cache and workspace
 // offset is 64-bit (a V row of kvw * n_ctx f16 passes 2^31 bytes' neighbourhood at 131072 cells).
+//
+// The batch form (STREAM_BATCH: mi355x_attn_batch / ATTN_BATCH under mi355x_attn_stream, after
+// kq_kv_store_batch of kq_attn_batch.hip) runs the same three bodies per token tile with the
+// row taken from the descriptor: cells [0, n_kv), workspace rows of n_kv entries, the score
+// dot * scale + mask[token][cell] (kq_attn_batch's), the position selecting the rope row only.
+// A 64-cell chunk without a visible cell (mask != -INF) loads no K row; the workgroups of KV
+// group 0 leave one flag byte per (token, 32-cell block) behind the p16 rows, from which every
+// wave of launch C lists the 512-cell stages that hold a visible cell and runs its ring over
+// those alone. A skipped stage adds v * (+0) to every lane, which changes nothing but the sign
+// of a zero (the header of kq_attn_batch.hip): a wave with a lane that ends as -0 runs every
+// stage again. A token without a cell (kq_kv_store_batch's test) gets a NaN row.
 #include <math.h>
 #include <stdint.h>
 
@@ -48,17 +59,38 @@ constexpr int STREAM_VROW = 2 * STREAM_CELLS + 64;                  // C: a stag
 constexpr int STREAM_STAGE = 4 * STREAM_VROW + 2 * STREAM_CELLS;    // C: 4 V rows + p16 of one chunk
 constexpr int STREAM_RS = 16;        // C: outputs per workgroup (4 per wave)
 constexpr size_t kStreamKqvLds = (size_t)4 * STREAM_DEPTH * STREAM_STAGE + 256 * 4;
+// C, batch form: behind the above, per wave the list of its visible stages (uint16 each)
+constexpr int STREAM_LIST = kAttnStreamMaxCtx / STREAM_CELLS;
+constexpr size_t kStreamBatchKqvLds = kStreamKqvLds + (size_t)4 * STREAM_LIST * 2;
 // a prompt's token tile: the most workspace one tile may take (mi355x_attn_prompt, T > 1)
 constexpr size_t kStreamPromptWorkspaceMax = (size_t)256 << 20;
 
 // ------------------------------------------------------------------ A: store and scores
-// PROMPT: token blockIdx.z of the tile at tok0 (q / pos rows per token; the cells were stored by
+enum { STREAM_DECODE = 0, STREAM_PROMPT = 1, STREAM_BATCH = 2 };
+
+__device__ __forceinline__ int64_t stream_batch_cell(const AttnBatchArgs &b, int i) {
+    return b.cells_i64 ? ((const int64_t *)b.cells)[i] : (int64_t)((const int32_t *)b.cells)[i];
+}
+// the batch form's token has no cell (kq_kv_store_batch stored nothing for it): a NaN row
+__device__ __forceinline__ bool stream_batch_bad(const AttnBatchArgs &b, int tok) {
+    const int pos = b.a.pos[tok];
+    const int64_t cell = stream_batch_cell(b, tok);
+    return pos < 0 || pos >= b.n_pos || cell < 0 || cell >= b.a.n_ctx;
+}
+// bytes of a token's block flags: one per 32 cells, in whole 512-cell stages (C reads 16 B per stage)
+__host__ __device__ inline int stream_flags_stride(int n_kv) { return (n_kv / 32 + 15) & ~15; }
+
+// STREAM_PROMPT: token blockIdx.z of the tile at tok0 (q / pos rows per token; the cells were stored by
 // kq_kv_store, a kernel boundary before, so cell pos is read from the cache like the others).
-template <int HD, bool PROMPT>
-__global__ void __launch_bounds__(256) kq_attn_stream_scores(const AttnArgs a, float *scores, int tok0) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+// STREAM_BATCH: likewise after kq_kv_store_batch, over the row [0, b->n_kv) under the token's mask
+// row (b: the descriptor, null for the other kinds; flags: the tile's block flags).
+template <int HD, int KIND>
+__device__ __forceinline__ void stream_scores(const AttnArgs &a, const AttnBatchArgs *b, float *scores, uint8_t *flags,
+                                              int tok0, uint8_t *smem) {
+    constexpr bool PROMPT = KIND != STREAM_DECODE, BATCH = KIND == STREAM_BATCH;
     constexpr int KV4 = HD / 8;                    // 16-B pieces of a K row
     constexpr int KPT = STREAM_CHUNK * KV4 / 256;  // pieces per thread
+    static_assert(STREAM_CHUNK == 64, "a thread scores the cell of its lane in every pass; one ballot covers the chunk");
     const int g = blockIdx.y, c0 = blockIdx.x * STREAM_CHUNK, t = threadIdx.x;
     const int ti = PROMPT ? (int)blockIdx.z : 0, tok = PROMPT ? tok0 + ti : 0;
     const int gsz = a.n_head / a.n_head_kv;
@@ -66,16 +98,46 @@ __global__ void __launch_bounds__(256) kq_attn_stream_scores(const AttnArgs a, f
     // the position first: a chunk past n_kv reads nothing (kq_attn_cells requests its K rows
     // with the position; over a cache of 131072 cells that would read every K row per token)
     const int pos_in = a.pos[tok];
-    const bool bad = pos_in < 0 || pos_in >= a.n_ctx;  // no cache cell: caches untouched, C outputs NaN
-    const int pos = bad ? 0 : pos_in;
-    int n_kv = (pos + 1 + 31) / 32 * 32;
-    n_kv = n_kv < a.n_ctx ? n_kv : a.n_ctx;
+    bool bad;  // no cache cell: caches untouched, C outputs NaN
+    int pos, n_kv, rowlen;
+    if constexpr (BATCH) {
+        if (stream_batch_bad(*b, tok)) return;  // (uniform) C reads nothing of this token's rows
+        bad = false, pos = pos_in, n_kv = rowlen = b->n_kv;
+    } else {
+        bad = pos_in < 0 || pos_in >= a.n_ctx;
+        pos = bad ? 0 : pos_in;
+        n_kv = (pos + 1 + 31) / 32 * 32;
+        n_kv = n_kv < a.n_ctx ? n_kv : a.n_ctx;
+        rowlen = a.n_ctx;
+    }
     if (c0 >= n_kv) return;  // (uniform)
+    float *srow = scores + (int64_t)ti * a.n_head * rowlen;
+    // BATCH: the mask entry of this thread's cell c0 + lane (f16 widened first) and the chunk's
+    // visible cells, the same 64 bits in every wave
+    float m = 0.0f;
+    uint64_t vb = ~0ull;
+    if constexpr (BATCH) {
+        const uint8_t *mp = (const uint8_t *)b->mask + (int64_t)tok * b->mask_row_bytes;
+        const int c = c0 + (t & 63);
+        m = -INFINITY;
+        if (c < n_kv) m = b->mask_f16 ? (float)u2h(((const uint16_t *)mp)[c]) : ((const float *)mp)[c];
+        vb = __ballot(m != -INFINITY);
+        if (g == 0 && t < 2 && c0 + 32 * t < n_kv)
+            flags[(int64_t)ti * stream_flags_stride(n_kv) + (c0 >> 5) + t] = (uint32_t)(vb >> (32 * t)) != 0u;
+        if (vb == 0) {  // (uniform) nothing visible: no K row is loaded
+            for (int i = t; i < STREAM_CHUNK * gsz; i += 256) {
+                const int c1 = c0 + i % STREAM_CHUNK;
+                if (c1 < n_kv) srow[(int64_t)(g * gsz + i / STREAM_CHUNK) * rowlen + c1] = -INFINITY;
+            }
+            return;
+        }
+    }
     uint4 kr[KPT];
 #pragma unroll
     for (int u = 0; u < KPT; ++u) {
         const int i = t + 256 * u, r = i / KV4, k = i % KV4;
-        kr[u] = c0 + r < n_kv ? *(const uint4 *)(a.k_cache + (int64_t)(c0 + r) * kvw + (int64_t)g * HD + 8 * k) : uint4{};
+        const bool rd = c0 + r < n_kv && (!BATCH || ((vb >> r) & 1));  // (a hidden cell's row is not read)
+        kr[u] = rd ? *(const uint4 *)(a.k_cache + (int64_t)(c0 + r) * kvw + (int64_t)g * HD + 8 * k) : uint4{};
     }
     // LDS: q16 [gsz][HD] | k16 [HD] | K rows [STREAM_CHUNK][KV4] (piece k of row r at k ^ (r % KV4))
     uint16_t *q16 = (uint16_t *)smem;
@@ -109,12 +171,11 @@ __global__ void __launch_bounds__(256) kq_attn_stream_scores(const AttnArgs a, f
             a.v_cache[(int64_t)(g * HD + d) * a.n_ctx + pos] = h2u(f2h_rne(a.v[(int64_t)g * HD + d]));
     }
     __syncthreads();
-    float *srow = scores + (int64_t)ti * a.n_head * a.n_ctx;
     for (int i = t; i < STREAM_CHUNK * gsz; i += 256) {  // lane <-> cell, waves <-> heads
         const int r = i % STREAM_CHUNK, hh = i / STREAM_CHUNK, c = c0 + r;
         if (c >= n_kv) continue;
-        float sc = -INFINITY;  // cells past pos: masked
-        if (c <= pos) {
+        float sc = -INFINITY;  // cells past pos (BATCH: hidden by the mask): masked
+        if (BATCH ? m != -INFINITY : c <= pos) {
             uint4 kv[KV4];
             if (holds && c == pos) {
 #pragma unroll
@@ -124,9 +185,23 @@ __global__ void __launch_bounds__(256) kq_attn_stream_scores(const AttnArgs a, f
                 for (int k = 0; k < KV4; ++k) kv[k] = krow[r * KV4 + (k ^ (r % KV4))];
             }
             sc = vec_dot_f16_rows<HD>(kv, (const uint4 *)(q16 + hh * HD)) * a.scale;
+            if constexpr (BATCH) sc = sc + m;  // (r is the lane in every pass: this thread's mask entry)
         }
-        srow[(int64_t)(g * gsz + hh) * a.n_ctx + c] = sc;
+        srow[(int64_t)(g * gsz + hh) * rowlen + c] = sc;
     }
+}
+
+template <int HD, bool PROMPT>
+__global__ void __launch_bounds__(256) kq_attn_stream_scores(const AttnArgs a, float *scores, int tok0) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    stream_scores<HD, PROMPT ? STREAM_PROMPT : STREAM_DECODE>(a, nullptr, scores, nullptr, tok0, smem);
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256) kq_attn_stream_scores_batch(const AttnBatchArgs b, float *scores, uint8_t *flags,
+                                                                   int tok0) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    stream_scores<HD, STREAM_BATCH>(b.a, &b, scores, flags, tok0, smem);
 }
 
 // ------------------------------------------------------------------ B: soft_max over the workspace
@@ -145,23 +220,14 @@ __device__ __forceinline__ double stream_seq_sum(const float4 *e4, int ng, int l
     return tot;
 }
 
-__global__ void __launch_bounds__(STREAM_SM_NT) kq_attn_stream_softmax(const AttnArgs a, float *scores, uint16_t *p16,
-                                                                       int tok0) {
+// The three passes over one head's row: ng groups of four scores at w4, their p16 at p2
+__device__ __forceinline__ void stream_softmax_row(float4 *w4, uint2 *p2, int ng) {
     constexpr int NW = STREAM_SM_NT / 64;
     __shared__ float s_max[NW];
     __shared__ double s_part[NW + 1];
     __shared__ int s_gmin[NW], s_bad[NW];
-    const int h = blockIdx.x, ti = blockIdx.y, t = threadIdx.x, ln = t & 63;
+    const int t = threadIdx.x, ln = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int pos_in = a.pos[tok0 + ti];
-    const bool bad = pos_in < 0 || pos_in >= a.n_ctx;
-    const int pos = bad ? 0 : pos_in;
-    int n_kv = (pos + 1 + 31) / 32 * 32;
-    n_kv = n_kv < a.n_ctx ? n_kv : a.n_ctx;
-    const int ng = n_kv >> 2;
-    const int64_t row = ((int64_t)ti * a.n_head + h) * a.n_ctx;
-    float4 *w4 = (float4 *)(scores + row);
-    uint2 *p2 = (uint2 *)(p16 + row);
     // 1: the max (order-free)
     float m = -INFINITY;
     for (int gi = t; gi < ng; gi += STREAM_SM_NT) {
@@ -223,6 +289,27 @@ __global__ void __launch_bounds__(STREAM_SM_NT) kq_attn_stream_softmax(const Att
     }
 }
 
+__global__ void __launch_bounds__(STREAM_SM_NT) kq_attn_stream_softmax(const AttnArgs a, float *scores, uint16_t *p16,
+                                                                       int tok0) {
+    const int h = blockIdx.x, ti = blockIdx.y;
+    const int pos_in = a.pos[tok0 + ti];
+    const bool bad = pos_in < 0 || pos_in >= a.n_ctx;
+    const int pos = bad ? 0 : pos_in;
+    int n_kv = (pos + 1 + 31) / 32 * 32;
+    n_kv = n_kv < a.n_ctx ? n_kv : a.n_ctx;
+    const int64_t row = ((int64_t)ti * a.n_head + h) * a.n_ctx;
+    stream_softmax_row((float4 *)(scores + row), (uint2 *)(p16 + row), n_kv >> 2);
+}
+
+// ... of the batch form: the descriptor's row, the rows n_kv apart
+__global__ void __launch_bounds__(STREAM_SM_NT) kq_attn_stream_softmax_batch(const AttnBatchArgs b, float *scores,
+                                                                             uint16_t *p16, int tok0) {
+    const int h = blockIdx.x, ti = blockIdx.y;
+    if (stream_batch_bad(b, tok0 + ti)) return;  // (uniform) launch A wrote no scores for this token
+    const int64_t row = ((int64_t)ti * b.a.n_head + h) * b.n_kv;
+    stream_softmax_row((float4 *)(scores + row), (uint2 *)(p16 + row), b.n_kv >> 2);
+}
+
 // ------------------------------------------------------------------ C: KQV through the LDS ring
 template <int VM>
 __device__ __forceinline__ void stream_wait_vm() {  // s_waitcnt vmcnt(VM), a compiler barrier for memory
@@ -230,9 +317,11 @@ __device__ __forceinline__ void stream_wait_vm() {  // s_waitcnt vmcnt(VM), a co
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
 }
 
-template <int HD>
-__global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, const uint16_t *p16, int tok0) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+// BATCH (b: the descriptor, null otherwise; flags: launch A's block flags of the tile): the row
+// is the descriptor's, and the ring runs over the stages that hold a visible cell.
+template <int HD, bool BATCH>
+__device__ __forceinline__ void stream_kqv(const AttnArgs &a, const AttnBatchArgs *b, const uint16_t *p16,
+                                           const uint8_t *flags, int tok0, uint8_t *smem) {
     constexpr int DS = HD / STREAM_RS;
     constexpr int NDMA = 5;  // LDS-DMA instructions of one stage: 4 V rows + p16
     static_assert((STREAM_DEPTH - 1) * NDMA < 64, "the counted waits fit vmcnt");
@@ -240,11 +329,20 @@ __global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, cons
     const int t = threadIdx.x, ln = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int g = h / (a.n_head / a.n_head_kv);
-    const int pos_in = a.pos[tok0 + ti];
-    const bool bad = pos_in < 0 || pos_in >= a.n_ctx;
-    const int pos = bad ? 0 : pos_in;
-    const int n_it = (pos + 32) / 32;  // 32-cell iterations holding a cell <= pos (32 n_it <= n_ctx)
-    const int n_kv = 32 * n_it;
+    bool bad;
+    int n_kv, rowlen;  // the cells accumulated (32-cell iterations), the workspace's row stride
+    if constexpr (BATCH) {
+        bad = stream_batch_bad(*b, tok0 + ti);
+        n_kv = bad ? 0 : b->n_kv;  // (no cell: nothing is read, a NaN row)
+        rowlen = b->n_kv;
+    } else {
+        const int pos_in = a.pos[tok0 + ti];
+        bad = pos_in < 0 || pos_in >= a.n_ctx;
+        const int pos = bad ? 0 : pos_in;
+        const int n_it = (pos + 32) / 32;  // 32-cell iterations holding a cell <= pos (32 n_it <= n_ctx)
+        n_kv = 32 * n_it;
+        rowlen = a.n_ctx;
+    }
     const int nch = (n_kv + STREAM_CELLS - 1) / STREAM_CELLS;
     uint8_t *ring = smem + (size_t)wv * STREAM_DEPTH * STREAM_STAGE;  // this wave's stages
     uint32_t *red = (uint32_t *)(smem + (size_t)4 * STREAM_DEPTH * STREAM_STAGE);
@@ -252,55 +350,111 @@ __global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, cons
     // the wave's 4 V rows (outputs ds * 16 + 4 wv + r) and the head's p16 row
     const int64_t vrow0 = (int64_t)(g * HD + ds * STREAM_RS + 4 * wv) * a.n_ctx;
     const uint8_t *vsrc = (const uint8_t *)(a.v_cache + vrow0) + 16 * ln;
-    const uint8_t *psrc = (const uint8_t *)(p16 + ((int64_t)ti * a.n_head + h) * a.n_ctx) + 16 * ln;
+    const uint8_t *psrc = (const uint8_t *)(p16 + ((int64_t)ti * a.n_head + h) * rowlen) + 16 * ln;
     const int64_t vstep = (int64_t)a.n_ctx * 2;
-    // chunk c -> stage c % DEPTH: NDMA instructions on every path (a partial chunk masks lanes),
-    // bytes [1024 c, 1024 c + 2 cells) of each row: inside the row's first 2 n_kv <= 2 n_ctx bytes
-    auto issue = [&](int c) {
+    // chunk c -> stage j % DEPTH (j: its place among the chunks the ring runs over): NDMA
+    // instructions on every path (a partial chunk masks lanes), bytes [1024 c, 1024 c + 2 cells)
+    // of each row: inside the row's first 2 n_kv <= 2 n_ctx bytes
+    auto issue = [&](int j, int c) {
         const int cells = n_kv - c * STREAM_CELLS < STREAM_CELLS ? n_kv - c * STREAM_CELLS : STREAM_CELLS;
         const int nl = cells >> 3;  // 16-B lanes
-        const uint32_t st = ring_lds + (uint32_t)((c % STREAM_DEPTH) * STREAM_STAGE);
+        const uint32_t st = ring_lds + (uint32_t)((j % STREAM_DEPTH) * STREAM_STAGE);
         const int64_t off = (int64_t)c * (2 * STREAM_CELLS);
 #pragma unroll
         for (int r = 0; r < 4; ++r) attn_dma16_lanes(vsrc + r * vstep + off, st + (uint32_t)(r * STREAM_VROW), ln, nl);
         attn_dma16_lanes(psrc + off, st + (uint32_t)(4 * STREAM_VROW), ln, nl);
     };
+    // BATCH: the wave's list of the chunks with a visible cell, in order, built before the ring
+    // starts (uniform control flow; the flag loads are the kernel's only loads the compiler
+    // counts, and all of them are consumed here): lane l looks at chunk s0 + l's 16 flag bytes
+    // (those past the row's n_kv / 32 blocks are not flags)
+    uint16_t *list = BATCH ? (uint16_t *)(smem + kStreamKqvLds) + wv * STREAM_LIST : nullptr;
+    int n_vis = nch;
+    if constexpr (BATCH) {
+        const int nblk = n_kv >> 5;
+        const uint8_t *frow = flags + (int64_t)ti * stream_flags_stride(rowlen);
+        n_vis = 0;
+        for (int s0 = 0; s0 < nch; s0 += 64) {
+            const int s = s0 + ln;
+            bool on = false;
+            if (s < nch) {
+                const uint4 f = *(const uint4 *)(frow + 16 * s);
+                const uint32_t fw[4] = {f.x, f.y, f.z, f.w};
 #pragma unroll
-    for (int c = 0; c < STREAM_DEPTH - 1; ++c)
-        if (c < nch) issue(c);  // (uniform)
+                for (int k = 0; k < 4; ++k) {
+                    const int rem = nblk - 16 * s - 4 * k;  // flags in word k
+                    const uint32_t keep = rem >= 4 ? 0xffffffffu : rem <= 0 ? 0u : (1u << (8 * rem)) - 1u;
+                    on = on || (fw[k] & keep) != 0u;
+                }
+            }
+            const uint64_t bl = __ballot(on);
+            if (on) list[n_vis + __popcll(bl & ((1ull << ln) - 1ull))] = (uint16_t)s;
+            n_vis += __builtin_amdgcn_readfirstlane((int)__popcll(bl));
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the list is written (read back by other lanes)
+        __builtin_amdgcn_wave_barrier();
+    }
+    // the j-th chunk of a run: of the list, or (every) of all chunks
+    auto chunk_of = [&](int j, bool every) {
+        if constexpr (BATCH) {
+            if (!every) return __builtin_amdgcn_readfirstlane((int)list[j]);
+        }
+        return j;
+    };
     const int r = ln >> 4, jq = ln & 15;
     uint32_t acc1 = 0;
-    for (int c = 0; c < nch; ++c) {
-        // stage (c + DEPTH - 1) % DEPTH was read in the last round: those reads have returned
-        // (lgkmcnt(0)) before the DMA that overwrites it is issued
-        if (c + STREAM_DEPTH - 1 < nch) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            issue(c + STREAM_DEPTH - 1);
-            stream_wait_vm<(STREAM_DEPTH - 1) * NDMA>();
-        } else if (STREAM_DEPTH > 2 && c + 1 < nch) {
-            stream_wait_vm<NDMA>();  // (DEPTH 3: one later chunk in flight)
-        } else {
-            stream_wait_vm<0>();
-        }
-        static_assert(STREAM_DEPTH == 2 || STREAM_DEPTH == 3, "the tail waits above are written for 2 or 3 stages");
-        const uint8_t *st = ring + (c % STREAM_DEPTH) * STREAM_STAGE;
-        const uint32_t *vrow = (const uint32_t *)(st + r * STREAM_VROW) + jq;
-        const uint32_t *prow = (const uint32_t *)(st + 4 * STREAM_VROW) + jq;
-        const int its = (n_kv - c * STREAM_CELLS < STREAM_CELLS ? n_kv - c * STREAM_CELLS : STREAM_CELLS) >> 5;
-        if (its == STREAM_CELLS / 32) {
-            uint32_t vb[16], pb[16];
+    auto run = [&](const bool every) {
+        const int nj = every ? nch : n_vis;
+        acc1 = 0;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                vb[k] = vrow[16 * k];
-                pb[k] = prow[16 * k];
+        for (int j = 0; j < STREAM_DEPTH - 1; ++j)
+            if (j < nj) issue(j, chunk_of(j, every));  // (uniform)
+        for (int j = 0; j < nj; ++j) {
+            // stage (j + DEPTH - 1) % DEPTH was read in the last round: those reads have returned
+            // (lgkmcnt(0)) before the DMA that overwrites it is issued
+            if (j + STREAM_DEPTH - 1 < nj) {
+                const int cn = chunk_of(j + STREAM_DEPTH - 1, every);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                issue(j + STREAM_DEPTH - 1, cn);
+                stream_wait_vm<(STREAM_DEPTH - 1) * NDMA>();
+            } else if (STREAM_DEPTH > 2 && j + 1 < nj) {
+                stream_wait_vm<NDMA>();  // (DEPTH 3: one later chunk in flight)
+            } else {
+                stream_wait_vm<0>();
             }
+            static_assert(STREAM_DEPTH == 2 || STREAM_DEPTH == 3, "the tail waits above are written for 2 or 3 stages");
+            const int c = chunk_of(j, every);
+            const uint8_t *st = ring + (j % STREAM_DEPTH) * STREAM_STAGE;
+            const uint32_t *vrow = (const uint32_t *)(st + r * STREAM_VROW) + jq;
+            const uint32_t *prow = (const uint32_t *)(st + 4 * STREAM_VROW) + jq;
+            const int its = (n_kv - c * STREAM_CELLS < STREAM_CELLS ? n_kv - c * STREAM_CELLS : STREAM_CELLS) >> 5;
+            if (its == STREAM_CELLS / 32) {
+                uint32_t vb[16], pb[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) acc1 = pk_fma_w(vb[k], pb[k], acc1);
-        } else {
-            for (int k = 0; k < its; ++k) acc1 = pk_fma_w(vrow[16 * k], prow[16 * k], acc1);
+                for (int k = 0; k < 16; ++k) {
+                    vb[k] = vrow[16 * k];
+                    pb[k] = prow[16 * k];
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k) acc1 = pk_fma_w(vb[k], pb[k], acc1);
+            } else {
+                for (int k = 0; k < its; ++k) acc1 = pk_fma_w(vrow[16 * k], prow[16 * k], acc1);
+            }
         }
-    }
+    };
     static_assert(STREAM_CELLS / 32 == 16, "a full stage is 16 iterations");
+    if constexpr (BATCH) {
+        run(false);
+        // a skipped stage's products are v * (+0): they can only have turned a lane that ends as
+        // -0 into +0 (kq_attn_batch.hip's header). A wave with such a lane runs every stage.
+        const bool negz = (acc1 & 0xffffu) == 0x8000u || (acc1 >> 16) == 0x8000u;
+        if (n_vis < nch && __any(negz)) {  // (uniform)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the last stage's reads returned
+            run(true);
+        }
+    } else {
+        run(true);
+    }
     red[t] = acc1;
     __syncthreads();
     // the GGML_F16_VEC_REDUCE of output vr_l's 4 accumulators: quad (vr_l, j = 0..3)
@@ -312,6 +466,19 @@ __global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, cons
     const float o = f16x8_reduce_quad(acc);  // every lane active; the quad's lane 0 holds output vr_l
     if (kt && j == 0)
         a.out[((int64_t)(tok0 + ti) * a.n_head + h) * HD + ds * STREAM_RS + vr_l] = bad ? __builtin_nanf("") : o;
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256) kq_attn_stream_kqv(const AttnArgs a, const uint16_t *p16, int tok0) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    stream_kqv<HD, false>(a, nullptr, p16, nullptr, tok0, smem);
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256) kq_attn_stream_kqv_batch(const AttnBatchArgs b, const uint16_t *p16,
+                                                                const uint8_t *flags, int tok0) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    stream_kqv<HD, true>(b.a, &b, p16, flags, tok0, smem);
 }
 
 // ------------------------------------------------------------------ host side
@@ -350,6 +517,42 @@ int launch_stream_tile(const AttnArgs &a, bool prompt, int tok0, int nt, uint8_t
                         (const uint16_t *)p16, tok0);
 }
 
+// ... of the batch form for tokens [tok0, tok0 + nt): rows of n_kv entries, then the block flags
+template <int HD>
+int launch_stream_batch_tile(const AttnBatchArgs &b, int tok0, int nt, uint8_t *ws, hipStream_t s) {
+    const AttnArgs &a = b.a;
+    const int gsz = a.n_head / a.n_head_kv;
+    float *scores = (float *)ws;
+    uint16_t *p16 = (uint16_t *)(ws + (size_t)nt * a.n_head * b.n_kv * 4);
+    uint8_t *flags = ws + (size_t)nt * a.n_head * b.n_kv * 6;
+    const dim3 ga((unsigned)((b.n_kv + STREAM_CHUNK - 1) / STREAM_CHUNK), (unsigned)a.n_head_kv, (unsigned)nt);
+    int rc = timed_launch(HD == 64 ? "kq::kq_attn_stream_scores<64, batch>" : "kq::kq_attn_stream_scores<128, batch>", 0.0,
+                          kq_attn_stream_scores_batch<HD>, ga, dim3(256), stream_scores_lds(HD, gsz), s, b, scores, flags, tok0);
+    if (rc) return rc;
+    rc = timed_launch("kq::kq_attn_stream_softmax<batch>", 0.0, kq_attn_stream_softmax_batch,
+                      dim3((unsigned)a.n_head, (unsigned)nt), dim3(STREAM_SM_NT), 0, s, b, scores, p16, tok0);
+    if (rc) return rc;
+    allow_lds((const void *)kq_attn_stream_kqv_batch<HD>, kStreamBatchKqvLds);
+    return timed_launch(HD == 64 ? "kq::kq_attn_stream_kqv<64, batch>" : "kq::kq_attn_stream_kqv<128, batch>", 0.0,
+                        kq_attn_stream_kqv_batch<HD>, dim3((unsigned)(a.n_head * (HD / STREAM_RS)), (unsigned)nt), dim3(256),
+                        kStreamBatchKqvLds, s, b, (const uint16_t *)p16, (const uint8_t *)flags, tok0);
+}
+
+// tokens per tile: by the workspace cap (ATTN_STREAM_TILE: fewer), at least one
+int stream_tile(size_t per_tok, int n_tok) {
+    int64_t tile = (int64_t)(kStreamPromptWorkspaceMax / per_tok);
+    const int64_t kt = (int64_t)knob(KNOB_ATTN_STREAM_TILE);
+    if (kt > 0 && kt < tile) tile = kt;
+    if (tile > 65535) tile = 65535;  // one grid row per token
+    if (tile > n_tok) tile = n_tok;
+    return tile < 1 ? 1 : (int)tile;
+}
+
+// the batch form's workspace per token of a tile: 6 bytes per (head, cell of the row), the block flags
+size_t stream_batch_per_tok(const AttnBatchArgs &b) {
+    return (size_t)b.a.n_head * b.n_kv * 6 + (size_t)stream_flags_stride(b.n_kv);
+}
+
 }  // namespace
 
 // mi355x_attn_stream's mode, or the ATTN_STREAM debug knob's where that holds one (bench runs
@@ -380,16 +583,8 @@ bool attn_stream_prompt_applies(const AttnArgs &a) {
            (mode == 2 || attn_size_refused(a) || attn_prompt_lds(a.head_dim, a.n_ctx) > 160 * 1024);
 }
 
-// tokens per tile of a prompt of n_tok tokens: by the workspace cap (ATTN_STREAM_TILE: fewer), at least one
-int attn_stream_tile(const AttnArgs &a, int n_tok) {
-    const size_t per_tok = (size_t)a.n_head * a.n_ctx * 6;
-    int64_t tile = (int64_t)(kStreamPromptWorkspaceMax / per_tok);
-    const int64_t kt = (int64_t)knob(KNOB_ATTN_STREAM_TILE);
-    if (kt > 0 && kt < tile) tile = kt;
-    if (tile > 65535) tile = 65535;  // one grid row per token
-    if (tile > n_tok) tile = n_tok;
-    return tile < 1 ? 1 : (int)tile;
-}
+// tokens per tile of a prompt of n_tok tokens
+int attn_stream_tile(const AttnArgs &a, int n_tok) { return stream_tile((size_t)a.n_head * a.n_ctx * 6, n_tok); }
 
 size_t attn_stream_workspace(const AttnArgs &a, int n_tok) {
     return (size_t)attn_stream_tile(a, n_tok < 1 ? 1 : n_tok) * a.n_head * a.n_ctx * 6;
@@ -414,6 +609,32 @@ int launch_attn_stream_prompt(const AttnArgs &a0, int n_tok, hipStream_t s) {
     for (int tok0 = 0; tok0 < n_tok && !rc; tok0 += tile) {
         const int nt = n_tok - tok0 < tile ? n_tok - tok0 : tile;
         rc = a.head_dim == 64 ? launch_stream_tile<64>(a, true, tok0, nt, ws, s) : launch_stream_tile<128>(a, true, tok0, nt, ws, s);
+    }
+    return rc;
+}
+
+// ---- the batch form (kq_attn_batch.hip selects it: attn_batch_form)
+bool attn_batch_stream_applies(const AttnBatchArgs &b, bool refused) {
+    const int mode = attn_stream_mode();
+    return mode != 0 && stream_shape_ok(b.a) && (mode == 2 || refused);
+}
+
+size_t attn_batch_stream_workspace(const AttnBatchArgs &b) {
+    const size_t per_tok = stream_batch_per_tok(b);
+    return (size_t)stream_tile(per_tok, b.n_tok) * per_tok;
+}
+
+void *attn_batch_stream_buffer(const AttnBatchArgs &b, hipStream_t s) {
+    return attn_cells_buffer(attn_batch_stream_workspace(b), s, !capturing(s));
+}
+
+int launch_attn_batch_stream(const AttnBatchArgs &b, void *ws, hipStream_t s) {
+    const int tile = stream_tile(stream_batch_per_tok(b), b.n_tok);
+    int rc = MI355X_OK;
+    for (int tok0 = 0; tok0 < b.n_tok && !rc; tok0 += tile) {
+        const int nt = b.n_tok - tok0 < tile ? b.n_tok - tok0 : tile;
+        rc = b.a.head_dim == 64 ? launch_stream_batch_tile<64>(b, tok0, nt, (uint8_t *)ws, s)
+                                : launch_stream_batch_tile<128>(b, tok0, nt, (uint8_t *)ws, s);
     }
     return rc;
 }

@@ -660,10 +660,19 @@ int ensure_layer_tables(mi355x_backend *b, const std::vector<Launch> &launches) 
 }
 
 // long-cache attention: the score workspace of a decode node (the split over cells, the
-// streamed kernels) and of a prompt node that takes the streamed kernels
+// streamed kernels), of a prompt node and of an ATTN_BATCH node that take the streamed kernels
 int reserve_attn_cells(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<Launch> &launches) {
     for (const Launch &l : launches) {
         const mi355x_tensor *t = nodes[l.first];
+        if (l.kind == LaunchKind::Node && t->op == MI355X_OP_ATTN_BATCH) {
+            mi355x_attn_batch_desc d;
+            attn_batch_desc_of(t, d);
+            kq::AttnBatchArgs ba;
+            if (kq::attn_batch_args_from(&d, (int)t->src[6]->ne[1], ba) == MI355X_OK &&
+                kq::attn_batch_form(ba) == MI355X_ATTN_PATH_STREAM && !kq::attn_batch_stream_buffer(ba, b->stream))
+                return MI355X_E_WORKSPACE;
+            continue;
+        }
         if (l.kind != LaunchKind::Node || t->op != MI355X_OP_ATTN_DECODE) continue;
         const int64_t T = t->src[0]->ne[1];
         mi355x_attn_desc d = {};

@@ -244,6 +244,14 @@ bool attn_stream_prompt_applies(const AttnArgs &a);
 size_t attn_stream_workspace(const AttnArgs &a, int n_tok);
 int launch_attn_stream(const AttnArgs &a, hipStream_t s);
 int launch_attn_stream_prompt(const AttnArgs &a, int n_tok, hipStream_t s);
+// The batch form (ATTN_BATCH's cells and mask; rows of n_kv entries plus one flag per 32 cells).
+// attn_batch_stream_applies: the mode sends these (checked) arguments to it, `refused` saying
+// that kq_attn_batch cannot take them; _buffer: its workspace on attn_cells_buffer (null under
+// capture without a reservation); launch_attn_batch_stream: the launches after kq_kv_store_batch.
+bool attn_batch_stream_applies(const AttnBatchArgs &b, bool refused);
+size_t attn_batch_stream_workspace(const AttnBatchArgs &b);
+void *attn_batch_stream_buffer(const AttnBatchArgs &b, hipStream_t s);
+int launch_attn_batch_stream(const AttnBatchArgs &b, void *ws, hipStream_t s);
 
 // ---------------------------------------------------------------- kq_attn_oproj.hip
 // Decode attention + the o-proj GEMV (+ residual ADD) in one launch.
@@ -278,7 +286,8 @@ int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *ste
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from
 // checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /
-// MI355X_ATTN_HEAD, or MI355X_E_UNSUPPORTED where neither form's LDS fits.
+// MI355X_ATTN_HEAD, MI355X_ATTN_PATH_STREAM (the streamed form, where mi355x_attn_stream's mode
+// sends the descriptor), or MI355X_E_UNSUPPORTED where no form takes it.
 int attn_batch_args_from(const mi355x_attn_batch_desc *d, int n_pos, AttnBatchArgs &b);
 int attn_batch_form(const AttnBatchArgs &b);
 int launch_attn_batch(const AttnBatchArgs &b, hipStream_t s);

@@ -197,8 +197,8 @@ bool layer_match(const PlanOpts &po, mi355x_tensor *const *nodes, int n, int i, 
 bool contig_f32(const mi355x_tensor *t) { return t && t->type == MI355X_TYPE_F32 && t->nb[0] == 4 && t->data; }
 
 // ATTN_DECODE / ATTN_BATCH: the caches (src4, src5) exactly [n_ctx][kvw] and [kvw][n_ctx] f16,
-// 16-B aligned (the kernels' addressing), n_ctx a multiple of 32 up to max_ctx (8192; ATTN_DECODE
-// up to kAttnStreamMaxCtx while mi355x_attn_stream is on); pos (src3) i32
+// 16-B aligned (the kernels' addressing), n_ctx a multiple of 32 up to max_ctx (8192; up to
+// kAttnStreamMaxCtx while mi355x_attn_stream is on); pos (src3) i32
 bool kv_caches_ok(const mi355x_tensor *op, int nkv, int hd, int64_t max_ctx = 8192) {
     const mi355x_tensor *kc = op->src[4], *vc = op->src[5];
     if (kc->type != MI355X_TYPE_F16 || vc->type != MI355X_TYPE_F16) return false;
@@ -620,7 +620,9 @@ bool supports_op(const mi355x_tensor *op) {
             // T tokens: q, k, v, pos as ATTN_DECODE's, cells [T]
             const int64_t T = op->src[0]->ne[1];
             if (T < 1 || T > 65535) return false;
-            if (!kv_caches_ok(op, nkv, hd) || !qkv_rows_ok(op, nh, nkv, hd, T)) return false;
+            if (!kv_caches_ok(op, nkv, hd, attn_stream_mode() != 0 ? kAttnStreamMaxCtx : 8192) ||
+                !qkv_rows_ok(op, nh, nkv, hd, T))
+                return false;
             if (n_kv < 32 || n_kv % 32 || n_kv > op->src[4]->ne[1]) return false;
             if (!contig_f32(tab) || tab->ne[0] != hd || tab->ne[1] < 1 || tab->ne[1] > 0x7fffffff) return false;
             if ((cells->type != MI355X_TYPE_I32 && cells->type != MI355X_TYPE_I64) || nelem(cells) != T) return false;
@@ -631,7 +633,8 @@ bool supports_op(const mi355x_tensor *op) {
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(op, d);
             AttnBatchArgs ba;
-            if (attn_batch_args_from(&d, (int)tab->ne[1], ba) != MI355X_OK) return false;  // the LDS of either form
+            // the LDS of either form, or the streamed form under mi355x_attn_stream
+            if (attn_batch_args_from(&d, (int)tab->ne[1], ba) != MI355X_OK) return false;
             return contig_f32(op) && op->ne[0] == (int64_t)nh * hd && op->ne[1] == T &&
                    (T == 1 || op->nb[1] == (size_t)nh * hd * 4);
         }

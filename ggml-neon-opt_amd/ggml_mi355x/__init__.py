@@ -552,8 +552,8 @@ def attn_impl(impl):
 def attn_stream(mode):
     """Streamed attention for caches of up to 131072 cells (mi355x_attn_stream): 0 off (default),
     1 for the descriptors refused for their cache size alone, 2 for every valid descriptor (tests,
-    A/B). attn_path / attn_decode / attn_prompt and the graph backend follow it. Returns the
-    previous mode, E_INVAL for any other value."""
+    A/B). attn_path / attn_decode / attn_prompt, attn_batch / attn_batch_path and the graph backend
+    (OP_ATTN_BATCH included) follow it. Returns the previous mode, E_INVAL for any other value."""
     return int(lib().mi355x_attn_stream(mode))
 
 
@@ -711,8 +711,9 @@ def attn_batch(q, k, v, pos, cells, mask, table, k_cache, v_cache, n_head, n_hea
 
 
 def attn_batch_path(n_ctx, n_head, n_head_kv, head_dim, n_kv):
-    """ATTN_GROUP / ATTN_HEAD: the form mi355x_attn_batch takes for this shape (negative: the
-    status it would return). No launch, no device access (synthetic, aligned addresses)."""
+    """ATTN_GROUP / ATTN_HEAD, or ATTN_PATH_STREAM (7) where attn_stream's mode sends the shape to
+    the streamed form: the form mi355x_attn_batch takes for this shape (negative: the status it
+    would return). No launch, no device access (synthetic, aligned addresses)."""
     base = 1 << 20
     a = AttnDesc(base, base + 4096, base + 8192, base + 64, base + 12288, base + (1 << 12), base + (1 << 13),
                  base + (1 << 14), n_ctx, n_head, n_head_kv, head_dim, 1.0 / float(head_dim) ** 0.5, 0)

@@ -438,12 +438,15 @@ int mi355x_attn_impl(int impl);
  *   1: a descriptor refused only for its cache size (mi355x_attn_prompt: also one whose prompt
  *      kernel does not fit the LDS) takes the streamed kernels; every descriptor that runs with
  *      0 keeps its kernel;
- *   2: every valid descriptor takes them, decode and prompt (tests, A/B runs).
- * mi355x_attn_prompt runs its tokens in tiles whose workspace stays under 256 MiB (at least one
- * token). A launch captured into a hipGraph needs its workspace reserved beforehand (the graph
- * backend does it); otherwise it returns MI355X_E_WORKSPACE. The mode is part of the graph
- * backend's plan key. Not covered: ATTN_BATCH, the attention + o-proj fusion and the layer
- * engine keep their sizes. Returns the previous mode, or MI355X_E_INVAL. */
+ *   2: every valid descriptor takes them, decode, prompt and batch (tests, A/B runs).
+ * mi355x_attn_batch (ATTN_BATCH) follows the same modes with its streamed form: rows of n_kv
+ * entries, cells and mask from the descriptor (mode 1: a descriptor kq_attn_batch refuses for
+ * its size alone). mi355x_attn_prompt and mi355x_attn_batch run their tokens in tiles whose
+ * workspace stays under 256 MiB (at least one token). A launch captured into a hipGraph needs
+ * its workspace reserved beforehand (the graph backend does it); otherwise it returns
+ * MI355X_E_WORKSPACE. The mode is part of the graph backend's plan key. Not covered: the
+ * attention + o-proj fusion and the layer engine keep their sizes. Returns the previous mode,
+ * or MI355X_E_INVAL. */
 int mi355x_attn_stream(int mode);
 /* Prompt attention selector (A/B runs, parity of both): MI355X_ATTN_GROUP (default: one
  * workgroup per kv group and token, the group's query heads sharing every K/V load, where
@@ -464,7 +467,12 @@ int mi355x_attn_prompt_impl(int impl);
  * the same cell is undefined, as in ggml. Cells inside [0, n_kv) must hold finite values
  * (zero-initialised caches do); nothing at or past n_kv is read. The K rows of hidden cells and
  * the V chunks of 32-cell blocks without a visible cell are not loaded (exactly the same bits:
- * csrc/kq_attn_batch.hip). Returns MI355X_E_INVAL for a null pointer, a type outside the list,
+ * csrc/kq_attn_batch.hip). Caches of more than 8192 cells (7616 at head_dim 64, 7040 at 128) run
+ * only under mi355x_attn_stream, in the streamed form (kq_kv_store_batch, then per token tile
+ * kq_attn_stream_scores / _softmax / _kqv over the descriptor's row, up to 131072 cells, the
+ * same bits; there the K rows of 64-cell chunks and the V rows of 512-cell stages without a
+ * visible cell are not loaded; a captured launch needs its workspace reserved, else
+ * MI355X_E_WORKSPACE). Returns MI355X_E_INVAL for a null pointer, a type outside the list,
  * n_kv % 32 != 0, n_kv < 32, n_kv > n_ctx, mask_row_bytes below n_kv entries, rope_row != 0 or
  * n_tokens <= 0 (before any device access), MI355X_E_UNSUPPORTED for a shape the kernels do
  * not take. */
@@ -477,8 +485,9 @@ typedef struct {
 int mi355x_attn_batch(const mi355x_attn_batch_desc *d, void *stream);
 /* The form mi355x_attn_batch runs for this descriptor: MI355X_ATTN_GROUP (one workgroup per
  * KV group and token: the group's query heads share every K row, V chunk and mask row; groups
- * of at most 8 heads whose rows fit 160 KB of LDS) or MI355X_ATTN_HEAD (one per query head and
- * token), or the MI355X_E_* mi355x_attn_batch would return. No launch, no device access. */
+ * of at most 8 heads whose rows fit 160 KB of LDS), MI355X_ATTN_HEAD (one per query head and
+ * token) or MI355X_ATTN_PATH_STREAM (7: the streamed form, where mi355x_attn_stream's mode sends
+ * the descriptor), or the MI355X_E_* mi355x_attn_batch would return. No launch, no device access. */
 int mi355x_attn_batch_path(const mi355x_attn_batch_desc *d);
 
 /* Greedy sampling: *out = the smallest index i whose x[i] equals the maximum of the non-NaN

@@ -5,12 +5,15 @@ synthetic Q4_K_M weights, hipGraph replay — and the kq_attn_batch launch besid
 kq_attn_prompt_group on a causal single-sequence batch of the same T and n_kv.
 
     python tools/batch_decode.py [--cells 512,2048] [--seqs 1,2,4,8] [--steps 64] [--warmup 16] [--reps 3]
-                                 [--form auto|head]
+                                 [--form auto|head] [--attn-stream]
 
 The caches are pre-filled with random finite f16 values up to `cells` cells per sequence; in the
 batch decoder the sequences are interleaved (sequence s holds the cells c with c % n_seq == s).
 A (cells, n_seq) pair whose cache (n_seq * (cells + steps), rounded up to 32) is larger than the
-attention kernels take (7616 cells at head_dim 64) is reported as "not run". Each figure is the
+attention kernels take (7616 cells at head_dim 64) is reported as "not run", unless --attn-stream
+sets mi355x_attn_stream mode 1: then such caches (up to 131072 cells) run on the streamed kernels,
+on both sides where the size needs it, and the attention launch is also timed in its streamed form
+(mode 2) at the sizes kq_attn_batch takes. Each figure is the
 median of `reps` windows of `steps` steps after `warmup` steps, every window ending in a stream
 synchronise. Prints one line per measurement and a JSON summary at the end."""
 import argparse
@@ -71,7 +74,8 @@ def batch_side(tk, be, cells, n_seq, steps, warmup, reps, gen):
     med, wins = median_window(run, be.synchronize, steps, warmup, reps)
     del dec
     torch.cuda.empty_cache()
-    return dict(n_ctx=n_ctx, form="group" if form == g.ATTN_GROUP else "head", s_per_step=med / steps,
+    return dict(n_ctx=n_ctx, form={g.ATTN_GROUP: "group", g.ATTN_HEAD: "head", g.ATTN_PATH_STREAM: "stream"}[form],
+                s_per_step=med / steps,
                 tok_s=n_seq * steps / med, windows_s=wins)
 
 
@@ -93,9 +97,10 @@ def sequential_side(tk, be, cells, n_seq, steps, warmup, reps, gen):
     return dict(n_ctx=n_ctx, s_per_step=med / steps, tok_s=n_seq * steps / med, windows_s=wins)
 
 
-def kernel_side(hp, dev, T, n_kv, reps, gen):
+def kernel_side(hp, dev, T, n_kv, reps, gen, stream=False):
     """The attention launch alone, op level: T tokens of one sequence at the last T cells of a
-    cache of n_kv cells under the causal mask, through mi355x_attn_batch and mi355x_attn_prompt."""
+    cache of n_kv cells under the causal mask, through mi355x_attn_batch and mi355x_attn_prompt;
+    stream: also mi355x_attn_batch in its streamed form (mode 2 for the one measurement)."""
     hd, nh, nkv = hp["head_dim"], hp["n_head"], hp["n_head_kv"]
     kvw = nkv * hd
     tab = g.rope_table(n_kv, hd, hp["freq_base"], 1.0, device=dev)
@@ -108,8 +113,12 @@ def kernel_side(hp, dev, T, n_kv, reps, gen):
     mask = torch.where(torch.arange(n_kv, device=dev)[None, :] <= pos[:, None], 0.0, float("-inf")).to(torch.float32)
     scale = 1.0 / float(hd) ** 0.5
     out = {}
-    for name, fn in (("batch", lambda: g.attn_batch(q, k, v, pos, pos, mask, tab, kc, vc, nh, nkv, hd, scale, n_kv)),
-                     ("prompt", lambda: g.attn_prompt(q, k, v, pos, tab, kc, vc, nh, nkv, hd, scale))):
+    sides = [("batch", lambda: g.attn_batch(q, k, v, pos, pos, mask, tab, kc, vc, nh, nkv, hd, scale, n_kv)),
+             ("prompt", lambda: g.attn_prompt(q, k, v, pos, tab, kc, vc, nh, nkv, hd, scale))]
+    if stream:
+        sides.append(("batch_stream", sides[0][1]))
+    for name, fn in sides:
+        prev = g.attn_stream(2) if name == "batch_stream" else None
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
@@ -118,6 +127,8 @@ def kernel_side(hp, dev, T, n_kv, reps, gen):
             fn()
         rows = g.timing_read()
         g.timing_enable(False)
+        if prev is not None:
+            g.attn_stream(prev)
         per = {}
         for kn, _, ms in rows:
             per.setdefault(kn, []).append(ms)
@@ -135,10 +146,16 @@ def main():
     ap.add_argument("--model", default="tinyllama-1.1b")
     ap.add_argument("--form", default="auto", choices=["auto", "head"],
                     help="head: one attention workgroup per query head and token at every size (attn_prompt_impl)")
+    ap.add_argument("--attn-stream", action="store_true",
+                    help="mi355x_attn_stream mode 1: caches past the attention kernels' sizes run on the streamed kernels")
     args = ap.parse_args()
     if not g.device_available():
         raise SystemExit("batch_decode: no gfx950 device (the measurement does not fall back)")
     dev = torch.device("cuda:0")
+    if args.attn_stream:
+        global MAX_CTX
+        MAX_CTX = 131072  # kAttnStreamMaxCtx
+        g.attn_stream(1)
     if args.form == "head":
         g.attn_prompt_impl(g.ATTN_HEAD)
     be = g.Backend()
@@ -152,7 +169,7 @@ def main():
             s = sequential_side(tk, be, cells, n_seq, args.steps, args.warmup, args.reps, gen)
             row = dict(cells_per_seq=cells, n_seq=n_seq, batch=b, sequential=s)
             if b is not None:
-                row["kernels_us"] = kernel_side(tk.hp, dev, n_seq, b["n_ctx"], 20, gen)
+                row["kernels_us"] = kernel_side(tk.hp, dev, n_seq, b["n_ctx"], 20, gen, args.attn_stream)
             res.append(row)
             bt = "not run (cache too large)" if b is None else \
                 f"{b['tok_s']:8.1f} tok/s ({b['s_per_step'] * 1e3:.3f} ms/step, n_kv {b['n_ctx']}, {b['form']} form)"
