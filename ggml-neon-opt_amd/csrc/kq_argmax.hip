@@ -22,6 +22,13 @@
 // every word with sc1 loads behind a workgroup barrier, reduces them the same way and writes
 // the result. It stores 0 back to the counter, so every launch and every graph replay
 // starts at 0. No workgroup waits for another: nothing can deadlock, placement only changes speed.
+//
+// Rows. kq_argmax_rows is the same reduction over each of T rows of a matrix in one launch, grid
+// (workgroups per row, T): a row is split as argmax_plan splits a vector of its length and handed
+// off on a counter of its own, so the rows never meet. Its step-inputs form ends one step of
+// several sequences (LlamaDecoder.generate_batch): the last arriver of row i writes the
+// sequence's next token, position and cell where the batch graph reads them, makes that cell
+// visible in the row's own mask and files the token in the row's history.
 #include <string.h>
 
 #include "kq_internal.h"
@@ -32,6 +39,16 @@ namespace kq {
 namespace {
 
 constexpr int kArgmaxThreads = 256;
+constexpr int kArgmaxSlice = 1024;  // entries per workgroup up to 256 workgroups (ARGMAX_SLICE: A/B)
+constexpr int kArgmaxMaxWgs = 256;  // the last arriver reads one word per thread
+constexpr size_t kArgmaxCounterBytes = 128;  // the counter on a line of its own, then the words
+// kq_argmax_rows: a row's part of the workspace, the counter's line and the words of the largest
+// split. The same for every n, so every counter keeps its place whatever a workspace served
+// before (a place that depended on n would land on another call's leftover words), and a whole
+// number of lines, so no row's words share a line with a counter. Row 0's counter is kq_argmax's
+// and the next is past kq_argmax's words: the backend's one buffer serves both kernels.
+constexpr size_t kArgmaxRowBytes = kArgmaxCounterBytes + 8 * (size_t)kArgmaxMaxWgs;
+static_assert(kArgmaxRowBytes % kArgmaxCounterBytes == 0, "a row's part is a whole number of lines");
 
 struct ArgmaxArgs {
     const float *x;
@@ -86,13 +103,11 @@ __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v
     return max_u64(max_u64(lds[0], lds[1]), max_u64(lds[2], lds[3]));
 }
 
-__global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) {
-    __shared__ unsigned long long red[2][4];
-    __shared__ int flag;
+// The word of slice [lo, hi) of x (lo % 4 == 0, x 16-B aligned; hi % 4 != 0 only at x's end), in
+// every thread of the workgroup
+__device__ __forceinline__ unsigned long long slice_word(const float *x, int lo, int hi) {
+    __shared__ unsigned long long red[4];
     const int t = (int)threadIdx.x;
-    const int lo = (int)blockIdx.x * p.slice;  // (lo < n: wgs = ceil(n / slice))
-    const int hi = p.n - lo < p.slice ? p.n : lo + p.slice;
-
     // ---- this lane's vectors lo/4 + t, + 256, ... in index order: a strict > keeps the first
     uint32_t bestk = 0u, besti = 0xffffffffu;  // (no entry: the word 0, below every entry's)
     const int vfull = hi >> 2;  // vectors [lo/4, vfull) are whole
@@ -100,7 +115,7 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) 
         u32x4 r[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (v0 + j * kArgmaxThreads < vfull) r[j] = *(const u32x4 *)(p.x + 4 * (int64_t)(v0 + j * kArgmaxThreads));
+            if (v0 + j * kArgmaxThreads < vfull) r[j] = *(const u32x4 *)(x + 4 * (int64_t)(v0 + j * kArgmaxThreads));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (v0 + j * kArgmaxThreads >= vfull) break;
@@ -115,29 +130,47 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) 
     // the vector's last n % 4 entries (the last slice only), after every whole vector of the slice
     if (t == kArgmaxThreads - 1)
         for (int i = 4 * vfull; i < hi; ++i) {
-            const uint32_t k = ord_key(__float_as_uint(p.x[i]));
+            const uint32_t k = ord_key(__float_as_uint(x[i]));
             if (k > bestk) bestk = k, besti = (uint32_t)i;
         }
-    unsigned long long w = block_max_u64(((unsigned long long)bestk << 32) | (uint32_t)~besti, red[0]);
+    return block_max_u64(((unsigned long long)bestk << 32) | (uint32_t)~besti, red);
+}
 
-    // ---- hand-off: the word write-through, drained, barrier, one add; the last arriver goes on
-    if (t == 0) __hip_atomic_store(p.part + blockIdx.x, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// Hand-off of this workgroup's word `w` (word `wg` of `part`) on the counter `cnt` that `wgs`
+// workgroups count in on. False in every thread of a workgroup that is not the last arriver; in
+// the last arriver's threads true, and *token = the index of the maximum over all the words.
+__device__ __forceinline__ bool hand_off(unsigned long long w, unsigned long long *part, uint32_t *cnt, int wg, int wgs,
+                                         int n, int32_t *token) {
+    __shared__ unsigned long long red[4];
+    __shared__ int flag;
+    const int t = (int)threadIdx.x;
+    // ---- the word write-through, drained, barrier, one add; the last arriver goes on
+    if (t == 0) __hip_atomic_store(part + wg, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (t == 0) {
-        const uint32_t old = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = old == (uint32_t)(p.wgs - 1);
-        if (last) __hip_atomic_store(p.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch starts at 0
+        const uint32_t old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = old == (uint32_t)(wgs - 1);
+        if (last) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch starts at 0
         flag = last;
     }
     __syncthreads();
-    if (!flag) return;
+    if (!flag) return false;
 
     // ---- the last arriver: every workgroup's word (wgs <= 256: one per thread), sc1 loads
-    w = t < p.wgs ? __hip_atomic_load(p.part + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    w = block_max_u64(w, red[1]);
+    w = t < wgs ? __hip_atomic_load(part + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    w = block_max_u64(w, red);
     const uint32_t idx = ~(uint32_t)w;
-    const int32_t token = idx < (uint32_t)p.n ? (int32_t)idx : 0;  // (all NaN: the word 0)
+    *token = idx < (uint32_t)n ? (int32_t)idx : 0;  // (all NaN: the word 0)
+    return true;
+}
+
+__global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) {
+    const int t = (int)threadIdx.x;
+    const int lo = (int)blockIdx.x * p.slice;  // (lo < n: wgs = ceil(n / slice))
+    const int hi = p.n - lo < p.slice ? p.n : lo + p.slice;
+    int32_t token;
+    if (!hand_off(slice_word(p.x, lo, hi), p.part, p.cnt, (int)blockIdx.x, p.wgs, p.n, &token)) return;
     if (!p.pos) {
         if (t == 0) p.out[0] = token;
         return;
@@ -156,9 +189,44 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) 
         for (int k = t; k < p.hd; k += kArgmaxThreads) p.out[2 + k] = (int32_t)p.table[(size_t)next * p.hd + k];
 }
 
-constexpr int kArgmaxSlice = 1024;  // entries per workgroup up to 256 workgroups (ARGMAX_SLICE: A/B)
-constexpr int kArgmaxMaxWgs = 256;  // the last arriver reads one word per thread
-constexpr size_t kArgmaxCounterBytes = 128;  // the counter on a line of its own, then the words
+struct ArgmaxRowsArgs {
+    const float *x;
+    int64_t row_stride;  // floats between two rows
+    int n, slice, wgs;
+    uint8_t *ws;         // workspace, per row (kArgmaxRowBytes): the counter's line, then the row's words
+    int32_t *out;        // [T]: the rows' indices (step form: the sequences' next tokens)
+    // step-inputs form (pos != null): row i's last arriver also advances pos[i] and cells[i], shows
+    // the new cell in mask row i and files the token in history row i, where those entries exist
+    int32_t *pos, *cells, *hist;
+    float *mask;
+    int64_t mask_stride, hist_stride;  // entries between two rows
+    uint32_t n_kv, n_hist;
+    int cell_stride;
+};
+
+__global__ void __launch_bounds__(kArgmaxThreads) kq_argmax_rows(const ArgmaxRowsArgs p) {
+    const int64_t row = (int64_t)blockIdx.y;
+    const int lo = (int)blockIdx.x * p.slice;  // (lo < n: wgs = ceil(n / slice))
+    const int hi = p.n - lo < p.slice ? p.n : lo + p.slice;
+    uint32_t *cnt = (uint32_t *)(p.ws + (size_t)row * kArgmaxRowBytes);
+    unsigned long long *part = (unsigned long long *)((uint8_t *)cnt + kArgmaxCounterBytes);
+    int32_t token;
+    if (!hand_off(slice_word(p.x + row * p.row_stride, lo, hi), part, cnt, (int)blockIdx.x, p.wgs, p.n, &token)) return;
+    if (threadIdx.x != 0) return;
+    if (!p.pos) {
+        p.out[row] = token;
+        return;
+    }
+    // step inputs: the one thread that touches row i's entries; its loads of pos[i] and cells[i]
+    // have returned before it writes either
+    uint32_t np = (uint32_t)p.pos[row] + 1u, nc = (uint32_t)p.cells[row] + (uint32_t)p.cell_stride;
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(np), "+v"(nc)::"memory");
+    p.out[row] = token;
+    p.pos[row] = (int32_t)np;
+    p.cells[row] = (int32_t)nc;
+    if (nc < p.n_kv) p.mask[row * p.mask_stride + nc] = 0.0f;  // the cell the next step writes: visible to its own row
+    if (np < p.n_hist) p.hist[row * p.hist_stride + np] = token;
+}
 
 }  // namespace
 
@@ -209,6 +277,47 @@ int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *ste
                         p);
 }
 
+size_t argmax_rows_workspace(int64_t n, int64_t rows) {
+    if (argmax_plan(n, nullptr, nullptr) != MI355X_OK || rows < 1 || rows > kArgmaxMaxRows) return 0;
+    return (size_t)rows * kArgmaxRowBytes;
+}
+
+int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
+                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream) {
+    int wgs = 0;
+    int64_t slice = 0;
+    if (!x || !out || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
+    if (rows < 1 || rows > kArgmaxMaxRows || row_stride < n || (row_stride & 3)) return MI355X_E_INVAL;
+    if (step && (!step->pos || !step->cells || !step->mask || !step->hist || step->cell_stride < 1 || step->n_kv < 0 ||
+                 step->n_kv > 0x7fffffff || step->n_hist < 0 || step->n_hist > 0x7fffffff ||
+                 step->mask_stride < step->n_kv || step->hist_stride < step->n_hist))
+        return MI355X_E_INVAL;
+    if (!ws || ((uintptr_t)ws & 7u) || ws_size < argmax_rows_workspace(n, rows)) return MI355X_E_WORKSPACE;
+    if (!device_ok()) return MI355X_E_NODEVICE;
+    ArgmaxRowsArgs p;
+    memset(&p, 0, sizeof(p));
+    p.x = x;
+    p.row_stride = row_stride;
+    p.n = (int)n;
+    p.slice = (int)slice;
+    p.wgs = wgs;
+    p.ws = (uint8_t *)ws;
+    p.out = out;
+    if (step) {
+        p.pos = step->pos;
+        p.cells = step->cells;
+        p.mask = step->mask;
+        p.hist = step->hist;
+        p.mask_stride = step->mask_stride;
+        p.hist_stride = step->hist_stride;
+        p.n_kv = (uint32_t)step->n_kv;
+        p.n_hist = (uint32_t)step->n_hist;
+        p.cell_stride = step->cell_stride;
+    }
+    return timed_launch("kq::kq_argmax_rows", (double)rows * (double)n * 4.0, kq_argmax_rows,
+                        dim3((unsigned)wgs, (unsigned)rows), dim3(kArgmaxThreads), 0, stream, p);
+}
+
 }  // namespace kq
 
 extern "C" {
@@ -219,6 +328,13 @@ size_t mi355x_argmax_workspace_size(int64_t n) { return kq::argmax_workspace(n);
 
 int mi355x_argmax(const float *x, int64_t n, int32_t *out, void *workspace, size_t workspace_size, void *stream) {
     return kq::launch_argmax(x, n, out, nullptr, workspace, workspace_size, (hipStream_t)stream);
+}
+
+size_t mi355x_argmax_rows_workspace_size(int64_t n, int64_t rows) { return kq::argmax_rows_workspace(n, rows); }
+
+int mi355x_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out, void *workspace,
+                       size_t workspace_size, void *stream) {
+    return kq::launch_argmax_rows(x, n, rows, row_stride, out, nullptr, workspace, workspace_size, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -51,7 +51,7 @@ struct mi355x_backend {
     void *fx = nullptr;      // its arrival counters (zeroed at allocation) and records
     size_t fx_size = 0;
     int fx_nsb = 0;          // the superblock count the counters' rounds are aligned to
-    void *am = nullptr;      // the ARGMAX nodes' arrival counter and partials (kq_argmax.hip), zeroed at
+    void *am = nullptr;      // the ARGMAX / ARGMAX_BATCH nodes' arrival counters and partials (kq_argmax.hip), zeroed at
     size_t am_size = 0;      // allocation; every launch leaves them ready for the next
     bool layer_engine = false;  // each decode layer as one persistent launch (kq_layer.hip)
     uint32_t *ly_sync = nullptr;  // the persistent layers' counter blocks (zeroed at allocation), then err
@@ -345,6 +345,25 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
                                          (int32_t *)t->src[3]->data, tab->ne[1], t->src[3]->ne[0], (int)tab->ne[0]};
             return kq::launch_argmax((const float *)t->src[0]->data, n, (int32_t *)t->data, &step, b->am, b->am_size, st);
         }
+        case MI355X_OP_ARGMAX_BATCH: {
+            const mi355x_tensor *x = t->src[0];
+            if (t->op_params[0] == 0)
+                return kq::launch_argmax_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], (int32_t *)t->data,
+                                              nullptr, b->am, b->am_size, st);
+            const mi355x_tensor *mask = t->src[3], *hist = t->src[4];
+            kq::ArgmaxRowsStep step;
+            step.pos = (int32_t *)t->src[1]->data;
+            step.cells = (int32_t *)t->src[2]->data;
+            step.mask = (float *)mask->data;
+            step.hist = (int32_t *)hist->data;
+            step.mask_stride = (int64_t)(mask->nb[1] / 4);
+            step.hist_stride = (int64_t)(hist->nb[1] / 4);
+            step.n_kv = t->op_params[2];
+            step.n_hist = hist->ne[0];
+            step.cell_stride = t->op_params[1];
+            return kq::launch_argmax_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], (int32_t *)t->data, &step,
+                                          b->am, b->am_size, st);
+        }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(t, d);
@@ -567,12 +586,14 @@ int ensure_attn_oproj_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, con
     return MI355X_OK;
 }
 
-// the ARGMAX nodes' counter and partials: sized for the longest vector, zeroed when (re)allocated.
+// the ARGMAX and ARGMAX_BATCH nodes' counters and partials: sized for the largest, zeroed when (re)allocated.
 // The nodes of a graph run one after the other on the backend stream, so they share it.
 int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
     size_t need = 0;
     for (int i = 0; i < n_nodes; ++i)
         if (nodes[i]->op == MI355X_OP_ARGMAX) need = std::max(need, kq::argmax_workspace(nodes[i]->src[0]->ne[0]));
+        else if (nodes[i]->op == MI355X_OP_ARGMAX_BATCH)
+            need = std::max(need, kq::argmax_rows_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
     if (need <= b->am_size) return MI355X_OK;
     hipStreamSynchronize(b->stream);
     drop_graph(b);

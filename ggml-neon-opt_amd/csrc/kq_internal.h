@@ -282,6 +282,23 @@ int argmax_plan(int64_t n, int *workgroups, int64_t *slice);
 size_t argmax_workspace(int64_t n);
 int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *step, void *ws, size_t ws_size,
                   hipStream_t stream);
+// The argmax of each of `rows` rows of an f32 matrix in one launch (kq_argmax_rows; row_stride in
+// floats): a row is split as argmax_plan(n) splits a vector. argmax_rows_workspace: per row a
+// counter on a line of its own and the words of the largest split, the same for every n
+// (0 outside 1 <= n <= 2^24, 1 <= rows <= 65535).
+// step: the step-inputs form (the ARGMAX_BATCH node's op_params[0] == 1): `out` is the batch
+// graph's tokens, and row i's pos / cells / mask row / history row are advanced with it.
+constexpr int64_t kArgmaxMaxRows = 65535;
+struct ArgmaxRowsStep {
+    int32_t *pos, *cells;  // [rows]
+    float *mask;           // [rows][mask_stride], n_kv entries of a row in use
+    int32_t *hist;         // [rows][hist_stride], n_hist entries of a row in use
+    int64_t mask_stride, hist_stride, n_kv, n_hist;
+    int cell_stride;
+};
+size_t argmax_rows_workspace(int64_t n, int64_t rows);
+int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
+                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream);
 
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from

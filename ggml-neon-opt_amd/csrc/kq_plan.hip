@@ -656,6 +656,30 @@ bool supports_op(const mi355x_tensor *op) {
                 return false;
             return op->ne[0] == 2 + tab->ne[0];
         }
+        case MI355X_OP_ARGMAX_BATCH: {
+            // f32 [n, T] of mi355x_argmax_rows' sizes, rows packed and 16-B aligned -> I32 [T]; the
+            // step-inputs form: pos [T], cells [T], the f32 mask [>= n_kv, T], the history [n_hist, T]
+            const mi355x_tensor *x = op->src[0];
+            if (!x || x->type != MI355X_TYPE_F32 || !x->data || ((uintptr_t)x->data & 15u) || x->nb[0] != 4) return false;
+            const int64_t n = x->ne[0], T = x->ne[1];
+            if (n < 1 || n > kArgmaxMaxN || n % 4 || T < 1 || T > kArgmaxMaxRows || nelem(x) != n * T) return false;
+            if (x->nb[1] != (size_t)n * 4) return false;
+            auto i32_vec = [T](const mi355x_tensor *t) {
+                return t && t->type == MI355X_TYPE_I32 && t->data && t->nb[0] == 4 && t->ne[0] == T && nelem(t) == T;
+            };
+            if (!i32_vec(op)) return false;
+            if (op->op_params[0] == 0) return true;
+            if (op->op_params[0] != 1) return false;
+            const mi355x_tensor *mask = op->src[3], *hist = op->src[4];
+            const int64_t n_kv = op->op_params[2];
+            if (!i32_vec(op->src[1]) || !i32_vec(op->src[2]) || op->op_params[1] < 1 || n_kv < 1) return false;
+            if (!mask || mask->type != MI355X_TYPE_F32 || !mask->data || mask->nb[0] != 4 || mask->ne[0] < n_kv ||
+                mask->ne[1] != T || nelem(mask) != mask->ne[0] * T || mask->nb[1] % 4 || mask->nb[1] < (size_t)n_kv * 4)
+                return false;
+            return hist && hist->type == MI355X_TYPE_I32 && hist->data && hist->nb[0] == 4 && hist->ne[0] >= 1 &&
+                   hist->ne[0] <= 0x7fffffff && hist->ne[1] == T && nelem(hist) == hist->ne[0] * T && hist->nb[1] % 4 == 0 &&
+                   hist->nb[1] >= (size_t)hist->ne[0] * 4;
+        }
         default:
             return false;
     }

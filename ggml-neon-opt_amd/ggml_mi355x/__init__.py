@@ -28,6 +28,7 @@ OP_NONE, OP_MUL_MAT, OP_GET_ROWS, OP_RMS_NORM, OP_MUL, OP_ADD, OP_SWIGLU, OP_ROP
 OP_ATTN_BATCH = 11
 OP_ARGMAX = 12  # op_params[0]: ARGMAX_PLAIN / ARGMAX_STEP_INPUTS
 ARGMAX_PLAIN, ARGMAX_STEP_INPUTS = 0, 1
+OP_ARGMAX_BATCH = 13  # the argmax of every row; op_params[0]: ARGMAX_PLAIN / ARGMAX_STEP_INPUTS
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -73,6 +74,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
     "mi355x_debug_rows_plan",
     "mi355x_argmax_plan", "mi355x_argmax_workspace_size", "mi355x_argmax",
+    "mi355x_argmax_rows_workspace_size", "mi355x_argmax_rows",
 )
 
 
@@ -258,6 +260,11 @@ def lib():
         L.mi355x_argmax_workspace_size.restype = sz
         L.mi355x_argmax.argtypes = [vp, i64, vp, vp, sz, vp]
         L.mi355x_argmax.restype = i32
+    if hasattr(L, "mi355x_argmax_rows"):
+        L.mi355x_argmax_rows_workspace_size.argtypes = [i64, i64]
+        L.mi355x_argmax_rows_workspace_size.restype = sz
+        L.mi355x_argmax_rows.argtypes = [vp, i64, i64, i64, vp, vp, sz, vp]
+        L.mi355x_argmax_rows.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -760,6 +767,44 @@ def argmax(x, out=None, workspace=None, stream=None):
             torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
     _check(_argmax_lib().mi355x_argmax(x.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                        _stream(stream)), "mi355x_argmax")
+    return out
+
+
+def _argmax_rows_lib():
+    L = lib()
+    if not hasattr(L, "mi355x_argmax_rows"):
+        raise Mi355xError(f"{LIB_PATH} has no mi355x_argmax_rows (a library built before it)")
+    return L
+
+
+def argmax_rows_workspace_size(n, rows):
+    """Bytes of mi355x_argmax_rows' workspace for `rows` rows of n entries (0: n outside 1 .. 2^24
+    or rows outside 1 .. 65535)."""
+    return int(_argmax_rows_lib().mi355x_argmax_rows_workspace_size(n, rows))
+
+
+def argmax_rows(x, out=None, workspace=None, stream=None):
+    """mi355x_argmax_rows: argmax's rule on every row of x, a 2-D f32 cuda tensor [T, n] with unit
+    column stride (the row stride is free: >= n and a multiple of 4 floats), as an int32 cuda
+    tensor [T] (no synchronization). workspace: a uint8 cuda tensor of
+    argmax_rows_workspace_size(n, T) bytes, zeroed once by its owner and reusable call after call
+    on one stream; None: a fresh zeroed one."""
+    torch = _torch()
+    _require_device()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and
+            x.stride(1) == 1):
+        raise Mi355xError("argmax_rows: x must be a 2-D float32 cuda tensor with unit column stride")
+    rows, n = x.shape
+    out = torch.empty(rows, dtype=torch.int32, device=x.device) if out is None else out
+    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= rows):
+        raise Mi355xError("argmax_rows: out must be a contiguous int32 cuda tensor of one entry per row")
+    if workspace is None:
+        workspace = torch.zeros(argmax_rows_workspace_size(n, rows) or 1, dtype=torch.uint8, device=x.device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
+    stride = x.stride(0) if rows > 1 else (n + 3) & ~3  # (one row: torch's stride of it means nothing)
+    _check(_argmax_rows_lib().mi355x_argmax_rows(x.data_ptr(), n, rows, stride, out.data_ptr(), workspace.data_ptr(),
+                                                 workspace.numel(), _stream(stream)), "mi355x_argmax_rows")
     return out
 
 

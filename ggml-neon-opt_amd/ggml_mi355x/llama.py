@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (ARGMAX_STEP_INPUTS, FLAG_OUTPUT, OP_ADD, OP_ARGMAX, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
+from . import (ARGMAX_STEP_INPUTS, FLAG_OUTPUT, OP_ADD, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
                OP_MUL_MAT,
                OP_RMS_NORM,
                OP_SWIGLU, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table)
@@ -425,22 +425,39 @@ class LlamaDecoder:
         [0, n_kv) under mask[i] (additive: 0 visible, -inf hidden; [T, >= n_kv] floats, numpy or
         torch on the host). Returns the device logits [T, n_vocab]. The graph of a (T, n_kv)
         pair is built once and replayed with new input contents."""
+        m = self._check_batch("step_batch", tokens, pos, cells, mask, n_kv)
+        g = self._batch_graph(len(tokens), n_kv)
+        L = self._stage_batch(g, tokens, pos, cells, m)
+        rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
+        if rc:
+            raise Mi355xError(f"graph_compute failed ({rc})")
+        return g["logits"]
+
+    def _check_batch(self, who: str, tokens, pos, cells, mask, n_kv: int):
+        """The argument checks of a batch step, raised in the name of the caller `who` (nothing is
+        enqueued); returns the mask as a float32 tensor."""
         import numpy as np
         import torch
         n_tok = len(tokens)
         if n_tok < 1 or len(pos) != n_tok or len(cells) != n_tok:
-            raise Mi355xError("step_batch: tokens, pos and cells need one entry per token")
+            raise Mi355xError(f"{who}: tokens, pos and cells need one entry per token")
         if n_kv < 32 or n_kv % 32 or n_kv > self.n_ctx:
-            raise Mi355xError(f"step_batch: n_kv {n_kv} must be a multiple of 32 in [32, n_ctx {self.n_ctx}]")
+            raise Mi355xError(f"{who}: n_kv {n_kv} must be a multiple of 32 in [32, n_ctx {self.n_ctx}]")
         if any(not 0 <= t < self.hp["n_vocab"] for t in tokens):
-            raise Mi355xError("step_batch: token outside the vocabulary")
+            raise Mi355xError(f"{who}: token outside the vocabulary")
         if any(not 0 <= c < self.n_ctx for c in cells) or any(not 0 <= p < self.n_ctx for p in pos):
-            raise Mi355xError(f"step_batch: cell or position outside the KV cache (n_ctx {self.n_ctx})")
+            raise Mi355xError(f"{who}: cell or position outside the KV cache (n_ctx {self.n_ctx})")
         m = torch.as_tensor(np.asarray(mask, dtype=np.float32) if not torch.is_tensor(mask) else mask).to(torch.float32)
         if m.dim() != 2 or m.shape[0] != n_tok or m.shape[1] < n_kv:
-            raise Mi355xError(f"step_batch: mask must be [{n_tok}, >= {n_kv}]")
+            raise Mi355xError(f"{who}: mask must be [{n_tok}, >= {n_kv}]")
+        return m
+
+    def _stage_batch(self, g, tokens, pos, cells, m):
+        """(tokens | pos | cells | mask) from a pinned row into the batch graph's input block."""
+        import torch
         from . import lib
-        g = self._batch_graph(n_tok, n_kv)
+        n_tok = len(tokens)
+        n_kv = (g["inp"].numel() - 3 * n_tok) // n_tok
         if g["slot"] == self.BATCH_SLOTS:  # a pinned staging row is reused only after its copy is done
             self.b.synchronize()
             g["slot"] = 0
@@ -454,10 +471,110 @@ class LlamaDecoder:
         rc = L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel())
         if rc:
             raise Mi355xError(f"set_tensor failed ({rc})")
-        rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
-        if rc:
-            raise Mi355xError(f"graph_compute failed ({rc})")
-        return g["logits"]
+        return L
+
+    # ------------------------------------------------------------ greedy generation of several sequences
+    def _generate_batch_graph(self, n_tok: int, n_kv: int, cell_stride: int):
+        """_batch_graph(n_tok, n_kv)'s nodes plus one step-inputs ARGMAX_BATCH on the logits: it ends
+        the step by writing every sequence's next token, position and cell into that graph's own
+        input block, showing the new cell in the sequence's mask row and filing the token in
+        self.batch_history[i][pos + 1], so the one captured graph is replayed with no host copy."""
+        import torch
+        key = (n_tok, n_kv, cell_stride)
+        cached = getattr(self, "_gen_batches", {}).get(key)
+        if cached is not None:
+            return cached
+        g = self._batch_graph(n_tok, n_kv)
+        if not hasattr(self, "_gen_batches"):
+            self._gen_batches, self._batch_hists = {}, {}
+        gens, hists = self._gen_batches, self._batch_hists
+        if n_tok not in hists:  # one per T: every step, the last cell's included, has an entry
+            hists[n_tok] = dict(dev=torch.zeros((n_tok, self.n_ctx + 1), dtype=torch.int32, device=g["inp"].device),
+                                host=torch.zeros((n_tok, self.n_ctx + 1), dtype=torch.int32).pin_memory())
+        hist, inp, T = hists[n_tok]["dev"], g["inp"], n_tok
+        srcs = [g["nodes"][-1],
+                make_tensor(TYPE_I32, T, 1, inp[T:2 * T].data_ptr()),
+                make_tensor(TYPE_I32, T, 1, inp[2 * T:3 * T].data_ptr()),
+                make_tensor(TYPE_F32, n_kv, T, inp[3 * T:].data_ptr()),
+                make_tensor(TYPE_I32, self.n_ctx + 1, T, hist.data_ptr())]
+        am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_ARGMAX_BATCH, srcs=srcs,
+                         op_params=[ARGMAX_STEP_INPUTS, cell_stride, n_kv], flags=FLAG_OUTPUT)
+        nodes = g["nodes"] + [am]
+        gg = dict(batch=g, nodes=nodes, keep=srcs + [am], hist=hists[n_tok],
+                  arr=(ctypes.POINTER(type(am)) * len(nodes))(*[ctypes.pointer(n) for n in nodes]))
+        gens[key] = gg
+        torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
+        return gg
+
+    def generate_batch(self, tokens, pos, cells, mask, n: int, n_kv: int, cell_stride: int = 1, eos=None,
+                       chunk: int = 32, use_graph: bool = True):
+        """Greedy decoding of n steps of T sequences together: sequence i starts from tokens[i] at
+        position pos[i] in cache cell cells[i] under mask[i] (step_batch's inputs), and its step k
+        runs at position pos[i] + k in cell cells[i] + k * cell_stride. Returns a list of T lists of
+        ints: sequence i's tokens, each the argmax of its row of that step's logits
+        (mi355x_argmax's rule). The inputs are staged from the host once; then the graph runs
+        `chunk` times back to back, each step's ARGMAX_BATCH node staging the next (tokens,
+        positions, cells, and the new cell made visible in its own sequence's mask row), and only
+        after a chunk the host synchronizes and reads the chunk's tokens from the history
+        (self.batch_history, int32 [T, n_ctx + 1]: row i holds the token picked at position p in
+        entry p + 1). No mask is rebuilt or copied per step, so the cells the steps after the
+        first will write must be hidden (-inf) in every row of `mask`: the device shows each to
+        its own sequence when its turn comes, and to no other sequence ever.
+        eos: a sequence's list ends with its first such token; the call returns when every
+        sequence has ended or after n steps. A finished sequence keeps running on the device to
+        the end of the call's steps (the last chunk's included): its later cells and history
+        entries are written too. A following step_batch or generate_batch works as ever: it
+        restages the whole input block."""
+        import numpy as np
+        if self.split is not None:
+            raise Mi355xError("generate_batch runs on one GPU (no row split)")
+        m = self._check_batch("generate_batch", tokens, pos, cells, mask, n_kv)
+        T = len(tokens)
+        if n < 0 or chunk < 1 or cell_stride < 1:
+            raise Mi355xError(f"generate_batch: n {n}, chunk {chunk} and cell_stride {cell_stride} must be >= 0, >= 1 "
+                              "and >= 1")
+        if self.hp["n_vocab"] % 4:
+            raise Mi355xError("generate_batch: the vocabulary must be a multiple of 4 entries (ARGMAX_BATCH's rows)")
+        if n == 0:
+            return [[] for _ in range(T)]
+        if any(c + (n - 1) * cell_stride >= n_kv for c in cells) or any(p + n - 1 >= self.n_ctx for p in pos):
+            raise Mi355xError(f"generate_batch: {n} steps leave the cells [0, n_kv {n_kv}) or the positions "
+                              f"[0, n_ctx {self.n_ctx})")
+        written = np.asarray(cells, dtype=np.int64)[:, None] + cell_stride * np.arange(n, dtype=np.int64)[None, :]
+        if np.unique(written).size != written.size:
+            raise Mi355xError("generate_batch: two steps would write the same cache cell")
+        if not np.isneginf(m[:, :n_kv].numpy()[:, written[:, 1:].ravel()]).all():
+            raise Mi355xError("generate_batch: a cell that a later step writes is visible in the mask (every such cell "
+                              "must be -inf in every row; the device shows it to its own sequence)")
+        g = self._generate_batch_graph(T, n_kv, cell_stride)
+        self.batch_history = g["hist"]["dev"]
+        L = self._stage_batch(g["batch"], tokens, pos, cells, m)
+        dev, host = g["hist"]["dev"], g["hist"]["host"]
+        out, live, done = [[] for _ in range(T)], [True] * T, 0
+        while done < n and any(live):
+            c = min(chunk, n - done)
+            for _ in range(c):
+                rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
+                if rc:
+                    raise Mi355xError(f"graph_compute failed ({rc})")
+            # the chunk's tokens of sequence i: history[i][p + 1] for its steps at p
+            for i in range(T):
+                lo = pos[i] + done + 1
+                rc = L.mi355x_backend_get_tensor(self.b.h, host[i, lo:].data_ptr(), dev[i, lo:].data_ptr(), 4 * c)
+                if rc:
+                    raise Mi355xError(f"get_tensor failed ({rc})")
+            self.b.synchronize()
+            for i in range(T):
+                if not live[i]:
+                    continue
+                lo = pos[i] + done + 1
+                for t in host[i, lo:lo + c].tolist():
+                    out[i].append(t)
+                    if eos is not None and t == eos:
+                        live[i] = False
+                        break
+            done += c
+        return out
 
     def _stage_inputs(self, token: int, pos: int):
         """(token, pos, the position's rope row) from a pinned slot into the input block."""

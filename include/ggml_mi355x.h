@@ -509,6 +509,24 @@ int mi355x_argmax_plan(int64_t n, int *workgroups, int64_t *slice);
 size_t mi355x_argmax_workspace_size(int64_t n);
 int mi355x_argmax(const float *x, int64_t n, int32_t *out, void *workspace, size_t workspace_size, void *stream);
 
+/* mi355x_argmax of each of `rows` rows of an f32 matrix in one launch: out[i] = the argmax of
+ * x[i * row_stride .. + n), by the same rule (smallest index of the maximum of the non-NaN
+ * entries, -0.0 == +0.0, all NaN gives 0). Grid (workgroups per row, rows): a row is split as
+ * mi355x_argmax_plan(n) splits a vector and handed off on a counter of its own, so a row reduces
+ * exactly as mi355x_argmax reduces it alone. row_stride is in floats, >= n; x and row_stride * 4
+ * must be 16-B aligned (n itself need not be a multiple of 4). 1 <= n <= 2^24, 1 <= rows <= 65535.
+ * mi355x_argmax_rows_workspace_size: per row a counter on a 128-B line of its own and the words
+ * of the largest split, 2176 bytes a row whatever n is (0 for an n or rows outside the ranges),
+ * so one workspace serves call after call of any n and any rows it is large enough for. The caller owns the workspace (8-B aligned) and
+ * zeroes it once before the first call; every call leaves it ready for the next; two calls that
+ * can run concurrently must not share one. Returns MI355X_E_INVAL (null or misaligned x, a
+ * row_stride below n or not 16-B aligned in bytes, null out, n or rows outside the range),
+ * MI355X_E_WORKSPACE (missing or too small) or MI355X_E_NODEVICE, in that order, before any device
+ * access. */
+size_t mi355x_argmax_rows_workspace_size(int64_t n, int64_t rows);
+int mi355x_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out, void *workspace,
+                       size_t workspace_size, void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -565,12 +583,26 @@ int mi355x_argmax(const float *x, int64_t n, int32_t *out, void *workspace, size
  *                pos + 1 if pos + 1 < rows (else left alone), history[pos + 1] = the index if
  *                pos + 1 < n_hist (unsigned compares). pos + 1 is written even at the end of
  *                the cache: a further replay meets ATTN_DECODE's position outside the cache
- *                (NaN output, caches untouched). */
+ *                (NaN output, caches untouched).
+ *   ARGMAX_BATCH mi355x_argmax_rows of src0, f32 [n, T] with packed rows (nb[1] = 4 n, n % 4 == 0,
+ *                1 <= n <= 2^24, 1 <= T <= 65535), 16-B aligned; one launch, never fused or
+ *                elided; the rows' counters and partials belong to the backend. op_params[0] = 0:
+ *                -> I32 [T], the rows' indices. op_params[0] = 1, the step-inputs form (greedy
+ *                decoding of several sequences without the host, LlamaDecoder.generate_batch):
+ *                src1 I32 pos [T], src2 I32 cells [T], src3 F32 mask [>= n_kv, T] (nb[1] the row
+ *                stride), src4 I32 history [n_hist, T] (nb[1] the row stride), op_params[1] =
+ *                cell_stride >= 1, op_params[2] = n_kv -> I32 [T], the tokens. For row i, with
+ *                tok its index, p = pos[i] + 1 and c = cells[i] + cell_stride: dst[i] = tok,
+ *                pos[i] = p, cells[i] = c, mask[i][c] = 0.0f if c < n_kv, history[i][p] = tok if
+ *                p < n_hist (unsigned compares: a negative or overrun value writes nothing
+ *                outside its array). p and c are written even at the end of the cache: a
+ *                further replay meets ATTN_BATCH's cell or position outside the cache (NaN row,
+ *                caches untouched). An F16 mask or I64 cells are not taken. */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
-    MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12,
+    MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */
