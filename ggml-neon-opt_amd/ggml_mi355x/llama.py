@@ -1,29 +1,41 @@
-"""The llama decode graph (llm_build_llama, one token, non-flash attention) as
-ggml-mirror nodes on the MI355X backend.
+"""llm_build_llama (non-flash attention) as ggml-mirror nodes on the MI355X backend
+(SURVEY.md §8f rank 4), for one token, a prompt and a batch of several sequences.
 
 The reference builds this graph in llama.cpp (llama_model::build_graph ->
 llm_build_llama, artifacts/perf/out.folded:249-251) and ggml-cpu computes it node by
 node (ggml_graph_compute_thread -> ggml_compute_forward, out.folded:91-234). Here the
 same nodes go to mi355x_backend_graph_compute, which fuses RMS_NORM -> MUL -> MUL_MAT,
-SWIGLU -> MUL_MAT and MUL_MAT -> ADD into the GEMV launches, and replays the token's
-launches from a hipGraph (the node list is identical for every token; the token id
-and position are device inputs written before each step, as ggml's inp_tokens /
-inp_pos are).
+SWIGLU -> MUL_MAT and MUL_MAT -> ADD into the GEMV launches, and replays a graph's
+launches from a hipGraph (a node list is identical for every step; the token ids,
+positions and the rest of ggml's inp_* tensors are device inputs written before each
+step).
 
 Per layer:
-  rms_norm(x)*attn_norm -> q, k, v (MUL_MAT) -> ATTN_DECODE (rope, f16 KV cache,
-  KQ, soft_max, KQV) -> attn_output (MUL_MAT) -> +x -> rms_norm*ffn_norm ->
+  rms_norm(x)*attn_norm -> q, k, v (MUL_MAT) -> attention (rope, f16 KV cache, KQ,
+  soft_max, KQV) -> attn_output (MUL_MAT) -> +x -> rms_norm*ffn_norm ->
   gate, up (MUL_MAT) -> swiglu -> down (MUL_MAT) -> +ffn_inp
 then rms_norm*output_norm -> output (MUL_MAT) -> logits.
+
+LlamaDecoder's entry points and the graph each runs; all of them are emitted by the one
+layer body and the one head below (LlamaDecoder._layers, ._head) over a _Graph:
+  step            the token graph, built with the decoder: one row, ATTN_DECODE; under a
+                  row split with the ALL_GATHER / ALL_REDUCE nodes of its mode
+  prompt          _prompt_graph(n_tok): n_tok rows, ATTN_DECODE over the batch, the last
+                  layer's inp_out_ids selection, logits of the last token
+  step_batch      _batch_graph(n_tok, n_kv): n_tok rows of any sequences, ATTN_BATCH with
+                  cells and mask from the inputs, logits of every row
+  generate,       the token graph / the batch graph plus one ARGMAX / ARGMAX_BATCH node
+  generate_batch  that stages the next step's inputs on the device
 """
 from __future__ import annotations
 
 import ctypes
 
-from . import (ARGMAX_STEP_INPUTS, FLAG_OUTPUT, OP_ADD, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL,
-               OP_MUL_MAT,
-               OP_RMS_NORM,
-               OP_SWIGLU, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table)
+from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ARGMAX,
+               OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL, OP_MUL_MAT, OP_RMS_NORM,
+               OP_SWIGLU, QK_K, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor,
+               rope_table)
+
 
 def torch_tensor(values):
     import torch
@@ -42,8 +54,66 @@ TINYLLAMA = hparams(2048, 22, 32, 4, 5632, 32000)
 LLAMA3_8B = hparams(4096, 32, 32, 8, 14336, 128256, eps=1e-5, freq_base=500000.0)
 
 
+def _check(rc, what):
+    if rc:
+        raise Mi355xError(f"{what} failed ({rc})")
+
+
+def _node_array(nodes):
+    return (ctypes.POINTER(type(nodes[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes])
+
+
+class _Graph:
+    """One graph under construction: its node list, every node's zeroed f32 output buffer and
+    every Tensor descriptor (kept alive here; the nodes point at them)."""
+
+    def __init__(self, hp, weights):
+        self.hp, self.w, self.dev = hp, weights, weights["output_norm"].device
+        self.tensors, self.bufs, self.nodes = [], [], []
+
+    def leaf(self, t, type_, ne0, ne1=1, row_stride=None):
+        x = make_tensor(type_, ne0, ne1, t.data_ptr(), row_stride=row_stride)
+        self.tensors.append(x)
+        return x
+
+    def node(self, op, n, srcs, params=None, flags=0, ne1=1):
+        """A node of ne1 rows of n floats: (its descriptor, its output buffer)."""
+        import torch
+        b = torch.zeros(n * ne1, dtype=torch.float32, device=self.dev)
+        self.bufs.append(b)
+        x = make_tensor(TYPE_F32, n, ne1, b.data_ptr(), op=op, srcs=srcs, op_params=params, flags=flags)
+        self.tensors.append(x)
+        self.nodes.append(x)
+        return x, b
+
+    def mat(self, name):
+        """The leaf of a K-quant matrix (type, uint8 [rows, rowbytes])."""
+        t, w = self.w[name]
+        return self.leaf(w, t, w.shape[1] // BLOCK_BYTES[t] * QK_K, w.shape[0], row_stride=w.stride(0))
+
+    def mm(self, name, x, flags=0):
+        wt = self.mat(name)
+        return self.node(OP_MUL_MAT, wt.ne[1], [wt, x], flags=flags, ne1=x.ne[1])
+
+    def embed(self, tok):
+        et, ew = self.w["token_embd"]
+        emb_t = self.leaf(ew, et, self.hp["n_embd"], ew.shape[0], row_stride=ew.stride(0) * ew.element_size())
+        return self.node(OP_GET_ROWS, self.hp["n_embd"], [emb_t, tok], ne1=tok.ne[0])
+
+    def norm(self, x, name):
+        """rms_norm(x) * the norm weight `name`, over x's rows."""
+        n, _ = self.node(OP_RMS_NORM, x.ne[0], [x], [f32_bits(self.hp["eps"])], ne1=x.ne[1])
+        return self.node(OP_MUL, x.ne[0], [n, self.leaf(self.w[name], TYPE_F32, x.ne[0])], ne1=x.ne[1])[0]
+
+    def arr(self):
+        return _node_array(self.nodes)
+
+
 class LlamaDecoder:
-    """Device state and node list of one decode token.
+    """Device state (weights, KV caches, rope table) of one llama model and the graphs that run
+    on it: the token graph built here (step, generate) and, built at first use and kept, one
+    prompt graph per length (prompt) and one batch graph per (tokens, cells) pair (step_batch,
+    generate_batch). Every graph reads the same weights, caches and table.
 
     weights: dict with "token_embd", "output", "output_norm" and per layer i
     "blk.{i}.<name>" for name in LAYER_MATS + ("attn_norm", "ffn_norm"); a K-quant
@@ -53,7 +123,8 @@ class LlamaDecoder:
     matrices in `weights` are then the rank's row slices (TokenSplit.slice_weights),
     the KV caches hold the rank's KV heads, and every stage's slice is ALL_GATHERed
     (RCCL, the backend's communicator) before the next stage reads it. The logits
-    (and every gathered vector) are bit-identical to the single-GPU token.
+    (and every gathered vector) are bit-identical to the single-GPU token. Only the
+    token graph is split: prompt, step_batch and the generate calls refuse.
     """
 
     HOST_SLOTS = 1024
@@ -68,147 +139,35 @@ class LlamaDecoder:
         import torch
         self.b, self.hp, self.w, self.n_ctx, self.split = backend, hp, weights, n_ctx, split
         dev = weights["output_norm"].device
-        E, F, V = hp["n_embd"], hp["n_ff"], hp["n_vocab"]
-        hd, nh, nkv = hp["head_dim"], hp["n_head"], hp["n_head_kv"]
-        world = split.world if split is not None else 1
-        if split is not None:
-            nh, nkv = split.n_head, split.n_head_kv  # this rank's heads
-        kvw = nkv * hd
+        hd = hp["head_dim"]
+        kvw = (split.n_head_kv if split is not None else hp["n_head_kv"]) * hd  # this rank's KV heads
         self.gathers = []  # (node output buffer) of every ALL_GATHER, in graph order
         self.reduces = []  # (input partial, output) buffers of every ALL_REDUCE (split mode "reduce")
-        reduce_mode = split is not None and split.mode == "reduce"
-        f32 = torch.float32
-
-        def buf(n, dtype=f32):
-            return torch.zeros(n, dtype=dtype, device=dev)
-
+        self._prompts, self._batches, self._gen_batches, self._batch_hists, self._gen = {}, {}, {}, {}, None
         # inp_tokens, inp_pos and the rope row of that position side by side: one
         # set_tensor of 8 + 4*head_dim bytes per token. The attention reads its cos/sin
         # with q/k/v instead of after the position (one dependent round trip less);
         # the row is the table's row, so the values are those of the device table.
-        self.inp = buf(2 + hd, torch.int32)
+        self.inp = torch.zeros(2 + hd, dtype=torch.int32, device=dev)
         self.token, self.pos = self.inp[0:1], self.inp[1:2]
         if backend is not None:
             self.table = rope_table(n_ctx, hd, hp["freq_base"], 1.0, device=dev, stream=backend.stream)
             self._table_host = self.table.cpu().reshape(n_ctx, hd).view(torch.int32)
         else:
-            self.table = torch.zeros(n_ctx * hd, dtype=f32, device=dev)
+            self.table = torch.zeros(n_ctx * hd, dtype=torch.float32, device=dev)
         self.k_cache = [torch.zeros((n_ctx, kvw), dtype=torch.int16, device=dev) for _ in range(hp["n_layer"])]
         self.v_cache = [torch.zeros((kvw, n_ctx), dtype=torch.int16, device=dev) for _ in range(hp["n_layer"])]
-        self._bufs = []
-        self.nodes = []
-        T = []  # keeps every Tensor alive
 
-        def leaf(t, type_, ne0, ne1=1, row_stride=None):
-            x = make_tensor(type_, ne0, ne1, t.data_ptr(), row_stride=row_stride)
-            T.append(x)
-            return x
-
-        def node(op, n, srcs, params=None, flags=0, ne1=1):
-            b = buf(n)
-            self._bufs.append(b)
-            x = make_tensor(TYPE_F32, n, ne1, b.data_ptr(), op=op, srcs=srcs, op_params=params, flags=flags)
-            T.append(x)
-            self.nodes.append(x)
-            return x, b
-
-        def mat(name):
-            t, w = weights[name]
-            return leaf(w, t, w.shape[1] * 256 // {12: 144, 13: 176, 14: 210}[t], w.shape[0], row_stride=w.stride(0))
-
-        def mm(name, x):
-            wt = mat(name)
-            return node(OP_MUL_MAT, wt.ne[1], [wt, x])[0]
-
-        def gather(part, n_local, flags=0):
-            """ALL_GATHER of a row-split stage's slice (emitted for every split, a
-            world-1 split included: one RCCL copy; none without a split)."""
-            if split is None:
-                return part, None
-            full, b = node(OP_ALL_GATHER, n_local * world, [part], flags=flags)
-            self.gathers.append(b)
-            return full, b
-
-        def allreduce(part, part_buf):
-            """ALL_REDUCE(sum) of a K-split stage's partial (reduce mode)."""
-            full, b = node(OP_ALL_REDUCE, part.ne[0], [part])
-            self.reduces.append((part_buf, b))
-            return full, b
-
-        def rows_view(t_buf, lo, n):
-            """The rows [lo, lo+n) of a full f32 vector (the residual of a local slice)."""
-            return leaf(t_buf[lo:lo + n], TYPE_F32, n)
-
-        El = E // world
-        r_e0 = split.rows["attn_output"][0] if split is not None else 0
-
-        eps_bits = [f32_bits(hp["eps"])]
-        tok = leaf(self.token, TYPE_I32, 1)
-        pos = leaf(self.pos, TYPE_I32, 1)
+        g = self._graph = _Graph(hp, weights)
+        tok = g.leaf(self.token, TYPE_I32, 1)
+        pos = g.leaf(self.pos, TYPE_I32, 1)
         if rope_src == "row":
-            tab = leaf(self.inp[2:], TYPE_F32, hd, 1)  # the position's rope row (ne1 = 1)
+            tab = g.leaf(self.inp[2:], TYPE_F32, hd, 1)  # the position's rope row (ne1 = 1)
         else:
-            tab = leaf(self.table, TYPE_F32, hd, n_ctx)
-        et, ew = weights["token_embd"]
-        emb_t = leaf(ew, et, E, ew.shape[0], row_stride=ew.stride(0) * ew.element_size())
-        x, xb = node(OP_GET_ROWS, E, [emb_t, tok])
-        scale = f32_bits(float(torch.tensor(1.0) / torch.sqrt(torch.tensor(float(hd)))))
-        for i in range(hp["n_layer"]):
-            p = f"blk.{i}."
-            n1, _ = node(OP_RMS_NORM, E, [x], eps_bits)
-            m1, _ = node(OP_MUL, E, [n1, leaf(weights[p + "attn_norm"], TYPE_F32, E)])
-            q = mm(p + "attn_q", m1)
-            k = mm(p + "attn_k", m1)
-            v = mm(p + "attn_v", m1)
-            kc = leaf(self.k_cache[i], TYPE_F16, kvw, n_ctx)
-            vc = leaf(self.v_cache[i], TYPE_F16, n_ctx, kvw)
-            att, _ = node(OP_ATTN_DECODE, nh * hd, [q, k, v, pos, kc, vc, tab], [nh, nkv, hd, scale])
-            if reduce_mode:
-                # K-split attn_output over the rank's heads; the residual rides on rank 0's
-                # partial, so the ALL_REDUCE delivers mul_mat + x
-                o = mm(p + "attn_output", att)
-                if split.rank == 0:
-                    o, ob = node(OP_ADD, E, [o, x])
-                else:
-                    ob = self._bufs[-1]
-                ffn_inp, fb = allreduce(o, ob)
-            else:
-                att, _ = gather(att, nh * hd)
-                o = mm(p + "attn_output", att)
-                res = x if split is None else rows_view(xb, r_e0, El)
-                ffn_inp, fb = node(OP_ADD, El, [o, res])
-                ffn_inp, fbg = gather(ffn_inp, El)
-                fb = fbg if fbg is not None else fb
-            n2, _ = node(OP_RMS_NORM, E, [ffn_inp], eps_bits)
-            m2, _ = node(OP_MUL, E, [n2, leaf(weights[p + "ffn_norm"], TYPE_F32, E)])
-            gt = mm(p + "ffn_gate", m2)
-            up = mm(p + "ffn_up", m2)
-            glu, _ = node(OP_SWIGLU, gt.ne[0], [gt, up])
-            if reduce_mode:  # the rank's ffn rows are its K slice of ffn_down
-                dn = mm(p + "ffn_down", glu)
-                if split.rank == 0:
-                    dn, db = node(OP_ADD, E, [dn, ffn_inp])
-                else:
-                    db = self._bufs[-1]
-                x, xb = allreduce(dn, db)
-            else:
-                glu, _ = gather(glu, F // world)
-                dn = mm(p + "ffn_down", glu)
-                res = ffn_inp if split is None else rows_view(fb, r_e0, El)
-                x, xb = node(OP_ADD, El, [dn, res])
-                x, xbg = gather(x, El)
-                xb = xbg if xbg is not None else xb
-            self.last_hidden = xb
-        n3, _ = node(OP_RMS_NORM, E, [x], eps_bits)
-        m3, _ = node(OP_MUL, E, [n3, leaf(weights["output_norm"], TYPE_F32, E)])
-        wt = mat("output")
-        if split is None:
-            _, self.logits = node(OP_MUL_MAT, V, [wt, m3], flags=FLAG_OUTPUT)
-        else:
-            lg, _ = node(OP_MUL_MAT, wt.ne[1], [wt, m3])
-            _, self.logits = gather(lg, V // world, flags=FLAG_OUTPUT)
-        self._tensors = T
-        self._arr = (ctypes.POINTER(type(T[0])) * len(self.nodes))(*[ctypes.pointer(n) for n in self.nodes])
+            tab = g.leaf(self.table, TYPE_F32, hd, n_ctx)
+        x, self.last_hidden = self._layers(g, tok, pos, tab, split=split)
+        self.logits = self._head(g, x, split=split)
+        self.nodes, self._arr = g.nodes, g.arr()
         if backend is None:
             return
         # pinned staging slots for (token, pos): a slot is reused only after the stream
@@ -222,6 +181,92 @@ class LlamaDecoder:
         for c in self.k_cache + self.v_cache:
             c.zero_()
 
+    def _run(self, L, g, use_graph, times=1):
+        """Enqueue the graph g (its "arr" and "nodes") `times` times back to back."""
+        for _ in range(times):
+            _check(L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0),
+                   "graph_compute")
+
+    # ------------------------------------------------------------ the one layer body and head
+    def _gather(self, g, split, part, part_buf, n_local, flags=0):
+        """ALL_GATHER of a row-split stage's slice (emitted for every split, a
+        world-1 split included: one RCCL copy; none without a split)."""
+        if split is None:
+            return part, part_buf
+        full, b = g.node(OP_ALL_GATHER, n_local * split.world, [part], flags=flags)
+        self.gathers.append(b)
+        return full, b
+
+    def _layers(self, g, tok, pos, tab, batch=None, out_ids=None, split=None):
+        """Embedding and every layer over tok's rows; returns the last residual and its buffer.
+        batch (cells, mask, n_kv): the attention is an ATTN_BATCH node that takes every row's
+        cache cell and mask row from these; without it ATTN_DECODE (cell == position, causal).
+        out_ids: llm_build_llama's inp_out_ids, applied in the last layer of more than one row.
+        split: the rank's TokenSplit; the gather and reduce arms below are its exchange nodes."""
+        import torch
+        hp = self.hp
+        E, F, hd, n_ctx = hp["n_embd"], hp["n_ff"], hp["head_dim"], self.n_ctx
+        nh, nkv = (split.n_head, split.n_head_kv) if split is not None else (hp["n_head"], hp["n_head_kv"])
+        kvw = nkv * hd
+        world = split.world if split is not None else 1
+        reduce_mode = split is not None and split.mode == "reduce"
+        El = E // world
+        r_e0 = split.rows["attn_output"][0] if split is not None else 0
+        scale = f32_bits(float(torch.tensor(1.0) / torch.sqrt(torch.tensor(float(hd)))))
+
+        def project(name, inp, n_local, res, res_buf, select=None):
+            """MUL_MAT `name` of inp (a slice of n_local under a split) plus the residual res."""
+            if reduce_mode:
+                # K-split over the rank's heads / ffn rows; the residual rides on rank 0's
+                # partial, so the ALL_REDUCE(sum) delivers mul_mat + res
+                o, ob = g.mm(name, inp)
+                if split.rank == 0:
+                    o, ob = g.node(OP_ADD, E, [o, res])
+                full, b = g.node(OP_ALL_REDUCE, o.ne[0], [o])
+                self.reduces.append((ob, b))
+                return full, b
+            inp, _ = self._gather(g, split, inp, None, n_local)
+            o, _ = g.mm(name, inp)
+            if select is not None:
+                # llm_build_llama's inp_out_ids: after the last attention only the rows whose
+                # logits are wanted (the last token's) go on: GET_ROWS of attn_out and inpSA
+                o, _ = g.node(OP_GET_ROWS, E, [o, select])
+                res, _ = g.node(OP_GET_ROWS, E, [res, select])
+            if split is not None:  # the rows [r_e0, r_e0 + El) of the full residual
+                res = g.leaf(res_buf[r_e0:r_e0 + El], TYPE_F32, El)
+            y, yb = g.node(OP_ADD, El, [o, res], ne1=o.ne[1])
+            return self._gather(g, split, y, yb, El)
+
+        x, xb = g.embed(tok)
+        for i in range(hp["n_layer"]):
+            p = f"blk.{i}."
+            m1 = g.norm(x, p + "attn_norm")
+            q, k, v = g.mm(p + "attn_q", m1)[0], g.mm(p + "attn_k", m1)[0], g.mm(p + "attn_v", m1)[0]
+            kc = g.leaf(self.k_cache[i], TYPE_F16, kvw, n_ctx)
+            vc = g.leaf(self.v_cache[i], TYPE_F16, n_ctx, kvw)
+            if batch is None:
+                att, _ = g.node(OP_ATTN_DECODE, nh * hd, [q, k, v, pos, kc, vc, tab], [nh, nkv, hd, scale],
+                                ne1=q.ne[1])
+            else:
+                cells, mask, n_kv = batch
+                att, _ = g.node(OP_ATTN_BATCH, nh * hd, [q, k, v, pos, kc, vc, tab, cells, mask],
+                                [nh, nkv, hd, scale, n_kv], ne1=q.ne[1])
+            last_rows = out_ids if i == hp["n_layer"] - 1 and x.ne[1] > 1 else None
+            ffn_inp, fb = project(p + "attn_output", att, nh * hd, x, xb, select=last_rows)
+            m2 = g.norm(ffn_inp, p + "ffn_norm")
+            gt, up = g.mm(p + "ffn_gate", m2)[0], g.mm(p + "ffn_up", m2)[0]
+            glu, _ = g.node(OP_SWIGLU, gt.ne[0], [gt, up], ne1=gt.ne[1])
+            x, xb = project(p + "ffn_down", glu, F // world, ffn_inp, fb)
+        return x, xb
+
+    def _head(self, g, x, split=None):
+        """output_norm -> output over x's rows; returns the logits' buffer."""
+        m3 = g.norm(x, "output_norm")
+        if split is None:
+            return g.mm("output", m3, flags=FLAG_OUTPUT)[1]
+        lg, lb = g.mm("output", m3)
+        return self._gather(g, split, lg, lb, self.hp["n_vocab"] // split.world, flags=FLAG_OUTPUT)[1]
+
     # ------------------------------------------------------------ prompt processing
     def _prompt_graph(self, n_tok: int):
         """Node list of a prompt batch of n_tok tokens (llm_build_llama over a ubatch,
@@ -232,84 +277,25 @@ class LlamaDecoder:
         through the output norm and head (llama.cpp computes the logits of the last token
         of a prompt)."""
         import torch
-        cached = getattr(self, "_prompts", {}).get(n_tok)
+        cached = self._prompts.get(n_tok)
         if cached is not None:
             return cached
         if self.split is not None:
             raise Mi355xError("prompt processing runs on one GPU (no row split)")
-        hp, weights, n_ctx = self.hp, self.w, self.n_ctx
-        dev = weights["output_norm"].device
-        E, V = hp["n_embd"], hp["n_vocab"]
-        hd, nh, nkv = hp["head_dim"], hp["n_head"], hp["n_head_kv"]
-        kvw = nkv * hd
-        T, bufs, nodes = [], [], []
-        inp = torch.zeros(2 * n_tok + 1, dtype=torch.int32, device=dev)  # token ids | positions | out id
-
-        def leaf(t, type_, ne0, ne1=1, row_stride=None):
-            x = make_tensor(type_, ne0, ne1, t.data_ptr(), row_stride=row_stride)
-            T.append(x)
-            return x
-
-        def node(op, n, srcs, params=None, flags=0, ne1=1):
-            b = torch.zeros(n * ne1, dtype=torch.float32, device=dev)
-            bufs.append(b)
-            x = make_tensor(TYPE_F32, n, ne1, b.data_ptr(), op=op, srcs=srcs, op_params=params, flags=flags)
-            T.append(x)
-            nodes.append(x)
-            return x, b
-
-        def mm(name, x):
-            t, w = weights[name]
-            wt = leaf(w, t, w.shape[1] * 256 // {12: 144, 13: 176, 14: 210}[t], w.shape[0], row_stride=w.stride(0))
-            return node(OP_MUL_MAT, wt.ne[1], [wt, x], ne1=x.ne[1])[0]
-
-        eps_bits = [f32_bits(hp["eps"])]
-        tok = leaf(inp[:n_tok], TYPE_I32, n_tok)
-        pos = leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
-        out_ids = leaf(inp[2 * n_tok:], TYPE_I32, 1)  # inp_out_ids: the last token's row
-        tab = leaf(self.table, TYPE_F32, hd, n_ctx)
-        et, ew = weights["token_embd"]
-        emb_t = leaf(ew, et, E, ew.shape[0], row_stride=ew.stride(0) * ew.element_size())
-        x, xb = node(OP_GET_ROWS, E, [emb_t, tok], ne1=n_tok)
-        scale = f32_bits(float(torch.tensor(1.0) / torch.sqrt(torch.tensor(float(hd)))))
-        for i in range(hp["n_layer"]):
-            p = f"blk.{i}."
-            n1, _ = node(OP_RMS_NORM, E, [x], eps_bits, ne1=n_tok)
-            m1, _ = node(OP_MUL, E, [n1, leaf(weights[p + "attn_norm"], TYPE_F32, E)], ne1=n_tok)
-            q, k, v = mm(p + "attn_q", m1), mm(p + "attn_k", m1), mm(p + "attn_v", m1)
-            kc = leaf(self.k_cache[i], TYPE_F16, kvw, n_ctx)
-            vc = leaf(self.v_cache[i], TYPE_F16, n_ctx, kvw)
-            att, _ = node(OP_ATTN_DECODE, nh * hd, [q, k, v, pos, kc, vc, tab], [nh, nkv, hd, scale], ne1=n_tok)
-            o = mm(p + "attn_output", att)
-            rows = n_tok
-            if i == hp["n_layer"] - 1 and n_tok > 1:
-                # llm_build_llama's inp_out_ids: after the last attention only the rows whose
-                # logits are wanted (the last token's) go on: GET_ROWS of attn_out and inpSA
-                o, _ = node(OP_GET_ROWS, E, [o, out_ids])
-                x, _ = node(OP_GET_ROWS, E, [x, out_ids])
-                rows = 1
-            ffn_inp, _ = node(OP_ADD, E, [o, x], ne1=rows)
-            n2, _ = node(OP_RMS_NORM, E, [ffn_inp], eps_bits, ne1=rows)
-            m2, _ = node(OP_MUL, E, [n2, leaf(weights[p + "ffn_norm"], TYPE_F32, E)], ne1=rows)
-            gt, up = mm(p + "ffn_gate", m2), mm(p + "ffn_up", m2)
-            glu, _ = node(OP_SWIGLU, gt.ne[0], [gt, up], ne1=rows)
-            dn = mm(p + "ffn_down", glu)
-            x, xb = node(OP_ADD, E, [dn, ffn_inp], ne1=rows)
-        n3, _ = node(OP_RMS_NORM, E, [x], eps_bits)
-        m3, _ = node(OP_MUL, E, [n3, leaf(weights["output_norm"], TYPE_F32, E)])
-        t_out, w_out = weights["output"]
-        wt = leaf(w_out, t_out, w_out.shape[1] * 256 // {12: 144, 13: 176, 14: 210}[t_out], w_out.shape[0],
-                  row_stride=w_out.stride(0))
-        _, logits = node(OP_MUL_MAT, V, [wt, m3], flags=FLAG_OUTPUT)
-        g = dict(inp=inp, nodes=nodes, tensors=T, bufs=bufs, logits=logits, hidden=xb, pos=pos,
-                 arr=(ctypes.POINTER(type(T[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes]),
-                 host=torch.zeros(2 * n_tok + 1, dtype=torch.int32).pin_memory() if self.b is not None else None)
-        if not hasattr(self, "_prompts"):
-            self._prompts = {}
-        self._prompts[n_tok] = g
+        g = _Graph(self.hp, self.w)
+        inp = torch.zeros(2 * n_tok + 1, dtype=torch.int32, device=g.dev)  # token ids | positions | out id
+        tok = g.leaf(inp[:n_tok], TYPE_I32, n_tok)
+        pos = g.leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
+        out_ids = g.leaf(inp[2 * n_tok:], TYPE_I32, 1)  # inp_out_ids: the last token's row
+        tab = g.leaf(self.table, TYPE_F32, self.hp["head_dim"], self.n_ctx)
+        x, hidden = self._layers(g, tok, pos, tab, out_ids=out_ids)
+        logits = self._head(g, x)
+        pg = dict(graph=g, inp=inp, nodes=g.nodes, logits=logits, hidden=hidden, arr=g.arr(),
+                  host=torch.zeros(2 * n_tok + 1, dtype=torch.int32).pin_memory() if self.b is not None else None)
+        self._prompts[n_tok] = pg
         if self.b is not None:
             torch.cuda.synchronize()  # zeroed buffers (torch's stream) before the backend stream runs
-        return g
+        return pg
 
     def prompt(self, tokens, start_pos: int = 0, use_graph: bool = True):
         """Enqueue a prompt batch (positions start_pos ..): writes its KV cells and returns
@@ -328,12 +314,9 @@ class LlamaDecoder:
         host[n_tok:2 * n_tok] = torch_tensor(range(start_pos, start_pos + n_tok))
         host[2 * n_tok] = n_tok - 1
         L = lib()
-        rc = L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel())
-        if rc:
-            raise Mi355xError(f"set_tensor failed ({rc})")
-        rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
-        if rc:
-            raise Mi355xError(f"graph_compute failed ({rc})")
+        _check(L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel()),
+               "set_tensor")
+        self._run(L, g, use_graph)
         self.prompt_hidden = g["hidden"]
         return g["logits"]
 
@@ -347,77 +330,27 @@ class LlamaDecoder:
         [n_tok] each) | the mask, f32 [n_tok, n_kv]."""
         import torch
         key = (n_tok, n_kv)
-        cached = getattr(self, "_batches", {}).get(key)
+        cached = self._batches.get(key)
         if cached is not None:
             return cached
         if self.split is not None:
             raise Mi355xError("batched decoding runs on one GPU (no row split)")
-        hp, weights, n_ctx = self.hp, self.w, self.n_ctx
-        dev = weights["output_norm"].device
-        E, V = hp["n_embd"], hp["n_vocab"]
-        hd, nh, nkv = hp["head_dim"], hp["n_head"], hp["n_head_kv"]
-        kvw = nkv * hd
-        T, bufs, nodes = [], [], []
-        inp = torch.zeros(3 * n_tok + n_tok * n_kv, dtype=torch.int32, device=dev)
-
-        def leaf(t, type_, ne0, ne1=1, row_stride=None):
-            x = make_tensor(type_, ne0, ne1, t.data_ptr(), row_stride=row_stride)
-            T.append(x)
-            return x
-
-        def node(op, n, srcs, params=None, flags=0):
-            b = torch.zeros(n * n_tok, dtype=torch.float32, device=dev)
-            bufs.append(b)
-            x = make_tensor(TYPE_F32, n, n_tok, b.data_ptr(), op=op, srcs=srcs, op_params=params, flags=flags)
-            T.append(x)
-            nodes.append(x)
-            return x, b
-
-        def mm(name, x, flags=0):
-            t, w = weights[name]
-            wt = leaf(w, t, w.shape[1] * 256 // {12: 144, 13: 176, 14: 210}[t], w.shape[0], row_stride=w.stride(0))
-            return node(OP_MUL_MAT, wt.ne[1], [wt, x], flags=flags)
-
-        eps_bits = [f32_bits(hp["eps"])]
-        tok = leaf(inp[:n_tok], TYPE_I32, n_tok)
-        pos = leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
-        cells = leaf(inp[2 * n_tok:3 * n_tok], TYPE_I32, n_tok)
-        mask = leaf(inp[3 * n_tok:], TYPE_F32, n_kv, n_tok)
-        tab = leaf(self.table, TYPE_F32, hd, n_ctx)
-        et, ew = weights["token_embd"]
-        emb_t = leaf(ew, et, E, ew.shape[0], row_stride=ew.stride(0) * ew.element_size())
-        x, _ = node(OP_GET_ROWS, E, [emb_t, tok])
-        scale = f32_bits(float(torch.tensor(1.0) / torch.sqrt(torch.tensor(float(hd)))))
-        for i in range(hp["n_layer"]):
-            p = f"blk.{i}."
-            n1, _ = node(OP_RMS_NORM, E, [x], eps_bits)
-            m1, _ = node(OP_MUL, E, [n1, leaf(weights[p + "attn_norm"], TYPE_F32, E)])
-            q, k, v = mm(p + "attn_q", m1)[0], mm(p + "attn_k", m1)[0], mm(p + "attn_v", m1)[0]
-            kc = leaf(self.k_cache[i], TYPE_F16, kvw, n_ctx)
-            vc = leaf(self.v_cache[i], TYPE_F16, n_ctx, kvw)
-            att, _ = node(OP_ATTN_BATCH, nh * hd, [q, k, v, pos, kc, vc, tab, cells, mask],
-                          [nh, nkv, hd, scale, n_kv])
-            o = mm(p + "attn_output", att)[0]
-            ffn_inp, _ = node(OP_ADD, E, [o, x])
-            n2, _ = node(OP_RMS_NORM, E, [ffn_inp], eps_bits)
-            m2, _ = node(OP_MUL, E, [n2, leaf(weights[p + "ffn_norm"], TYPE_F32, E)])
-            gt, up = mm(p + "ffn_gate", m2)[0], mm(p + "ffn_up", m2)[0]
-            glu, _ = node(OP_SWIGLU, gt.ne[0], [gt, up])
-            dn = mm(p + "ffn_down", glu)[0]
-            x, _ = node(OP_ADD, E, [dn, ffn_inp])
-        n3, _ = node(OP_RMS_NORM, E, [x], eps_bits)
-        m3, _ = node(OP_MUL, E, [n3, leaf(weights["output_norm"], TYPE_F32, E)])
-        _, logits = mm("output", m3, flags=FLAG_OUTPUT)
-        g = dict(inp=inp, nodes=nodes, tensors=T, bufs=bufs, logits=logits.view(n_tok, V),
-                 arr=(ctypes.POINTER(type(T[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes]),
-                 host=torch.zeros((self.BATCH_SLOTS, inp.numel()), dtype=torch.int32).pin_memory()
-                 if self.b is not None else None, slot=0)
-        if not hasattr(self, "_batches"):
-            self._batches = {}
-        self._batches[key] = g
+        g = _Graph(self.hp, self.w)
+        inp = torch.zeros(3 * n_tok + n_tok * n_kv, dtype=torch.int32, device=g.dev)
+        tok = g.leaf(inp[:n_tok], TYPE_I32, n_tok)
+        pos = g.leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
+        cells = g.leaf(inp[2 * n_tok:3 * n_tok], TYPE_I32, n_tok)
+        mask = g.leaf(inp[3 * n_tok:], TYPE_F32, n_kv, n_tok)
+        tab = g.leaf(self.table, TYPE_F32, self.hp["head_dim"], self.n_ctx)
+        x, _ = self._layers(g, tok, pos, tab, batch=(cells, mask, n_kv))
+        logits = self._head(g, x)
+        bg = dict(graph=g, inp=inp, nodes=g.nodes, logits=logits.view(n_tok, self.hp["n_vocab"]), arr=g.arr(),
+                  host=torch.zeros((self.BATCH_SLOTS, inp.numel()), dtype=torch.int32).pin_memory()
+                  if self.b is not None else None, slot=0)
+        self._batches[key] = bg
         if self.b is not None:
             torch.cuda.synchronize()  # zeroed buffers (torch's stream) before the backend stream runs
-        return g
+        return bg
 
     def step_batch(self, tokens, pos, cells, mask, n_kv: int, use_graph: bool = True):
         """Enqueue one batch of T tokens of any sequences (no synchronization): token i has
@@ -428,9 +361,7 @@ class LlamaDecoder:
         m = self._check_batch("step_batch", tokens, pos, cells, mask, n_kv)
         g = self._batch_graph(len(tokens), n_kv)
         L = self._stage_batch(g, tokens, pos, cells, m)
-        rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
-        if rc:
-            raise Mi355xError(f"graph_compute failed ({rc})")
+        self._run(L, g, use_graph)
         return g["logits"]
 
     def _check_batch(self, who: str, tokens, pos, cells, mask, n_kv: int):
@@ -468,9 +399,8 @@ class LlamaDecoder:
         host[2 * n_tok:3 * n_tok] = torch_tensor(cells)
         host[3 * n_tok:].view(torch.float32).view(n_tok, n_kv).copy_(m[:, :n_kv])
         L = lib()
-        rc = L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel())
-        if rc:
-            raise Mi355xError(f"set_tensor failed ({rc})")
+        _check(L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel()),
+               "set_tensor")
         return L
 
     # ------------------------------------------------------------ greedy generation of several sequences
@@ -481,13 +411,11 @@ class LlamaDecoder:
         self.batch_history[i][pos + 1], so the one captured graph is replayed with no host copy."""
         import torch
         key = (n_tok, n_kv, cell_stride)
-        cached = getattr(self, "_gen_batches", {}).get(key)
+        cached = self._gen_batches.get(key)
         if cached is not None:
             return cached
         g = self._batch_graph(n_tok, n_kv)
-        if not hasattr(self, "_gen_batches"):
-            self._gen_batches, self._batch_hists = {}, {}
-        gens, hists = self._gen_batches, self._batch_hists
+        hists = self._batch_hists
         if n_tok not in hists:  # one per T: every step, the last cell's included, has an entry
             hists[n_tok] = dict(dev=torch.zeros((n_tok, self.n_ctx + 1), dtype=torch.int32, device=g["inp"].device),
                                 host=torch.zeros((n_tok, self.n_ctx + 1), dtype=torch.int32).pin_memory())
@@ -500,9 +428,8 @@ class LlamaDecoder:
         am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_ARGMAX_BATCH, srcs=srcs,
                          op_params=[ARGMAX_STEP_INPUTS, cell_stride, n_kv], flags=FLAG_OUTPUT)
         nodes = g["nodes"] + [am]
-        gg = dict(batch=g, nodes=nodes, keep=srcs + [am], hist=hists[n_tok],
-                  arr=(ctypes.POINTER(type(am)) * len(nodes))(*[ctypes.pointer(n) for n in nodes]))
-        gens[key] = gg
+        gg = dict(batch=g, nodes=nodes, keep=srcs + [am], hist=hists[n_tok], arr=_node_array(nodes))
+        self._gen_batches[key] = gg
         torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
         return gg
 
@@ -553,16 +480,12 @@ class LlamaDecoder:
         out, live, done = [[] for _ in range(T)], [True] * T, 0
         while done < n and any(live):
             c = min(chunk, n - done)
-            for _ in range(c):
-                rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
-                if rc:
-                    raise Mi355xError(f"graph_compute failed ({rc})")
+            self._run(L, g, use_graph, times=c)
             # the chunk's tokens of sequence i: history[i][p + 1] for its steps at p
             for i in range(T):
                 lo = pos[i] + done + 1
-                rc = L.mi355x_backend_get_tensor(self.b.h, host[i, lo:].data_ptr(), dev[i, lo:].data_ptr(), 4 * c)
-                if rc:
-                    raise Mi355xError(f"get_tensor failed ({rc})")
+                _check(L.mi355x_backend_get_tensor(self.b.h, host[i, lo:].data_ptr(), dev[i, lo:].data_ptr(), 4 * c),
+                       "get_tensor")
             self.b.synchronize()
             for i in range(T):
                 if not live[i]:
@@ -591,19 +514,16 @@ class LlamaDecoder:
         row[1] = pos
         row[2:] = self._table_host[pos]
         L = lib()
-        hp = row.data_ptr()
         self._slot += 1
-        rc = L.mi355x_backend_set_tensor(self.b.h, self.inp.data_ptr(), hp, 4 * row.numel())
-        if rc:
-            raise Mi355xError(f"set_tensor failed ({rc})")
+        _check(L.mi355x_backend_set_tensor(self.b.h, self.inp.data_ptr(), row.data_ptr(), 4 * row.numel()),
+               "set_tensor")
         return L
 
     def step(self, token: int, pos: int, use_graph: bool = True):
         """Enqueue one token (no synchronization); returns the device logits tensor."""
         L = self._stage_inputs(token, pos)
-        rc = L.mi355x_backend_graph_compute(self.b.h, self._arr, len(self.nodes), 1 if use_graph else 0)
-        if rc:
-            raise Mi355xError(f"graph_compute failed ({rc})")
+        _check(L.mi355x_backend_graph_compute(self.b.h, self._arr, len(self.nodes), 1 if use_graph else 0),
+               "graph_compute")
         return self.logits
 
     # ------------------------------------------------------------ greedy generation on the device
@@ -612,9 +532,8 @@ class LlamaDecoder:
         by writing the next one's (token, pos, rope row) into the input block and the token into
         self.history[pos + 1], so the one captured graph is replayed with no host copy."""
         import torch
-        g = getattr(self, "_gen", None)
-        if g is not None:
-            return g
+        if self._gen is not None:
+            return self._gen
         hd = self.hp["head_dim"]
         self.history = torch.zeros(self.n_ctx, dtype=torch.int32, device=self.inp.device)
         srcs = [self.nodes[-1],
@@ -624,10 +543,8 @@ class LlamaDecoder:
         am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_ARGMAX, srcs=srcs,
                          op_params=[ARGMAX_STEP_INPUTS], flags=FLAG_OUTPUT)
         nodes = self.nodes + [am]
-        g = dict(nodes=nodes, keep=srcs + [am],
-                 arr=(ctypes.POINTER(type(am)) * len(nodes))(*[ctypes.pointer(n) for n in nodes]),
-                 host=torch.zeros(self.n_ctx + 1, dtype=torch.int32).pin_memory())
-        self._gen = g
+        g = self._gen = dict(nodes=nodes, keep=srcs + [am], arr=_node_array(nodes),
+                             host=torch.zeros(self.n_ctx + 1, dtype=torch.int32).pin_memory())
         torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
         return g
 
@@ -653,23 +570,17 @@ class LlamaDecoder:
         host, out, done = g["host"], [], 0
         while done < n:
             c = min(chunk, n - done)
-            for _ in range(c):
-                rc = L.mi355x_backend_graph_compute(self.b.h, g["arr"], len(g["nodes"]), 1 if use_graph else 0)
-                if rc:
-                    raise Mi355xError(f"graph_compute failed ({rc})")
+            self._run(L, g, use_graph, times=c)
             # the chunk's tokens: history[p + 1] for the step at p; the step on the last cell has
             # no history entry, its token is the input block's
             lo, hi = pos + done + 1, pos + done + c + 1
             in_hist = min(hi, self.n_ctx) - lo
             if in_hist > 0:
-                rc = L.mi355x_backend_get_tensor(self.b.h, host[lo:].data_ptr(), self.history[lo:].data_ptr(),
-                                                 4 * in_hist)
-                if rc:
-                    raise Mi355xError(f"get_tensor failed ({rc})")
+                _check(L.mi355x_backend_get_tensor(self.b.h, host[lo:].data_ptr(), self.history[lo:].data_ptr(),
+                                                   4 * in_hist), "get_tensor")
             if hi > self.n_ctx:
-                rc = L.mi355x_backend_get_tensor(self.b.h, host[self.n_ctx:].data_ptr(), self.inp.data_ptr(), 4)
-                if rc:
-                    raise Mi355xError(f"get_tensor failed ({rc})")
+                _check(L.mi355x_backend_get_tensor(self.b.h, host[self.n_ctx:].data_ptr(), self.inp.data_ptr(), 4),
+                       "get_tensor")
             self.b.synchronize()
             for t in host[lo:hi].tolist():
                 out.append(t)
