@@ -31,6 +31,7 @@
 // visible in the row's own mask and files the token in the row's history.
 #include <string.h>
 
+#include "kq_argmax_device.h"
 #include "kq_internal.h"
 #include "kq_rows_device.h"
 
@@ -38,10 +39,7 @@ namespace kq {
 
 namespace {
 
-constexpr int kArgmaxThreads = 256;
 constexpr int kArgmaxSlice = 1024;  // entries per workgroup up to 256 workgroups (ARGMAX_SLICE: A/B)
-constexpr int kArgmaxMaxWgs = 256;  // the last arriver reads one word per thread
-constexpr size_t kArgmaxCounterBytes = 128;  // the counter on a line of its own, then the words
 // kq_argmax_rows: a row's part of the workspace, the counter's line and the words of the largest
 // split. The same for every n, so every counter keeps its place whatever a workspace served
 // before (a place that depended on n would land on another call's leftover words), and a whole
@@ -64,12 +62,6 @@ struct ArgmaxArgs {
     uint32_t rows, n_hist;
     int hd;
 };
-
-__device__ __forceinline__ uint32_t ord_key(uint32_t b) {
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;  // NaN: below -inf's key (0x007fffff)
-    if (b == 0x80000000u) b = 0u;                     // -0.0 == +0.0
-    return b & 0x80000000u ? ~b : b | 0x80000000u;
-}
 
 __device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 

@@ -26,6 +26,7 @@
 
 using kq::attn_batch_desc_of;
 using kq::attn_desc_of;
+using kq::sampler_of;
 using kq::f_of;
 using kq::Launch;
 using kq::LaunchKind;
@@ -53,6 +54,8 @@ struct mi355x_backend {
     int fx_nsb = 0;          // the superblock count the counters' rounds are aligned to
     void *am = nullptr;      // the ARGMAX / ARGMAX_BATCH nodes' arrival counters and partials (kq_argmax.hip), zeroed at
     size_t am_size = 0;      // allocation; every launch leaves them ready for the next
+    void *sm = nullptr;      // the SAMPLE / SAMPLE_BATCH nodes' counters and words (kq_sample.hip), as am
+    size_t sm_size = 0;
     bool layer_engine = false;  // each decode layer as one persistent launch (kq_layer.hip)
     uint32_t *ly_sync = nullptr;  // the persistent layers' counter blocks (zeroed at allocation), then err
     int ly_blocks = 0;
@@ -364,6 +367,44 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             return kq::launch_argmax_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], (int32_t *)t->data, &step,
                                           b->am, b->am_size, st);
         }
+        case MI355X_OP_SAMPLE: {
+            mi355x_sampler sp;
+            sampler_of(t, sp);
+            const int64_t n = t->src[0]->ne[0];
+            if (t->op_params[0] == 0)
+                return kq::launch_topk((const float *)t->src[0]->data, n, 0, nullptr, nullptr, &sp,
+                                       (const float *)t->src[1]->data, (int32_t *)t->data, nullptr, b->sm, b->sm_size, st);
+            const mi355x_tensor *tab = t->src[2];
+            const kq::SampleStep step = {{(const int32_t *)t->src[1]->data, (const float *)tab->data,
+                                          (int32_t *)t->src[3]->data, tab->ne[1], t->src[3]->ne[0], (int)tab->ne[0]},
+                                         t->src[4]->ne[0]};
+            return kq::launch_topk((const float *)t->src[0]->data, n, 0, nullptr, nullptr, &sp,
+                                   (const float *)t->src[4]->data, (int32_t *)t->data, &step, b->sm, b->sm_size, st);
+        }
+        case MI355X_OP_SAMPLE_BATCH: {
+            mi355x_sampler sp;
+            sampler_of(t, sp);
+            const mi355x_tensor *x = t->src[0];
+            if (t->op_params[0] == 0)
+                return kq::launch_topk_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], 0, nullptr, nullptr, &sp,
+                                            (const float *)t->src[1]->data, (int32_t *)t->data, nullptr, b->sm, b->sm_size,
+                                            st);
+            const mi355x_tensor *mask = t->src[3], *hist = t->src[4], *draws = t->src[5];
+            kq::SampleRowsStep step;
+            step.a.pos = (int32_t *)t->src[1]->data;
+            step.a.cells = (int32_t *)t->src[2]->data;
+            step.a.mask = (float *)mask->data;
+            step.a.hist = (int32_t *)hist->data;
+            step.a.mask_stride = (int64_t)(mask->nb[1] / 4);
+            step.a.hist_stride = (int64_t)(hist->nb[1] / 4);
+            step.a.n_kv = t->op_params[6];
+            step.a.n_hist = hist->ne[0];
+            step.a.cell_stride = t->op_params[5];
+            step.draws_stride = (int64_t)(draws->nb[1] / 4);
+            step.n_draws = draws->ne[0];
+            return kq::launch_topk_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], 0, nullptr, nullptr, &sp,
+                                        (const float *)draws->data, (int32_t *)t->data, &step, b->sm, b->sm_size, st);
+        }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(t, d);
@@ -607,6 +648,26 @@ int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_n
     return MI355X_OK;
 }
 
+// ... and the SAMPLE and SAMPLE_BATCH nodes', in a buffer of their own (b->am keeps its layout)
+int ensure_sample_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
+    size_t need = 0;
+    for (int i = 0; i < n_nodes; ++i)
+        if (nodes[i]->op == MI355X_OP_SAMPLE) need = std::max(need, kq::topk_workspace(nodes[i]->src[0]->ne[0], 1));
+        else if (nodes[i]->op == MI355X_OP_SAMPLE_BATCH)
+            need = std::max(need, kq::topk_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
+    if (need <= b->sm_size) return MI355X_OK;
+    hipStreamSynchronize(b->stream);
+    drop_graph(b);
+    if (b->sm) hipFree(b->sm);
+    b->sm = nullptr;
+    b->sm_size = 0;
+    if (hipMalloc(&b->sm, need) != hipSuccess) return MI355X_E_WORKSPACE;
+    b->sm_size = need;
+    if (hipMemsetAsync(b->sm, 0, need, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
+        return MI355X_E_WORKSPACE;
+    return MI355X_OK;
+}
+
 // The persistent layers' counter blocks: one per Layer launch, zeroed whenever they are
 // (re)allocated. A launch's counters are monotonic over its launches with ITS producer
 // counts, so a block is keyed by (layer index in the graph, producers per edge and shard):
@@ -817,6 +878,7 @@ void mi355x_backend_free(mi355x_backend_t b) {
     if (b->workspace) hipFree(b->workspace);
     if (b->fx) hipFree(b->fx);
     if (b->am) hipFree(b->am);
+    if (b->sm) hipFree(b->sm);
     if (b->ly_sync) hipFree(b->ly_sync);
     for (auto &t : b->ly_tabs)
         if (t.dev) hipFree(t.dev);
@@ -986,6 +1048,7 @@ int mi355x_backend_graph_compute(mi355x_backend_t b, mi355x_tensor *const *nodes
     const std::vector<Launch> launches = kq::plan_launches(plan_opts(b), nodes, n_nodes);
     if ((rc = ensure_attn_oproj_buffer(b, nodes, launches))) return rc;
     if ((rc = ensure_argmax_buffer(b, nodes, n_nodes))) return rc;
+    if ((rc = ensure_sample_buffer(b, nodes, n_nodes))) return rc;
     if ((rc = ensure_layer_blocks(b, launches))) return rc;
     if ((rc = ensure_layer_tables(b, launches))) return rc;
     if ((rc = reserve_attn_cells(b, nodes, launches))) return rc;

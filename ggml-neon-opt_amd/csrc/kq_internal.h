@@ -300,6 +300,30 @@ size_t argmax_rows_workspace(int64_t n, int64_t rows);
 int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
                        const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream);
 
+// ---------------------------------------------------------------- kq_sample.hip
+// The exact top-k of an f32 vector and the sampler chain on it, one launch (kq_topk; kq_topk_rows
+// over the rows of a matrix), the slices argmax_plan(n)'s. topk_workspace: per row the counter's
+// line and 256 x 64 words, whatever n and top_k are (0 outside argmax_rows_workspace's ranges).
+// launch_topk*: sp null: the plain form (idx / val [top_k], per row); else the sampled token,
+// `u` the draw(s) and `out` the token(s); step: the step-inputs forms (the SAMPLE / SAMPLE_BATCH
+// nodes' op_params[0] == 1), kq_argmax's / kq_argmax_rows' writes, `u` then the draws table: the
+// draw of the token that will stand at position p is entry p (0.0f where the table has none).
+struct SampleStep {
+    ArgmaxStep a;
+    int64_t n_draws;
+};
+struct SampleRowsStep {
+    ArgmaxRowsStep a;
+    int64_t draws_stride, n_draws;  // entries between two rows of the draws, entries of a row in use
+};
+size_t topk_workspace(int64_t n, int64_t rows);
+bool sampler_ok(const mi355x_sampler *s);
+int launch_topk(const float *x, int64_t n, int top_k, int32_t *idx, float *val, const mi355x_sampler *sp, const float *u,
+                int32_t *out, const SampleStep *step, void *ws, size_t ws_size, hipStream_t stream);
+int launch_topk_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int top_k, int32_t *idx, float *val,
+                     const mi355x_sampler *sp, const float *u, int32_t *out, const SampleRowsStep *step, void *ws,
+                     size_t ws_size, hipStream_t stream);
+
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from
 // checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /

@@ -62,6 +62,7 @@ bool attn_feeds_batched_mm(const PlanOpts &o, const mi355x_tensor *t, const Laun
 bool kv_epilogue(mi355x_tensor *const *nodes, const Launch &l, const Launch &next, MmqKv &kv);
 void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a);  // rope_row left to the caller
 void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d);
+void sampler_of(const mi355x_tensor *t, mi355x_sampler &s);  // SAMPLE / SAMPLE_BATCH: op_params[1 .. 4]
 std::vector<uint64_t> graph_key_of(mi355x_tensor *const *nodes, int n_nodes);
 bool supports_op(const mi355x_tensor *op);  // mi355x_backend_supports_op
 

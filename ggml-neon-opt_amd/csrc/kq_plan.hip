@@ -241,6 +241,14 @@ void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a) {
     a.n_ctx = (int)t->src[4]->ne[1];
 }
 
+// SAMPLE / SAMPLE_BATCH: op_params[1 .. 4] = top_k and the bits of temp, top_p, min_p
+void sampler_of(const mi355x_tensor *t, mi355x_sampler &s) {
+    s.top_k = t->op_params[1];
+    s.temp = f_of(t->op_params[2]);
+    s.top_p = f_of(t->op_params[3]);
+    s.min_p = f_of(t->op_params[4]);
+}
+
 // ATTN_BATCH: the ATTN_DECODE operands, the cells (src7), the mask (src8) and n_kv
 void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d) {
     attn_desc_of(t, d.a);
@@ -679,6 +687,28 @@ bool supports_op(const mi355x_tensor *op) {
             return hist && hist->type == MI355X_TYPE_I32 && hist->data && hist->nb[0] == 4 && hist->ne[0] >= 1 &&
                    hist->ne[0] <= 0x7fffffff && hist->ne[1] == T && nelem(hist) == hist->ne[0] * T && hist->nb[1] % 4 == 0 &&
                    hist->nb[1] >= (size_t)hist->ne[0] * 4;
+        }
+        case MI355X_OP_SAMPLE:
+        case MI355X_OP_SAMPLE_BATCH: {
+            // the ARGMAX / ARGMAX_BATCH node of the same form on the same operands, the sampler's
+            // parameters in their ranges, and one more source: the draw(s) of the plain form (F32
+            // [1] / [T]) or the draws table of the step-inputs form (F32 [n_draws] / [n_draws, T])
+            const bool batch = op->op == MI355X_OP_SAMPLE_BATCH;
+            const int form = op->op_params[0];
+            if (form != 0 && form != 1) return false;
+            mi355x_sampler sp;
+            sampler_of(op, sp);
+            if (!sampler_ok(&sp)) return false;
+            mi355x_tensor am = *op;
+            am.op = batch ? MI355X_OP_ARGMAX_BATCH : MI355X_OP_ARGMAX;
+            am.op_params[1] = op->op_params[5], am.op_params[2] = op->op_params[6];
+            if (!supports_op(&am)) return false;
+            const mi355x_tensor *u = op->src[form == 0 ? 1 : batch ? 5 : 4];
+            const int64_t T = batch ? op->src[0]->ne[1] : 1;
+            if (!u || u->type != MI355X_TYPE_F32 || !u->data || ((uintptr_t)u->data & 3u) || u->nb[0] != 4) return false;
+            if (form == 0) return u->ne[0] == T && nelem(u) == T;
+            return u->ne[0] >= 1 && u->ne[0] <= 0x7fffffff && u->ne[1] == T && nelem(u) == u->ne[0] * T &&
+                   (T == 1 || (u->nb[1] % 4 == 0 && u->nb[1] >= (size_t)u->ne[0] * 4));
         }
         default:
             return false;

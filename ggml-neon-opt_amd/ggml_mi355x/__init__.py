@@ -29,6 +29,11 @@ OP_ATTN_BATCH = 11
 OP_ARGMAX = 12  # op_params[0]: ARGMAX_PLAIN / ARGMAX_STEP_INPUTS
 ARGMAX_PLAIN, ARGMAX_STEP_INPUTS = 0, 1
 OP_ARGMAX_BATCH = 13  # the argmax of every row; op_params[0]: ARGMAX_PLAIN / ARGMAX_STEP_INPUTS
+# op_params = [SAMPLE_PLAIN / SAMPLE_STEP_INPUTS, top_k, f32_bits(temp), f32_bits(top_p), f32_bits(min_p)]
+# (sampler_params); the batch op appends cell_stride, n_kv
+OP_SAMPLE, OP_SAMPLE_BATCH = 14, 15
+SAMPLE_PLAIN, SAMPLE_STEP_INPUTS = 0, 1
+SAMPLE_MAX_K = 64
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -75,11 +80,18 @@ EXPORTED_SYMBOLS = (
     "mi355x_debug_rows_plan",
     "mi355x_argmax_plan", "mi355x_argmax_workspace_size", "mi355x_argmax",
     "mi355x_argmax_rows_workspace_size", "mi355x_argmax_rows",
+    "mi355x_topk_workspace_size", "mi355x_topk", "mi355x_topk_rows", "mi355x_sample", "mi355x_sample_rows",
 )
 
 
 class Mi355xError(RuntimeError):
     pass
+
+
+class SamplerDesc(ctypes.Structure):
+    """struct mi355x_sampler"""
+    _fields_ = [("top_k", ctypes.c_int32), ("temp", ctypes.c_float), ("top_p", ctypes.c_float),
+                ("min_p", ctypes.c_float)]
 
 
 class GemvDesc(ctypes.Structure):
@@ -265,6 +277,17 @@ def lib():
         L.mi355x_argmax_rows_workspace_size.restype = sz
         L.mi355x_argmax_rows.argtypes = [vp, i64, i64, i64, vp, vp, sz, vp]
         L.mi355x_argmax_rows.restype = i32
+    if hasattr(L, "mi355x_topk"):
+        L.mi355x_topk_workspace_size.argtypes = [i64, i64]
+        L.mi355x_topk_workspace_size.restype = sz
+        L.mi355x_topk.argtypes = [vp, i64, i32, vp, vp, vp, sz, vp]
+        L.mi355x_topk.restype = i32
+        L.mi355x_topk_rows.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]
+        L.mi355x_topk_rows.restype = i32
+        L.mi355x_sample.argtypes = [vp, i64, ctypes.POINTER(SamplerDesc), vp, vp, vp, sz, vp]
+        L.mi355x_sample.restype = i32
+        L.mi355x_sample_rows.argtypes = [vp, i64, i64, i64, ctypes.POINTER(SamplerDesc), vp, vp, vp, sz, vp]
+        L.mi355x_sample_rows.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -805,6 +828,118 @@ def argmax_rows(x, out=None, workspace=None, stream=None):
     stride = x.stride(0) if rows > 1 else (n + 3) & ~3  # (one row: torch's stride of it means nothing)
     _check(_argmax_rows_lib().mi355x_argmax_rows(x.data_ptr(), n, rows, stride, out.data_ptr(), workspace.data_ptr(),
                                                  workspace.numel(), _stream(stream)), "mi355x_argmax_rows")
+    return out
+
+
+def _topk_lib():
+    L = lib()
+    if not hasattr(L, "mi355x_topk"):
+        raise Mi355xError(f"{LIB_PATH} has no mi355x_topk (a library built before it)")
+    return L
+
+
+def topk_workspace_size(n, rows=1):
+    """Bytes of the workspace of topk / sample (rows = 1) and topk_rows / sample_rows: 131200 a row
+    whatever n and top_k are (0: n outside 1 .. 2^24 or rows outside 1 .. 65535)."""
+    return int(_topk_lib().mi355x_topk_workspace_size(n, rows))
+
+
+def sampler_params(form, top_k, temp, top_p, min_p):
+    """The SAMPLE nodes' leading op_params."""
+    return [form, top_k, f32_bits(temp), f32_bits(top_p), f32_bits(min_p)]
+
+
+def _topk_workspace(workspace, n, rows, device, stream):
+    torch = _torch()
+    if workspace is None:
+        workspace = torch.zeros(topk_workspace_size(n, rows) or 1, dtype=torch.uint8, device=device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
+    return workspace
+
+
+def _rows_of(name, x):
+    torch = _torch()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and
+            x.stride(1) == 1):
+        raise Mi355xError(f"{name}: x must be a 2-D float32 cuda tensor with unit column stride")
+    rows, n = x.shape
+    return rows, n, (x.stride(0) if rows > 1 else (n + 3) & ~3)  # (one row: torch's stride of it means nothing)
+
+
+def topk(x, top_k, workspace=None, stream=None):
+    """mi355x_topk: the top_k (1 .. 64) largest non-NaN entries of x, a contiguous f32 cuda vector,
+    under argmax's order, sorted: (idx int32 [top_k], val f32 [top_k]) cuda tensors, places past
+    the number of non-NaN entries -1 / NaN (no synchronization). workspace: a uint8 cuda tensor of
+    topk_workspace_size(n) bytes, zeroed once by its owner and reusable call after call on one
+    stream, whatever n and top_k are; None: a fresh zeroed one."""
+    torch = _torch()
+    _require_device()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+        raise Mi355xError("topk: x must be a contiguous float32 cuda vector")
+    n, k = x.numel(), max(int(top_k), 1)
+    idx = torch.empty(k, dtype=torch.int32, device=x.device)
+    val = torch.empty(k, dtype=torch.float32, device=x.device)
+    workspace = _topk_workspace(workspace, n, 1, x.device, stream)
+    _check(_topk_lib().mi355x_topk(x.data_ptr(), n, int(top_k), idx.data_ptr(), val.data_ptr(), workspace.data_ptr(),
+                                   workspace.numel(), _stream(stream)), "mi355x_topk")
+    return idx, val
+
+
+def topk_rows(x, top_k, workspace=None, stream=None):
+    """mi355x_topk_rows: topk's rule on every row of x, a 2-D f32 cuda tensor [T, n] with unit
+    column stride (the row stride >= n and a multiple of 4 floats): (idx int32 [T, top_k], val f32
+    [T, top_k]). workspace: topk_workspace_size(n, T) bytes, as topk's."""
+    torch = _torch()
+    _require_device()
+    rows, n, stride = _rows_of("topk_rows", x)
+    k = max(int(top_k), 1)
+    idx = torch.empty((rows, k), dtype=torch.int32, device=x.device)
+    val = torch.empty((rows, k), dtype=torch.float32, device=x.device)
+    workspace = _topk_workspace(workspace, n, rows, x.device, stream)
+    _check(_topk_lib().mi355x_topk_rows(x.data_ptr(), n, rows, stride, int(top_k), idx.data_ptr(), val.data_ptr(),
+                                        workspace.data_ptr(), workspace.numel(), _stream(stream)), "mi355x_topk_rows")
+    return idx, val
+
+
+def sample(x, u, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, out=None, workspace=None, stream=None):
+    """mi355x_sample: one token from x, a contiguous f32 cuda vector of logits, by llama.cpp's
+    default chain (top-k -> top-p -> min-p -> temperature -> the draw u; the exact rule is in
+    include/ggml_mi355x.h), as an int32 cuda tensor [1] (no synchronization). u: an f32 cuda
+    tensor whose first entry is the draw, meant to lie in [0, 1). workspace: as topk's."""
+    torch = _torch()
+    _require_device()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+        raise Mi355xError("sample: x must be a contiguous float32 cuda vector")
+    if not (u.is_cuda and u.dtype == torch.float32 and u.numel() >= 1):
+        raise Mi355xError("sample: u must be a float32 cuda tensor")
+    n = x.numel()
+    out = torch.empty(1, dtype=torch.int32, device=x.device) if out is None else out
+    if not (out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1):
+        raise Mi355xError("sample: out must be an int32 cuda tensor")
+    workspace = _topk_workspace(workspace, n, 1, x.device, stream)
+    sp = SamplerDesc(int(top_k), float(temp), float(top_p), float(min_p))
+    _check(_topk_lib().mi355x_sample(x.data_ptr(), n, ctypes.byref(sp), u.data_ptr(), out.data_ptr(),
+                                     workspace.data_ptr(), workspace.numel(), _stream(stream)), "mi355x_sample")
+    return out
+
+
+def sample_rows(x, u, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, out=None, workspace=None, stream=None):
+    """mi355x_sample_rows: sample's rule on every row of x [T, n] (as topk_rows'), row i with the
+    draw u[i] (a contiguous f32 cuda tensor [T]), as an int32 cuda tensor [T]."""
+    torch = _torch()
+    _require_device()
+    rows, n, stride = _rows_of("sample_rows", x)
+    if not (u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() >= rows):
+        raise Mi355xError("sample_rows: u must be a contiguous float32 cuda tensor of one entry per row")
+    out = torch.empty(rows, dtype=torch.int32, device=x.device) if out is None else out
+    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= rows):
+        raise Mi355xError("sample_rows: out must be a contiguous int32 cuda tensor of one entry per row")
+    workspace = _topk_workspace(workspace, n, rows, x.device, stream)
+    sp = SamplerDesc(int(top_k), float(temp), float(top_p), float(min_p))
+    _check(_topk_lib().mi355x_sample_rows(x.data_ptr(), n, rows, stride, ctypes.byref(sp), u.data_ptr(), out.data_ptr(),
+                                          workspace.data_ptr(), workspace.numel(), _stream(stream)),
+           "mi355x_sample_rows")
     return out
 
 

@@ -25,7 +25,8 @@ layer body and the one head below (LlamaDecoder._layers, ._head) over a _Graph:
   step_batch      _batch_graph(n_tok, n_kv): n_tok rows of any sequences, ATTN_BATCH with
                   cells and mask from the inputs, logits of every row
   generate,       the token graph / the batch graph plus one ARGMAX / ARGMAX_BATCH node
-  generate_batch  that stages the next step's inputs on the device
+  generate_batch  that stages the next step's inputs on the device; with a Sampler that last
+                  node is a SAMPLE / SAMPLE_BATCH, which reads its draws from a device table
 """
 from __future__ import annotations
 
@@ -33,8 +34,8 @@ import ctypes
 
 from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ARGMAX,
                OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL, OP_MUL_MAT, OP_RMS_NORM,
-               OP_SWIGLU, QK_K, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor,
-               rope_table)
+               OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32,
+               TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table, sampler_params)
 
 
 def torch_tensor(values):
@@ -61,6 +62,31 @@ def _check(rc, what):
 
 def _node_array(nodes):
     return (ctypes.POINTER(type(nodes[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes])
+
+
+class Sampler:
+    """llama.cpp's default sampler chain, top-k -> top-p -> min-p -> temperature -> one draw, with
+    its defaults [U] (the exact rule: include/ggml_mi355x.h, mi355x_sample). seed: the draws of
+    generate / generate_batch are numpy's PCG64(seed) float32 stream (sequence i of a batch:
+    PCG64([seed, i])), entry p the draw of the token that will stand at position p, so the same
+    seed and context give the same tokens whatever chunk, n or use_graph is."""
+
+    def __init__(self, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, seed=0):
+        import math
+        self.top_k, self.top_p, self.min_p, self.temp, self.seed = int(top_k), float(top_p), float(min_p), float(temp), seed
+        if not (1 <= self.top_k <= SAMPLE_MAX_K and math.isfinite(self.temp) and self.temp >= 0 and
+                0 < self.top_p <= 1 and 0 <= self.min_p <= 1):
+            raise Mi355xError(f"Sampler: top_k {top_k} in [1, {SAMPLE_MAX_K}], temp {temp} finite and >= 0, top_p {top_p} "
+                              f"in (0, 1] and min_p {min_p} in [0, 1] are required")
+
+    def params(self, form=SAMPLE_STEP_INPUTS):
+        """The SAMPLE nodes' leading op_params (the graphs are cached by them: the seed is not part)."""
+        return sampler_params(form, self.top_k, self.temp, self.top_p, self.min_p)
+
+    def draws(self, n, row=None):
+        import numpy as np
+        seed = self.seed if row is None else [self.seed, row]
+        return np.random.Generator(np.random.PCG64(seed)).random(n, dtype=np.float32)
 
 
 class _Graph:
@@ -144,6 +170,7 @@ class LlamaDecoder:
         self.gathers = []  # (node output buffer) of every ALL_GATHER, in graph order
         self.reduces = []  # (input partial, output) buffers of every ALL_REDUCE (split mode "reduce")
         self._prompts, self._batches, self._gen_batches, self._batch_hists, self._gen = {}, {}, {}, {}, None
+        self._gen_sampled, self._draws, self._batch_draws, self.history = {}, None, {}, None
         # inp_tokens, inp_pos and the rope row of that position side by side: one
         # set_tensor of 8 + 4*head_dim bytes per token. The attention reads its cos/sin
         # with q/k/v instead of after the position (one dependent round trip less);
@@ -403,14 +430,44 @@ class LlamaDecoder:
                "set_tensor")
         return L
 
+    # ------------------------------------------------------------ the samplers' draws
+    def _draws_table(self, rows=None):
+        """The device table the SAMPLE node (rows None) or the SAMPLE_BATCH node of `rows` sequences
+        reads its draws from: f32 [n_ctx + 1] a sequence, entry p the draw of the token that
+        will stand at position p. Allocated once (the graphs hold its address), filled by _seed."""
+        import torch
+        if rows is None:
+            if self._draws is None:
+                self._draws = dict(dev=torch.zeros(self.n_ctx + 1, dtype=torch.float32, device=self.inp.device), seed=None)
+            return self._draws
+        if rows not in self._batch_draws:
+            self._batch_draws[rows] = dict(dev=torch.zeros((rows, self.n_ctx + 1), dtype=torch.float32,
+                                                           device=self.inp.device), seed=None)
+        return self._batch_draws[rows]
+
+    def _seed(self, sampler, rows=None):
+        """Fills the draws table for sampler.seed unless it holds that seed's draws already: the
+        backend is synchronized first (a run may still read the table), torch's stream after."""
+        import numpy as np
+        import torch
+        d = self._draws_table(rows)
+        if d["seed"] is not None and d["seed"] == (sampler.seed,):
+            return
+        n = self.n_ctx + 1
+        host = sampler.draws(n) if rows is None else np.stack([sampler.draws(n, i) for i in range(rows)])
+        self.b.synchronize()
+        d["dev"].copy_(torch.from_numpy(host))
+        torch.cuda.synchronize()
+        d["seed"] = (sampler.seed,)
+
     # ------------------------------------------------------------ greedy generation of several sequences
-    def _generate_batch_graph(self, n_tok: int, n_kv: int, cell_stride: int):
+    def _generate_batch_graph(self, n_tok: int, n_kv: int, cell_stride: int, sampler=None):
         """_batch_graph(n_tok, n_kv)'s nodes plus one step-inputs ARGMAX_BATCH on the logits: it ends
         the step by writing every sequence's next token, position and cell into that graph's own
         input block, showing the new cell in the sequence's mask row and filing the token in
         self.batch_history[i][pos + 1], so the one captured graph is replayed with no host copy."""
         import torch
-        key = (n_tok, n_kv, cell_stride)
+        key = (n_tok, n_kv, cell_stride) + (() if sampler is None else tuple(sampler.params()))
         cached = self._gen_batches.get(key)
         if cached is not None:
             return cached
@@ -425,8 +482,13 @@ class LlamaDecoder:
                 make_tensor(TYPE_I32, T, 1, inp[2 * T:3 * T].data_ptr()),
                 make_tensor(TYPE_F32, n_kv, T, inp[3 * T:].data_ptr()),
                 make_tensor(TYPE_I32, self.n_ctx + 1, T, hist.data_ptr())]
-        am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_ARGMAX_BATCH, srcs=srcs,
-                         op_params=[ARGMAX_STEP_INPUTS, cell_stride, n_kv], flags=FLAG_OUTPUT)
+        if sampler is None:
+            am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_ARGMAX_BATCH, srcs=srcs,
+                             op_params=[ARGMAX_STEP_INPUTS, cell_stride, n_kv], flags=FLAG_OUTPUT)
+        else:  # the same writes with sampled tokens: one more source, the sequences' draws
+            srcs.append(make_tensor(TYPE_F32, self.n_ctx + 1, T, self._draws_table(T)["dev"].data_ptr()))
+            am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_SAMPLE_BATCH, srcs=srcs,
+                             op_params=sampler.params() + [cell_stride, n_kv], flags=FLAG_OUTPUT)
         nodes = g["nodes"] + [am]
         gg = dict(batch=g, nodes=nodes, keep=srcs + [am], hist=hists[n_tok], arr=_node_array(nodes))
         self._gen_batches[key] = gg
@@ -434,7 +496,7 @@ class LlamaDecoder:
         return gg
 
     def generate_batch(self, tokens, pos, cells, mask, n: int, n_kv: int, cell_stride: int = 1, eos=None,
-                       chunk: int = 32, use_graph: bool = True):
+                       chunk: int = 32, use_graph: bool = True, sampler=None):
         """Greedy decoding of n steps of T sequences together: sequence i starts from tokens[i] at
         position pos[i] in cache cell cells[i] under mask[i] (step_batch's inputs), and its step k
         runs at position pos[i] + k in cell cells[i] + k * cell_stride. Returns a list of T lists of
@@ -451,7 +513,9 @@ class LlamaDecoder:
         sequence has ended or after n steps. A finished sequence keeps running on the device to
         the end of the call's steps (the last chunk's included): its later cells and history
         entries are written too. A following step_batch or generate_batch works as ever: it
-        restages the whole input block."""
+        restages the whole input block.
+        sampler: a Sampler: every token is sampled on the device instead (a SAMPLE_BATCH node ends
+        the step), sequence i's token for position p with entry p of its own row of draws."""
         import numpy as np
         if self.split is not None:
             raise Mi355xError("generate_batch runs on one GPU (no row split)")
@@ -473,7 +537,9 @@ class LlamaDecoder:
         if not np.isneginf(m[:, :n_kv].numpy()[:, written[:, 1:].ravel()]).all():
             raise Mi355xError("generate_batch: a cell that a later step writes is visible in the mask (every such cell "
                               "must be -inf in every row; the device shows it to its own sequence)")
-        g = self._generate_batch_graph(T, n_kv, cell_stride)
+        g = self._generate_batch_graph(T, n_kv, cell_stride, sampler)
+        if sampler is not None:
+            self._seed(sampler, T)
         self.batch_history = g["hist"]["dev"]
         L = self._stage_batch(g["batch"], tokens, pos, cells, m)
         dev, host = g["hist"]["dev"], g["hist"]["host"]
@@ -527,28 +593,43 @@ class LlamaDecoder:
         return self.logits
 
     # ------------------------------------------------------------ greedy generation on the device
-    def _generate_graph(self):
+    def _generate_graph(self, sampler=None):
         """The decode token's nodes plus one step-inputs ARGMAX on the logits: it ends the token
         by writing the next one's (token, pos, rope row) into the input block and the token into
-        self.history[pos + 1], so the one captured graph is replayed with no host copy."""
+        self.history[pos + 1], so the one captured graph is replayed with no host copy. With a
+        sampler the last node is a step-inputs SAMPLE instead: the same writes with the sampled
+        token, one more source (the draws); one graph per sampler parameters."""
         import torch
-        if self._gen is not None:
-            return self._gen
+        key = None if sampler is None else tuple(sampler.params())
+        cached = self._gen if sampler is None else self._gen_sampled.get(key)
+        if cached is not None:
+            return cached
         hd = self.hp["head_dim"]
-        self.history = torch.zeros(self.n_ctx, dtype=torch.int32, device=self.inp.device)
+        if self.history is None:
+            self.history = torch.zeros(self.n_ctx, dtype=torch.int32, device=self.inp.device)
         srcs = [self.nodes[-1],
                 make_tensor(TYPE_I32, 1, 1, self.pos.data_ptr()),
                 make_tensor(TYPE_F32, hd, self.n_ctx, self.table.data_ptr()),
                 make_tensor(TYPE_I32, self.n_ctx, 1, self.history.data_ptr())]
-        am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_ARGMAX, srcs=srcs,
-                         op_params=[ARGMAX_STEP_INPUTS], flags=FLAG_OUTPUT)
+        if sampler is None:
+            am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_ARGMAX, srcs=srcs,
+                             op_params=[ARGMAX_STEP_INPUTS], flags=FLAG_OUTPUT)
+        else:
+            srcs.append(make_tensor(TYPE_F32, self.n_ctx + 1, 1, self._draws_table()["dev"].data_ptr()))
+            am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_SAMPLE, srcs=srcs,
+                             op_params=sampler.params(), flags=FLAG_OUTPUT)
         nodes = self.nodes + [am]
-        g = self._gen = dict(nodes=nodes, keep=srcs + [am], arr=_node_array(nodes),
-                             host=torch.zeros(self.n_ctx + 1, dtype=torch.int32).pin_memory())
-        torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
+        g = dict(nodes=nodes, keep=srcs + [am], arr=_node_array(nodes))
+        if sampler is None:
+            self._gen = g
+        else:
+            self._gen_sampled[key] = g
+        if self.b is not None:  # (describe only: no device work)
+            g["host"] = torch.zeros(self.n_ctx + 1, dtype=torch.int32).pin_memory()
+            torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
         return g
 
-    def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True):
+    def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True, sampler=None):
         """Greedy decoding of n tokens at positions pos .. pos + n - 1, starting from `token` at
         `pos`: returns the generated tokens as a list of ints (the token picked after position p
         is the argmax of that step's logits, mi355x_argmax's rule). The inputs are staged from the
@@ -556,7 +637,9 @@ class LlamaDecoder:
         the next, and only after a chunk the host synchronizes and reads its tokens with one copy.
         eos: stop at the first such token, which is returned as the last one (the device may have
         run on to the end of that chunk: its later cells and history entries are then written
-        too). A following step() works as ever: it restages the whole input block."""
+        too). A following step() works as ever: it restages the whole input block.
+        sampler: a Sampler: every token is sampled on the device instead (mi355x_sample's rule; a
+        SAMPLE node ends the token), the token for position p with entry p of the seed's draws."""
         if self.split is not None:
             raise Mi355xError("generate runs on one GPU (no row split)")
         if n < 0 or chunk < 1:
@@ -565,7 +648,9 @@ class LlamaDecoder:
             raise Mi355xError(f"generate: {n} tokens from position {pos} outside the KV cache (n_ctx {self.n_ctx})")
         if n == 0:
             return []
-        g = self._generate_graph()
+        g = self._generate_graph(sampler)
+        if sampler is not None:
+            self._seed(sampler)
         L = self._stage_inputs(token, pos)
         host, out, done = g["host"], [], 0
         while done < n:

@@ -527,6 +527,59 @@ size_t mi355x_argmax_rows_workspace_size(int64_t n, int64_t rows);
 int mi355x_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out, void *workspace,
                        size_t workspace_size, void *stream);
 
+/* Sampling on the device: the exact top-k of an f32 vector and llama.cpp's default sampler chain
+ * (top-k -> top-p -> min-p -> temperature -> one draw [U]) on it, in one launch
+ * (csrc/kq_sample.hip): the slices are mi355x_argmax_plan(n)'s, each workgroup selects and sorts
+ * its slice's top_k, the workgroup that arrives last merges the slices that can contribute and
+ * runs the chain.
+ * The rule (exact: the same token as tests/sample_ref.py, no tolerance).
+ *   Parameters: top_k in [1, MI355X_SAMPLE_MAX_K], temp finite and >= 0, top_p in (0, 1], min_p in
+ *   [0, 1]; anything else is MI355X_E_INVAL. Per sampled token one f32 draw u supplied by the
+ *   caller, meant to lie in [0, 1).
+ *   Candidates: the m = min(top_k, number of non-NaN entries) largest entries under
+ *   mi355x_argmax's order (larger value first, -0.0 == +0.0, among equal values the smaller
+ *   index), sorted c_0 .. c_{m-1} with logits l_0 >= l_1 >= ...; a NaN is never a candidate;
+ *   m == 0 (all NaN) gives token 0; c_0 is mi355x_argmax's result. If temp == 0, m == 1 or l_0 is
+ *   not finite, the token is c_0 and no arithmetic runs.
+ *   Arithmetic: every step f32, rounded once per operation, nothing contracted, the division
+ *   correctly rounded, the sums sequential in candidate order. v_expf: ggml_v_expf, as the attention's.
+ *     1. d_i = l_i - l_0
+ *     2. e_i = 0 if d_i == -inf, else v_expf(d_i) (so e_0 == 1.0f)
+ *     3. S = e_0 + e_1 + ... + e_{m-1}
+ *     4. p_i = e_i / S
+ *     5. min-p keeps the prefix of i with e_i >= min_p (it ends before the first i that fails)
+ *     6. top-p keeps the shortest prefix whose running sum p_0 + ... + p_j is >= top_p, and all
+ *        candidates if top_p >= 1 (or if no running sum reaches top_p)
+ *     7. the kept set is the shorter of the two prefixes, never shorter than one candidate: length q
+ *     8. t_i = d_i / temp, f_i = 0 if t_i == -inf, else v_expf(t_i), F = f_0 + ... + f_{q-1}
+ *     9. r = u * F
+ *    10. the token is the first c_i with i < q whose running sum f_0 + ... + f_i is > r; if there
+ *        is none (u >= 1, a NaN, or rounding) it is c_{q-1}.
+ *   (d_i / temp instead of l_i / temp - max: a tiny temp cannot produce inf - inf.)
+ * mi355x_topk: idx[i] / val[i] = c_i / x[c_i] for i < m, -1 / the NaN 0x7fc00000 for m <= i < top_k.
+ * mi355x_topk_rows / mi355x_sample_rows: every row of a matrix in one launch, as
+ * mi355x_argmax_rows (row_stride in floats, >= n, a multiple of 4): idx / val [rows][top_k],
+ * u / out [rows]. mi355x_topk_workspace_size: per row a counter on a 128-B line of its own and
+ * 256 x 64 words, 131200 bytes a row whatever n and top_k are (0 for an n or rows outside
+ * mi355x_argmax_rows' ranges). The caller owns the workspace (8-B aligned) and zeroes it once;
+ * every call leaves it ready for the next, whatever n, rows and top_k that one has; two calls
+ * that can run concurrently must not share one. x: 16-B aligned. Returns MI355X_E_INVAL (a null
+ * pointer, a misaligned x, n / rows / row_stride / top_k or a sampler parameter outside its
+ * range), MI355X_E_WORKSPACE (missing, misaligned or too small) or MI355X_E_NODEVICE, in that
+ * order, before any device access. */
+#define MI355X_SAMPLE_MAX_K 64
+struct mi355x_sampler { int32_t top_k; float temp, top_p, min_p; };
+size_t mi355x_topk_workspace_size(int64_t n, int64_t rows);
+int mi355x_topk(const float *x, int64_t n, int top_k, int32_t *idx, float *val, void *workspace, size_t workspace_size,
+                void *stream);
+int mi355x_topk_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int top_k, int32_t *idx, float *val,
+                     void *workspace, size_t workspace_size, void *stream);
+int mi355x_sample(const float *x, int64_t n, const struct mi355x_sampler *s, const float *u, int32_t *out,
+                  void *workspace, size_t workspace_size, void *stream);
+int mi355x_sample_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, const struct mi355x_sampler *s,
+                       const float *u /* [rows] */, int32_t *out /* [rows] */, void *workspace, size_t workspace_size,
+                       void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -597,12 +650,27 @@ int mi355x_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
  *                p < n_hist (unsigned compares: a negative or overrun value writes nothing
  *                outside its array). p and c are written even at the end of the cache: a
  *                further replay meets ATTN_BATCH's cell or position outside the cache (NaN row,
- *                caches untouched). An F16 mask or I64 cells are not taken. */
+ *                caches untouched). An F16 mask or I64 cells are not taken.
+ *   SAMPLE       mi355x_sample of src0 (ARGMAX's vector); one launch, never fused or elided; its
+ *                counter and words belong to the backend (a buffer of their own). op_params =
+ *                {form, top_k, temp bits, top_p bits, min_p bits}, validated where the node is
+ *                enqueued. form 0: src1 F32 u [1] -> I32 [1], the token. form 1, the step-inputs
+ *                form (LlamaDecoder.generate(sampler=...)): src1, src2, src3 as ARGMAX's pos, rope
+ *                table and history, src4 F32 draws [n_draws] -> I32 [2 + head_dim]: ARGMAX's
+ *                writes with the sampled token, its draw u = draws[pos + 1] if pos + 1 < n_draws
+ *                (unsigned), else 0.0f (which picks c_0).
+ *   SAMPLE_BATCH mi355x_sample_rows of src0 (ARGMAX_BATCH's matrix); one launch, never fused or
+ *                elided. op_params = {form, top_k, temp bits, top_p bits, min_p bits, cell_stride,
+ *                n_kv}. form 0: src1 F32 u [T] -> I32 [T]. form 1: src1 .. src4 as ARGMAX_BATCH's
+ *                pos, cells, mask and history, src5 F32 draws [n_draws, T] (nb[1] the row stride)
+ *                -> I32 [T]: ARGMAX_BATCH's writes with row i's sampled token, its draw
+ *                draws[i][pos[i] + 1] where that entry exists, else 0.0f. */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
     MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
+    MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */

@@ -14,6 +14,12 @@ cache (sequence s holds the cells c with c % n_seq == s: cell_stride = n_seq).
     python tools/generate_batch_bench.py [--seqs 4,8] [--cells 2048] [--rounds 5] [--chunks 32,128]
                                          [--attn-stream]
 
+--sampler adds the sampling leg to the same session (rounds interleaved with a, b, c):
+  s  generate_batch(sampler=Sampler()) at every --chunks value (the SAMPLE_BATCH node; llama.cpp's
+     default chain)
+  h  (c) with sampled tokens: per row the rule of tests/sample_ref.py on the candidates of a numpy
+     argpartition top-k (numpy's exp in place of the rule's v_expf, which only makes the loop faster)
+
 A cache (n_seq * (cells + steps), rounded up to 32) larger than the attention kernels take (7616
 cells at head_dim 64) is reported as "not run" unless --attn-stream sets mi355x_attn_stream mode 1.
 Also times the kq_argmax_rows launch alone (event timing, the matrix written by the launch just
@@ -27,13 +33,13 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ggml-neon-opt_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "ggml-neon-opt_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import ggml_mi355x as g  # noqa: E402
 from bench import Token  # noqa: E402
-from ggml_mi355x.llama import LlamaDecoder  # noqa: E402
+from ggml_mi355x.llama import LlamaDecoder, Sampler  # noqa: E402
 
 MAX_CTX = 7616  # check_attn: 6 hd + 6 n_ctx + 64 hd + 16 + 2 n_ctx <= 64 KB at head_dim 64
 STEPS = 128
@@ -60,7 +66,7 @@ def rows_argmax(lg):
     return np.argmax(np.where(np.isnan(lg), -np.inf, lg), axis=1)
 
 
-def measure(tk, be, n_seq, cells, rounds, chunks, gen):
+def measure(tk, be, n_seq, cells, rounds, chunks, gen, sampler=None):
     n_ctx = (n_seq * (cells + STEPS) + 31) // 32 * 32
     if n_ctx > MAX_CTX:
         return None
@@ -103,8 +109,35 @@ def measure(tk, be, n_seq, cells, rounds, chunks, gen):
                         mask[s, cl[s]] = 0.0
         return timed(be, body)
 
+    def run_s(chunk):
+        return timed(be, lambda: dec.generate_batch(tok0, pos0, cells0, mask0, STEPS, n_ctx, cell_stride=n_seq, chunk=chunk,
+                                                    sampler=sampler))
+
+    def run_h():
+        from generate_bench import host_topk
+        from tests import sample_ref as R
+        draws = [sampler.draws(n_ctx + 1, s) for s in range(n_seq)]
+
+        def body():
+            tok, pos, cl, mask = list(tok0), list(pos0), list(cells0), mask0.copy()
+            for _ in range(STEPS):
+                lg = dec.step_batch(tok, pos, cl, mask, n_ctx)
+                be.synchronize()
+                lg = lg.cpu().numpy()
+                for s in range(n_seq):
+                    tok[s] = R.chain(lg[s], host_topk(lg[s], sampler.top_k), draws[s][pos[s] + 1], sampler.top_p,
+                                     sampler.min_p, sampler.temp, expf=np.exp)["token"]
+                    pos[s] += 1
+                    cl[s] += n_seq
+                    if cl[s] < n_ctx:
+                        mask[s, cl[s]] = 0.0
+        return timed(be, body)
+
     fns = {f"a_chunk{c}": (lambda c=c: run_a(c)) for c in chunks}
     fns.update(b=run_b, c=run_c)
+    if sampler is not None:
+        fns.update({f"s_chunk{c}": (lambda c=c: run_s(c)) for c in chunks})
+        fns["h"] = run_h
     for fn in fns.values():  # capture + warm
         fn()
     res = {v: [] for v in fns}
@@ -177,6 +210,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--chunks", default="32,128")
     ap.add_argument("--model", default="tinyllama-1.1b")
+    ap.add_argument("--sampler", action="store_true", help="add the sampling leg (s, h)")
     ap.add_argument("--attn-stream", action="store_true",
                     help="mi355x_attn_stream mode 1: caches past the attention kernels' sizes run on the streamed kernels")
     args = ap.parse_args()
@@ -194,7 +228,7 @@ def main():
     chunks = [int(c) for c in args.chunks.split(",")]
     res = []
     for n_seq in [int(s) for s in args.seqs.split(",")]:
-        r = measure(tk, be, n_seq, args.cells, args.rounds, chunks, gen)
+        r = measure(tk, be, n_seq, args.cells, args.rounds, chunks, gen, Sampler(seed=1) if args.sampler else None)
         res.append(r if r is not None else dict(n_seq=n_seq, cells_per_seq=args.cells, not_run="cache too large"))
         if r is None:
             print(f"seqs {n_seq} cells/seq {args.cells}: not run (cache too large; --attn-stream)", flush=True)

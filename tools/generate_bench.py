@@ -18,6 +18,17 @@ entries for every --slices value (ARGMAX_SLICE; 0: the library's default).
 head GEMV that wrote its logits, and the whole token's launches summed).
 
 With an older library under MI355X_LIB only --variants a runs (no generate in it).
+
+--sampler: the sampling leg instead, three timings in one session, rounds interleaved:
+  b  LlamaDecoder.generate, greedy
+  s  LlamaDecoder.generate(sampler=Sampler()) (llama.cpp's default chain; the SAMPLE node)
+  h  the loop a user writes for sampled tokens: step, synchronize, logits to the host, the rule of
+     tests/sample_ref.py on the candidates of a numpy argpartition top-k (numpy's exp in place of
+     the rule's v_expf, which only makes the host loop faster)
+and kq_topk's own launch time (event timing, behind the launch that wrote the vector) at 32000 and
+128256 entries for the plain top-k (k 40) and the sampled token, next to kq_argmax on the same
+vector in the same run. Under a KQ_SAMPLE_DIAG variant library (make variant-sample) the same
+launch stops early, which splits its time: 1: no merge on the last arriver, 2: no sampling tail.
 """
 import argparse
 import json
@@ -126,17 +137,114 @@ def argmax_launch_us(dev, n, slice_, reps=200):
         g.debug_knob("ARGMAX_SLICE", prev if prev else float("nan"))
 
 
+def host_topk(x, k):
+    """The k largest entries by numpy's argpartition, sorted by (-value, index): ref_topk's
+    candidates on finite logits, which is all the timed loop meets. Not the rule in general: a NaN
+    counts as -inf here (the rule never takes one), and a k-th value of -inf takes every entry."""
+    x = np.where(np.isnan(x), -np.inf, x)
+    k = min(k, x.size)
+    part = np.argpartition(-x, k - 1)[:k]
+    kth = x[part].min()
+    cand = np.flatnonzero(x >= kth)  # (ties at the k-th value: all of them, the smallest indices win)
+    return cand[np.lexsort((cand, -x[cand]))][:k]
+
+
+def host_sample_loop(tk, be, tok, pos, n, sp, draws):
+    from tests import sample_ref as R
+    for p in range(pos, pos + n):
+        tk.dec.step(tok, p)
+        be.synchronize()
+        x = tk.dec.logits.cpu().numpy()
+        tok = R.chain(x, host_topk(x, sp.top_k), draws[p + 1], sp.top_p, sp.min_p, sp.temp, expf=np.exp)["token"]
+    return tok
+
+
+def topk_launch_us(dev, n, reps=200):
+    """Median event times of kq_argmax, kq_topk (k 40) and the sampled token's kq_topk on one vector
+    that an elementwise launch writes just before."""
+    a, b, x = torch.randn(n, device=dev) * 4, torch.randn(n, device=dev) * 4, torch.empty(n, device=dev)
+    ws1 = torch.zeros(g.argmax_workspace_size(n), dtype=torch.uint8, device=dev)
+    ws = torch.zeros(g.topk_workspace_size(n), dtype=torch.uint8, device=dev)
+    out = torch.zeros(1, dtype=torch.int32, device=dev)
+    u = torch.full((1,), 0.37, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    res = {"workgroups": g.argmax_plan(n)[0]}
+    for name, fn in (("kq_argmax", lambda: g.argmax(x, out=out, workspace=ws1)),
+                     ("kq_topk_k40", lambda: g.topk(x, 40, workspace=ws)),
+                     ("kq_topk_sample", lambda: g.sample(x, u, out=out, workspace=ws))):
+        for _ in range(10):
+            g.add(a, b, out=x)
+            fn()
+        torch.cuda.synchronize()
+        g.timing_enable(True)
+        for _ in range(reps):
+            g.add(a, b, out=x)
+            fn()
+        rows = g.timing_read()
+        g.timing_enable(False)
+        ms = [r[2] for r in rows if "argmax" in r[0] or "topk" in r[0]]
+        assert len(ms) == reps
+        res[name] = {"us_p50": round(statistics.median(ms) * 1e3, 2), "us_min": round(min(ms) * 1e3, 2)}
+    return res
+
+
+def sampler_leg(args, dev, be, tk):
+    from ggml_mi355x.llama import Sampler
+    sp = Sampler(seed=1)
+    draws = sp.draws(tk.dec.n_ctx + 1)
+
+    def run_s(t, b):
+        t.dec.reset()
+        torch.cuda.synchronize()
+        tok = t.dec.generate(t.tokens[0], 0, WARM, sampler=sp)[-1]
+        return timed(b, lambda: t.dec.generate(tok, WARM, STEPS, chunk=args.chunk, sampler=sp))
+
+    def run_h(t, b):
+        t.dec.reset()
+        torch.cuda.synchronize()
+        tok = host_sample_loop(t, b, t.tokens[0], 0, WARM, sp, draws)
+        return timed(b, lambda: host_sample_loop(t, b, tok, WARM, STEPS, sp, draws))
+
+    fns = {"b": lambda t, b: run_b(t, b, args.chunk), "s": run_s, "h": run_h}
+    for fn in fns.values():  # capture + warm
+        fn(tk, be)
+    res = {v: [] for v in fns}
+    for _ in range(args.rounds):
+        for v, fn in fns.items():
+            res[v].append(fn(tk, be))
+    med = {v: statistics.median(x) for v, x in res.items()}
+    out = {"model": "tinyllama-1.1b", "leg": "sampler", "tokens": STEPS, "warmup": WARM, "rounds": args.rounds,
+           "chunk": args.chunk, "lib": os.path.relpath(g.LIB_PATH, ROOT),
+           "sampler": dict(top_k=sp.top_k, top_p=sp.top_p, min_p=sp.min_p, temp=sp.temp),
+           "ms_per_token": {v: [round(x, 4) for x in r] for v, r in res.items()},
+           "median_ms_per_token": {v: round(m, 4) for v, m in med.items()},
+           "h_minus_s_ms": round(med["h"] - med["s"], 4), "s_minus_b_ms": round(med["s"] - med["b"], 4),
+           "sampled_generate_below_host_loop_in_every_round": bool(max(res["s"]) < min(res["h"])),
+           "launch_us": {str(n): topk_launch_us(dev, n) for n in (32000, 128256)}}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="a,b,c")
     ap.add_argument("--slices", default="0,512,1024,2048,4096")
     ap.add_argument("--chunk", type=int, default=32, help="generate's steps between two synchronizations")
+    ap.add_argument("--sampler", action="store_true", help="the sampling leg: generate greedy / sampled / the host loop")
+    ap.add_argument("--launch-only", action="store_true", help="with --sampler: only the launches alone (diag variants)")
     args = ap.parse_args()
     variants = args.variants.split(",")
     dev = torch.device("cuda:0")
+    if args.sampler and args.launch_only:
+        print(json.dumps({"lib": os.path.relpath(g.LIB_PATH, ROOT),
+                          "launch_us": {str(n): topk_launch_us(dev, n) for n in (32000, 128256)}}))
+        return
     be = g.Backend(0)
     tk = bench.Token("tinyllama-1.1b", dev, 0x51A7, be, 160)
+    if args.sampler:
+        sampler_leg(args, dev, be, tk)
+        be.close()
+        return
     fns = {"a": run_a, "b": lambda t, b: run_b(t, b, args.chunk), "c": run_c}
     for v in variants:  # capture + warm
         fns[v](tk, be)
