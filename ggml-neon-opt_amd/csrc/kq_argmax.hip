@@ -54,13 +54,7 @@ struct ArgmaxArgs {
     unsigned long long *part;  // workspace: one word per workgroup ...
     uint32_t *cnt;             // ... behind the arrival counter
     int32_t *out;              // plain form: [1]; step form: the decoder's input block [2 + hd]
-    // step-inputs form (pos != null): out[0] = token, out[1] = *pos + 1, out[2 ..] = the bits of
-    // table row *pos + 1 where it exists, hist[*pos + 1] = token where it exists
-    const int32_t *pos;
-    const uint32_t *table;
-    int32_t *hist;
-    uint32_t rows, n_hist;
-    int hd;
+    TokenStepArgs step;
 };
 
 __device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
@@ -136,18 +130,9 @@ __device__ __forceinline__ bool hand_off(unsigned long long w, unsigned long lon
     __shared__ unsigned long long red[4];
     __shared__ int flag;
     const int t = (int)threadIdx.x;
-    // ---- the word write-through, drained, barrier, one add; the last arriver goes on
+    // ---- the word write-through, then the arrival; the last arriver goes on
     if (t == 0) __hip_atomic_store(part + wg, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-        const uint32_t old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = old == (uint32_t)(wgs - 1);
-        if (last) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch starts at 0
-        flag = last;
-    }
-    __syncthreads();
-    if (!flag) return false;
+    if (!arrive_last(cnt, wgs, &flag)) return false;
 
     // ---- the last arriver: every workgroup's word (wgs <= 256: one per thread), sc1 loads
     w = t < wgs ? __hip_atomic_load(part + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
@@ -163,22 +148,13 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax(const ArgmaxArgs p) 
     const int hi = p.n - lo < p.slice ? p.n : lo + p.slice;
     int32_t token;
     if (!hand_off(slice_word(p.x, lo, hi), p.part, p.cnt, (int)blockIdx.x, p.wgs, p.n, &token)) return;
-    if (!p.pos) {
+    if (!p.step.pos) {
         if (t == 0) p.out[0] = token;
         return;
     }
-    // step inputs. pos may be out[1]: every thread's load of it has returned (the barrier alone
-    // waits for no counter) before one of them writes it
-    uint32_t next = (uint32_t)*p.pos + 1u;
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(next)::"memory");
-    __syncthreads();
-    if (t == 0) {
-        p.out[0] = token;
-        p.out[1] = (int32_t)next;
-        if (next < p.n_hist) p.hist[next] = token;
-    }
-    if (next < p.rows)
-        for (int k = t; k < p.hd; k += kArgmaxThreads) p.out[2 + k] = (int32_t)p.table[(size_t)next * p.hd + k];
+    const uint32_t next = p.step.next();
+    __syncthreads();  // pos may be out + 1: every thread has read it before one of them writes it
+    p.step.write(p.out, next, token);
 }
 
 struct ArgmaxRowsArgs {
@@ -187,13 +163,7 @@ struct ArgmaxRowsArgs {
     int n, slice, wgs;
     uint8_t *ws;         // workspace, per row (kArgmaxRowBytes): the counter's line, then the row's words
     int32_t *out;        // [T]: the rows' indices (step form: the sequences' next tokens)
-    // step-inputs form (pos != null): row i's last arriver also advances pos[i] and cells[i], shows
-    // the new cell in mask row i and files the token in history row i, where those entries exist
-    int32_t *pos, *cells, *hist;
-    float *mask;
-    int64_t mask_stride, hist_stride;  // entries between two rows
-    uint32_t n_kv, n_hist;
-    int cell_stride;
+    RowsStepArgs step;
 };
 
 __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax_rows(const ArgmaxRowsArgs p) {
@@ -205,19 +175,13 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax_rows(const ArgmaxRow
     int32_t token;
     if (!hand_off(slice_word(p.x + row * p.row_stride, lo, hi), part, cnt, (int)blockIdx.x, p.wgs, p.n, &token)) return;
     if (threadIdx.x != 0) return;
-    if (!p.pos) {
+    if (!p.step.pos) {
         p.out[row] = token;
         return;
     }
-    // step inputs: the one thread that touches row i's entries; its loads of pos[i] and cells[i]
-    // have returned before it writes either
-    uint32_t np = (uint32_t)p.pos[row] + 1u, nc = (uint32_t)p.cells[row] + (uint32_t)p.cell_stride;
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(np), "+v"(nc)::"memory");
-    p.out[row] = token;
-    p.pos[row] = (int32_t)np;
-    p.cells[row] = (int32_t)nc;
-    if (nc < p.n_kv) p.mask[row * p.mask_stride + nc] = 0.0f;  // the cell the next step writes: visible to its own row
-    if (np < p.n_hist) p.hist[row * p.hist_stride + np] = token;
+    uint32_t np, nc;
+    p.step.next(row, np, nc);
+    p.step.write(p.out, row, np, nc, token);
 }
 
 }  // namespace
@@ -243,11 +207,8 @@ int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *ste
                   hipStream_t stream) {
     int wgs = 0;
     int64_t slice = 0;
-    if (!x || !out || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
-    if (step && (!step->pos || !step->table || !step->hist || step->hd <= 0 || step->rows < 0 || step->n_hist < 0))
-        return MI355X_E_INVAL;
-    if (!ws || ((uintptr_t)ws & 7u) || ws_size < argmax_workspace(n)) return MI355X_E_WORKSPACE;
-    if (!device_ok()) return MI355X_E_NODEVICE;
+    if (!out || !input_ok(x, n, 1, (n + 3) & ~(int64_t)3, &wgs, &slice) || (step && !step_ok(*step))) return MI355X_E_INVAL;
+    if (const int rc = workspace_status(ws, ws_size, argmax_workspace(n))) return rc;
     ArgmaxArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x;
@@ -257,14 +218,7 @@ int launch_argmax(const float *x, int64_t n, int32_t *out, const ArgmaxStep *ste
     p.cnt = (uint32_t *)ws;
     p.part = (unsigned long long *)((uint8_t *)ws + kArgmaxCounterBytes);
     p.out = out;
-    if (step) {
-        p.pos = step->pos;
-        p.table = (const uint32_t *)step->table;
-        p.hist = step->hist;
-        p.rows = (uint32_t)step->rows;
-        p.n_hist = (uint32_t)step->n_hist;
-        p.hd = step->hd;
-    }
+    if (step) p.step = step_args(*step);
     return timed_launch("kq::kq_argmax", (double)n * 4.0, kq_argmax, dim3((unsigned)wgs), dim3(kArgmaxThreads), 0, stream,
                         p);
 }
@@ -278,14 +232,8 @@ int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
                        const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream) {
     int wgs = 0;
     int64_t slice = 0;
-    if (!x || !out || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
-    if (rows < 1 || rows > kArgmaxMaxRows || row_stride < n || (row_stride & 3)) return MI355X_E_INVAL;
-    if (step && (!step->pos || !step->cells || !step->mask || !step->hist || step->cell_stride < 1 || step->n_kv < 0 ||
-                 step->n_kv > 0x7fffffff || step->n_hist < 0 || step->n_hist > 0x7fffffff ||
-                 step->mask_stride < step->n_kv || step->hist_stride < step->n_hist))
-        return MI355X_E_INVAL;
-    if (!ws || ((uintptr_t)ws & 7u) || ws_size < argmax_rows_workspace(n, rows)) return MI355X_E_WORKSPACE;
-    if (!device_ok()) return MI355X_E_NODEVICE;
+    if (!out || !input_ok(x, n, rows, row_stride, &wgs, &slice) || (step && !step_ok(*step))) return MI355X_E_INVAL;
+    if (const int rc = workspace_status(ws, ws_size, argmax_rows_workspace(n, rows))) return rc;
     ArgmaxRowsArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x;
@@ -295,17 +243,7 @@ int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
     p.wgs = wgs;
     p.ws = (uint8_t *)ws;
     p.out = out;
-    if (step) {
-        p.pos = step->pos;
-        p.cells = step->cells;
-        p.mask = step->mask;
-        p.hist = step->hist;
-        p.mask_stride = step->mask_stride;
-        p.hist_stride = step->hist_stride;
-        p.n_kv = (uint32_t)step->n_kv;
-        p.n_hist = (uint32_t)step->n_hist;
-        p.cell_stride = step->cell_stride;
-    }
+    if (step) p.step = step_args(*step);
     return timed_launch("kq::kq_argmax_rows", (double)rows * (double)n * 4.0, kq_argmax_rows,
                         dim3((unsigned)wgs, (unsigned)rows), dim3(kArgmaxThreads), 0, stream, p);
 }

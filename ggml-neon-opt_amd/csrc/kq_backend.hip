@@ -26,7 +26,9 @@
 
 using kq::attn_batch_desc_of;
 using kq::attn_desc_of;
+using kq::rows_step_of;
 using kq::sampler_of;
+using kq::token_step_of;
 using kq::f_of;
 using kq::Launch;
 using kq::LaunchKind;
@@ -343,9 +345,7 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             if (t->op_params[0] == 0)
                 return kq::launch_argmax((const float *)t->src[0]->data, n, (int32_t *)t->data, nullptr, b->am,
                                          b->am_size, st);
-            const mi355x_tensor *tab = t->src[2];
-            const kq::ArgmaxStep step = {(const int32_t *)t->src[1]->data, (const float *)tab->data,
-                                         (int32_t *)t->src[3]->data, tab->ne[1], t->src[3]->ne[0], (int)tab->ne[0]};
+            const kq::ArgmaxStep step = token_step_of(t);
             return kq::launch_argmax((const float *)t->src[0]->data, n, (int32_t *)t->data, &step, b->am, b->am_size, st);
         }
         case MI355X_OP_ARGMAX_BATCH: {
@@ -353,17 +353,7 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             if (t->op_params[0] == 0)
                 return kq::launch_argmax_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], (int32_t *)t->data,
                                               nullptr, b->am, b->am_size, st);
-            const mi355x_tensor *mask = t->src[3], *hist = t->src[4];
-            kq::ArgmaxRowsStep step;
-            step.pos = (int32_t *)t->src[1]->data;
-            step.cells = (int32_t *)t->src[2]->data;
-            step.mask = (float *)mask->data;
-            step.hist = (int32_t *)hist->data;
-            step.mask_stride = (int64_t)(mask->nb[1] / 4);
-            step.hist_stride = (int64_t)(hist->nb[1] / 4);
-            step.n_kv = t->op_params[2];
-            step.n_hist = hist->ne[0];
-            step.cell_stride = t->op_params[1];
+            const kq::ArgmaxRowsStep step = rows_step_of(t, 1);
             return kq::launch_argmax_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], (int32_t *)t->data, &step,
                                           b->am, b->am_size, st);
         }
@@ -374,10 +364,7 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             if (t->op_params[0] == 0)
                 return kq::launch_topk((const float *)t->src[0]->data, n, 0, nullptr, nullptr, &sp,
                                        (const float *)t->src[1]->data, (int32_t *)t->data, nullptr, b->sm, b->sm_size, st);
-            const mi355x_tensor *tab = t->src[2];
-            const kq::SampleStep step = {{(const int32_t *)t->src[1]->data, (const float *)tab->data,
-                                          (int32_t *)t->src[3]->data, tab->ne[1], t->src[3]->ne[0], (int)tab->ne[0]},
-                                         t->src[4]->ne[0]};
+            const kq::SampleStep step = {token_step_of(t), t->src[4]->ne[0]};
             return kq::launch_topk((const float *)t->src[0]->data, n, 0, nullptr, nullptr, &sp,
                                    (const float *)t->src[4]->data, (int32_t *)t->data, &step, b->sm, b->sm_size, st);
         }
@@ -389,19 +376,8 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
                 return kq::launch_topk_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], 0, nullptr, nullptr, &sp,
                                             (const float *)t->src[1]->data, (int32_t *)t->data, nullptr, b->sm, b->sm_size,
                                             st);
-            const mi355x_tensor *mask = t->src[3], *hist = t->src[4], *draws = t->src[5];
-            kq::SampleRowsStep step;
-            step.a.pos = (int32_t *)t->src[1]->data;
-            step.a.cells = (int32_t *)t->src[2]->data;
-            step.a.mask = (float *)mask->data;
-            step.a.hist = (int32_t *)hist->data;
-            step.a.mask_stride = (int64_t)(mask->nb[1] / 4);
-            step.a.hist_stride = (int64_t)(hist->nb[1] / 4);
-            step.a.n_kv = t->op_params[6];
-            step.a.n_hist = hist->ne[0];
-            step.a.cell_stride = t->op_params[5];
-            step.draws_stride = (int64_t)(draws->nb[1] / 4);
-            step.n_draws = draws->ne[0];
+            const mi355x_tensor *draws = t->src[5];
+            const kq::SampleRowsStep step = {rows_step_of(t, 5), (int64_t)(draws->nb[1] / 4), draws->ne[0]};
             return kq::launch_topk_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], 0, nullptr, nullptr, &sp,
                                         (const float *)draws->data, (int32_t *)t->data, &step, b->sm, b->sm_size, st);
         }
@@ -566,6 +542,22 @@ int enqueue(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<La
 // it allocates outside any capture, after waiting for the stream and dropping the captured
 // graphs that may reference the old allocation.
 
+// The device buffer *buf grown to `need` bytes (never shrunk), zeroed where `zero`: on the backend
+// stream (non-blocking: a legacy-stream memset is not ordered before its next launch), then waited for.
+int grow_buffer(mi355x_backend *b, void **buf, size_t *size, size_t need, bool zero) {
+    if (need <= *size) return MI355X_OK;
+    hipStreamSynchronize(b->stream);
+    drop_graph(b);
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *size = 0;
+    if (hipMalloc(buf, need) != hipSuccess) return MI355X_E_WORKSPACE;
+    *size = need;
+    if (zero && (hipMemsetAsync(*buf, 0, need, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess))
+        return MI355X_E_WORKSPACE;
+    return MI355X_OK;
+}
+
 // every node supported; the workspace grown to the largest MUL_MAT's need
 int ensure_workspace(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
     size_t ws = 0;
@@ -581,15 +573,7 @@ int ensure_workspace(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes
             ws = need > ws ? need : ws;
         }
     }
-    if (ws <= b->workspace_size) return MI355X_OK;
-    hipStreamSynchronize(b->stream);
-    drop_graph(b);
-    if (b->workspace) hipFree(b->workspace);
-    b->workspace = nullptr;
-    b->workspace_size = 0;
-    if (hipMalloc(&b->workspace, ws) != hipSuccess) return MI355X_E_WORKSPACE;
-    b->workspace_size = ws;
-    return MI355X_OK;
+    return grow_buffer(b, &b->workspace, &b->workspace_size, ws, false);
 }
 
 // the fused attention + o-proj launches' buffer: sized, and its counters zeroed
@@ -635,17 +619,7 @@ int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_n
         if (nodes[i]->op == MI355X_OP_ARGMAX) need = std::max(need, kq::argmax_workspace(nodes[i]->src[0]->ne[0]));
         else if (nodes[i]->op == MI355X_OP_ARGMAX_BATCH)
             need = std::max(need, kq::argmax_rows_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
-    if (need <= b->am_size) return MI355X_OK;
-    hipStreamSynchronize(b->stream);
-    drop_graph(b);
-    if (b->am) hipFree(b->am);
-    b->am = nullptr;
-    b->am_size = 0;
-    if (hipMalloc(&b->am, need) != hipSuccess) return MI355X_E_WORKSPACE;
-    b->am_size = need;
-    if (hipMemsetAsync(b->am, 0, need, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
-        return MI355X_E_WORKSPACE;
-    return MI355X_OK;
+    return grow_buffer(b, &b->am, &b->am_size, need, true);
 }
 
 // ... and the SAMPLE and SAMPLE_BATCH nodes', in a buffer of their own (b->am keeps its layout)
@@ -655,17 +629,7 @@ int ensure_sample_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_n
         if (nodes[i]->op == MI355X_OP_SAMPLE) need = std::max(need, kq::topk_workspace(nodes[i]->src[0]->ne[0], 1));
         else if (nodes[i]->op == MI355X_OP_SAMPLE_BATCH)
             need = std::max(need, kq::topk_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
-    if (need <= b->sm_size) return MI355X_OK;
-    hipStreamSynchronize(b->stream);
-    drop_graph(b);
-    if (b->sm) hipFree(b->sm);
-    b->sm = nullptr;
-    b->sm_size = 0;
-    if (hipMalloc(&b->sm, need) != hipSuccess) return MI355X_E_WORKSPACE;
-    b->sm_size = need;
-    if (hipMemsetAsync(b->sm, 0, need, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
-        return MI355X_E_WORKSPACE;
-    return MI355X_OK;
+    return grow_buffer(b, &b->sm, &b->sm_size, need, true);
 }
 
 // The persistent layers' counter blocks: one per Layer launch, zeroed whenever they are

@@ -299,6 +299,25 @@ struct ArgmaxRowsStep {
 size_t argmax_rows_workspace(int64_t n, int64_t rows);
 int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
                        const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream);
+// What the launchers of kq_argmax.hip and kq_sample.hip check first. Their statuses come in this
+// order: E_INVAL (input_ok, the launcher's own outputs, step_ok), then workspace_status'
+// E_WORKSPACE, then its E_NODEVICE.
+// x, the split of n entries and the rows (a vector: one row of n entries rounded up to 16 bytes)
+inline bool input_ok(const float *x, int64_t n, int64_t rows, int64_t row_stride, int *wgs, int64_t *slice) {
+    if (!x || ((uintptr_t)x & 15u) || argmax_plan(n, wgs, slice) != MI355X_OK) return false;
+    return rows >= 1 && rows <= kArgmaxMaxRows && row_stride >= n && !(row_stride & 3);
+}
+inline int workspace_status(const void *ws, size_t ws_size, size_t need) {
+    if (!ws || ((uintptr_t)ws & 7u) || ws_size < need) return MI355X_E_WORKSPACE;
+    return device_ok() ? MI355X_OK : MI355X_E_NODEVICE;
+}
+inline bool step_ok(const ArgmaxStep &s) {
+    return s.pos && s.table && s.hist && s.hd > 0 && s.rows >= 0 && s.n_hist >= 0;
+}
+inline bool step_ok(const ArgmaxRowsStep &s) {
+    return s.pos && s.cells && s.mask && s.hist && s.cell_stride >= 1 && s.n_kv >= 0 && s.n_kv <= 0x7fffffff &&
+           s.n_hist >= 0 && s.n_hist <= 0x7fffffff && s.mask_stride >= s.n_kv && s.hist_stride >= s.n_hist;
+}
 
 // ---------------------------------------------------------------- kq_sample.hip
 // The exact top-k of an f32 vector and the sampler chain on it, one launch (kq_topk; kq_topk_rows

@@ -249,6 +249,19 @@ void sampler_of(const mi355x_tensor *t, mi355x_sampler &s) {
     s.min_p = f_of(t->op_params[4]);
 }
 
+ArgmaxStep token_step_of(const mi355x_tensor *t) {
+    const mi355x_tensor *tab = t->src[2], *hist = t->src[3];
+    return {(const int32_t *)t->src[1]->data, (const float *)tab->data, (int32_t *)hist->data, tab->ne[1], hist->ne[0],
+            (int)tab->ne[0]};
+}
+
+ArgmaxRowsStep rows_step_of(const mi355x_tensor *t, int first_param) {
+    const mi355x_tensor *mask = t->src[3], *hist = t->src[4];
+    return {(int32_t *)t->src[1]->data, (int32_t *)t->src[2]->data, (float *)mask->data, (int32_t *)hist->data,
+            (int64_t)(mask->nb[1] / 4), (int64_t)(hist->nb[1] / 4), t->op_params[first_param + 1], hist->ne[0],
+            t->op_params[first_param]};
+}
+
 // ATTN_BATCH: the ATTN_DECODE operands, the cells (src7), the mask (src8) and n_kv
 void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d) {
     attn_desc_of(t, d.a);

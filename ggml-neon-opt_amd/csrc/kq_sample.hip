@@ -31,14 +31,14 @@
 // Decomposition. The slices are argmax_plan(n)'s. Workgroup s builds the words of its slice (16-B
 // loads; the vector's last n % 4 entries by scalar loads), selects the slice's min(top_k,
 // entries) largest and stores them SORTED, largest first, in its 64 places of the workspace;
-// places it does not fill up to top_k hold 0. Hand-off: the sequence of kq_argmax's hand_off,
-// restated in arrive_last (kq_argmax_device.h; two copies, hand_off keeps its own): the words
-// write-through, drained, barrier, one agent-scope add; the last arriver stores 0 back to the
-// counter; nobody waits. The last arriver reads each slice's FIRST word (one per thread), keeps the min(top_k,
-// wgs) slices with the largest first words (a slice whose maximum is not among the top_k largest
-// maxima cannot contribute), loads only those slices' words (<= 64 x 64 words, 32 KB of LDS),
-// selects and sorts the final m with the same routine, and one of its waves runs the rule above:
-// the e and f values in parallel, the sums in order.
+// places it does not fill up to top_k hold 0. Hand-off: kq_argmax's, on the same arrive_last
+// (kq_argmax_device.h): the words write-through, drained, barrier, one agent-scope add; the last
+// arriver stores 0 back to the counter; nobody waits. The last arriver reads each slice's FIRST
+// word (one per thread), keeps the min(top_k, wgs) slices with the largest first words (a slice
+// whose maximum is not among the top_k largest maxima cannot contribute), loads only those
+// slices' words (<= 64 x 64 words, 32 KB of LDS), selects and sorts the final m with the same
+// routine, and one of its waves runs the rule above: the e and f values in parallel, the sums in
+// order.
 //
 // Selection (select_sorted, one routine at both levels): a radix select on the whole 64-bit word,
 // 8 bits a pass from the top, histograms in LDS; bin 255 - t is thread t's, a scan over the
@@ -307,11 +307,15 @@ struct TopkArgs {
     SamplerArgs sp;
     const float *u;  // TOPK_SAMPLE: the draw [1]; TOPK_STEP: the draws table [n_draws]
     int32_t *out;    // TOPK_SAMPLE: [1]; TOPK_STEP: the decoder's input block [2 + hd], as kq_argmax's
+    // TOPK_STEP: TokenStepArgs' members with n_draws among them, not the struct embedded: with
+    // n_draws behind it the kernarg loads move, and the plain form at 128256 entries measured
+    // 0.2 us slower (profiles/token_selection_refactor.txt)
     const int32_t *pos;
     const uint32_t *table;
     int32_t *hist;
     uint32_t rows, n_hist, n_draws;
     int hd;
+    __device__ __forceinline__ TokenStepArgs step() const { return {pos, table, hist, rows, n_hist, hd}; }
 };
 
 __global__ void __launch_bounds__(kArgmaxThreads) kq_topk(const TopkArgs p) {
@@ -328,19 +332,12 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_topk(const TopkArgs p) {
         if (t == 0) p.out[0] = token;
         return;
     }
-    // step inputs, kq_argmax's: pos may be out[1], so every thread's load of it has returned
-    // before one of them writes it
-    uint32_t next = (uint32_t)*p.pos + 1u;
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(next)::"memory");
+    const TokenStepArgs step = p.step();
+    const uint32_t next = step.next();
     const float u = next < p.n_draws ? p.u[next] : 0.0f;
-    const int32_t token = sample_token(p.x, s, m, p.sp, u);  // (its barrier: behind every thread's load of pos)
-    if (t == 0) {
-        p.out[0] = token;
-        p.out[1] = (int32_t)next;
-        if (next < p.n_hist) p.hist[next] = token;
-    }
-    if (next < p.rows)
-        for (int k = t; k < p.hd; k += kArgmaxThreads) p.out[2 + k] = (int32_t)p.table[(size_t)next * p.hd + k];
+    // (its barrier: pos may be out + 1, and every thread has read it before one of them writes it)
+    const int32_t token = sample_token(p.x, s, m, p.sp, u);
+    step.write(p.out, next, token);
 }
 
 struct TopkRowsArgs {
@@ -353,13 +350,9 @@ struct TopkRowsArgs {
     SamplerArgs sp;
     const float *u;      // TOPK_SAMPLE: [rows]; TOPK_STEP: the draws [rows][draws_stride]
     int32_t *out;        // [rows]
-    // TOPK_STEP, kq_argmax_rows': row i's last arriver advances pos[i] and cells[i], shows the new
-    // cell in mask row i and files the token in history row i
-    int32_t *pos, *cells, *hist;
-    float *mask;
-    int64_t mask_stride, hist_stride, draws_stride;
-    uint32_t n_kv, n_hist, n_draws;
-    int cell_stride;
+    RowsStepArgs step;   // TOPK_STEP, kq_argmax_rows'
+    int64_t draws_stride;
+    uint32_t n_draws;
 };
 
 __global__ void __launch_bounds__(kArgmaxThreads) kq_topk_rows(const TopkRowsArgs p) {
@@ -378,24 +371,23 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_topk_rows(const TopkRowsArg
         if (threadIdx.x == 0) p.out[row] = token;
         return;
     }
-    // (row i's entries are touched by this workgroup alone, and written by its thread 0 alone,
-    // whose loads of pos[i] and cells[i] have returned before it writes either)
-    uint32_t np = (uint32_t)p.pos[row] + 1u, nc = (uint32_t)p.cells[row] + (uint32_t)p.cell_stride;
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(np), "+v"(nc)::"memory");
+    uint32_t np, nc;
+    p.step.next(row, np, nc);
     const float u = np < p.n_draws ? p.u[row * p.draws_stride + np] : 0.0f;
-    const int32_t token = sample_token(x, s, m, p.sp, u);
-    if (threadIdx.x != 0) return;
-    p.out[row] = token;
-    p.pos[row] = (int32_t)np;
-    p.cells[row] = (int32_t)nc;
-    if (nc < p.n_kv) p.mask[row * p.mask_stride + nc] = 0.0f;
-    if (np < p.n_hist) p.hist[row * p.hist_stride + np] = token;
+    p.step.write(p.out, row, np, nc, sample_token(x, s, m, p.sp, u));
 }
 
 bool top_k_ok(int top_k) { return top_k >= 1 && top_k <= kTopkMaxK; }
 
-bool workspace_ok(const void *ws, size_t ws_size, int64_t n, int64_t rows) {
-    return ws && !((uintptr_t)ws & 7u) && ws_size >= topk_workspace(n, rows);
+// where the result goes: the plain form's (sp null) idx / val, or the sampled token(s) with the draw(s)
+bool dest_ok(const mi355x_sampler *sp, int top_k, const int32_t *idx, const float *val, const float *u,
+             const int32_t *out) {
+    return sp ? sampler_ok(sp) && u && out : top_k_ok(top_k) && idx && val;
+}
+
+// a step's draws table: only a sampler has one
+bool draws_ok(const mi355x_sampler *sp, int64_t n_draws, int64_t draws_stride) {
+    return sp && n_draws >= 0 && n_draws <= 0x7fffffff && draws_stride >= n_draws;
 }
 
 }  // namespace
@@ -415,13 +407,10 @@ int launch_topk(const float *x, int64_t n, int top_k, int32_t *idx, float *val, 
                 int32_t *out, const SampleStep *step, void *ws, size_t ws_size, hipStream_t stream) {
     int wgs = 0;
     int64_t slice = 0;
-    if (!x || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
-    if (sp ? !sampler_ok(sp) || !u || !out : !top_k_ok(top_k) || !idx || !val) return MI355X_E_INVAL;
-    if (step && (!sp || !step->a.pos || !step->a.table || !step->a.hist || step->a.hd <= 0 || step->a.rows < 0 ||
-                 step->a.n_hist < 0 || step->n_draws < 0 || step->n_draws > 0x7fffffff))
+    if (!input_ok(x, n, 1, (n + 3) & ~(int64_t)3, &wgs, &slice) || !dest_ok(sp, top_k, idx, val, u, out))
         return MI355X_E_INVAL;
-    if (!workspace_ok(ws, ws_size, n, 1)) return MI355X_E_WORKSPACE;
-    if (!device_ok()) return MI355X_E_NODEVICE;
+    if (step && !(step_ok(step->a) && draws_ok(sp, step->n_draws, step->n_draws))) return MI355X_E_INVAL;
+    if (const int rc = workspace_status(ws, ws_size, topk_workspace(n, 1))) return rc;
     TopkArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x;
@@ -437,13 +426,9 @@ int launch_topk(const float *x, int64_t n, int top_k, int32_t *idx, float *val, 
     p.u = u;
     p.out = out;
     if (step) {
-        p.pos = step->a.pos;
-        p.table = (const uint32_t *)step->a.table;
-        p.hist = step->a.hist;
-        p.rows = (uint32_t)step->a.rows;
-        p.n_hist = (uint32_t)step->a.n_hist;
+        const TokenStepArgs a = step_args(step->a);
+        p.pos = a.pos, p.table = a.table, p.hist = a.hist, p.rows = a.rows, p.n_hist = a.n_hist, p.hd = a.hd;
         p.n_draws = (uint32_t)step->n_draws;
-        p.hd = step->a.hd;
     }
     return timed_launch("kq::kq_topk", (double)n * 4.0, kq_topk, dim3((unsigned)wgs), dim3(kArgmaxThreads), 0, stream, p);
 }
@@ -453,18 +438,9 @@ int launch_topk_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride
                      size_t ws_size, hipStream_t stream) {
     int wgs = 0;
     int64_t slice = 0;
-    if (!x || ((uintptr_t)x & 15u) || argmax_plan(n, &wgs, &slice) != MI355X_OK) return MI355X_E_INVAL;
-    if (rows < 1 || rows > kArgmaxMaxRows || row_stride < n || (row_stride & 3)) return MI355X_E_INVAL;
-    if (sp ? !sampler_ok(sp) || !u || !out : !top_k_ok(top_k) || !idx || !val) return MI355X_E_INVAL;
-    if (step) {
-        const ArgmaxRowsStep &a = step->a;
-        if (!sp || !a.pos || !a.cells || !a.mask || !a.hist || a.cell_stride < 1 || a.n_kv < 0 || a.n_kv > 0x7fffffff ||
-            a.n_hist < 0 || a.n_hist > 0x7fffffff || a.mask_stride < a.n_kv || a.hist_stride < a.n_hist ||
-            step->n_draws < 0 || step->n_draws > 0x7fffffff || step->draws_stride < step->n_draws)
-            return MI355X_E_INVAL;
-    }
-    if (!workspace_ok(ws, ws_size, n, rows)) return MI355X_E_WORKSPACE;
-    if (!device_ok()) return MI355X_E_NODEVICE;
+    if (!input_ok(x, n, rows, row_stride, &wgs, &slice) || !dest_ok(sp, top_k, idx, val, u, out)) return MI355X_E_INVAL;
+    if (step && !(step_ok(step->a) && draws_ok(sp, step->n_draws, step->draws_stride))) return MI355X_E_INVAL;
+    if (const int rc = workspace_status(ws, ws_size, topk_workspace(n, rows))) return rc;
     TopkRowsArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x;
@@ -480,20 +456,7 @@ int launch_topk_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride
     if (sp) p.sp = {sp->temp, sp->top_p, sp->min_p};
     p.u = u;
     p.out = out;
-    if (step) {
-        const ArgmaxRowsStep &a = step->a;
-        p.pos = a.pos;
-        p.cells = a.cells;
-        p.mask = a.mask;
-        p.hist = a.hist;
-        p.mask_stride = a.mask_stride;
-        p.hist_stride = a.hist_stride;
-        p.draws_stride = step->draws_stride;
-        p.n_kv = (uint32_t)a.n_kv;
-        p.n_hist = (uint32_t)a.n_hist;
-        p.n_draws = (uint32_t)step->n_draws;
-        p.cell_stride = a.cell_stride;
-    }
+    if (step) p.step = step_args(step->a), p.draws_stride = step->draws_stride, p.n_draws = (uint32_t)step->n_draws;
     return timed_launch("kq::kq_topk_rows", (double)rows * (double)n * 4.0, kq_topk_rows,
                         dim3((unsigned)wgs, (unsigned)rows), dim3(kArgmaxThreads), 0, stream, p);
 }

@@ -751,111 +751,18 @@ def attn_batch_path(n_ctx, n_head, n_head_kv, head_dim, n_kv):
     return int(lib().mi355x_attn_batch_path(ctypes.byref(d)))
 
 
-def _argmax_lib():
+def _lib_with(symbol):
     L = lib()
-    if not hasattr(L, "mi355x_argmax"):
-        raise Mi355xError(f"{LIB_PATH} has no mi355x_argmax (a library built before it)")
+    if not hasattr(L, symbol):
+        raise Mi355xError(f"{LIB_PATH} has no {symbol} (a library built before it)")
     return L
 
 
-def argmax_plan(n):
-    """(workgroups, slice) of mi355x_argmax over n entries (mi355x_argmax_plan: the host's choice,
-    no device): slice s is [s * slice, min(n, (s + 1) * slice)); or the error code."""
-    wgs, slice_ = ctypes.c_int(0), ctypes.c_int64(0)
-    rc = int(_argmax_lib().mi355x_argmax_plan(n, ctypes.byref(wgs), ctypes.byref(slice_)))
-    return (wgs.value, slice_.value) if rc == 0 else rc
-
-
-def argmax_workspace_size(n):
-    """Bytes of mi355x_argmax's workspace for n entries (0: n outside 1 .. 2^24)."""
-    return int(_argmax_lib().mi355x_argmax_workspace_size(n))
-
-
-def argmax(x, out=None, workspace=None, stream=None):
-    """Greedy sampling (mi355x_argmax): the smallest index of the maximum of the non-NaN entries
-    of x, a contiguous f32 cuda vector, as an int32 cuda tensor [1] (no synchronization).
-    workspace: a uint8 cuda tensor of argmax_workspace_size(n) bytes, zeroed once by its owner and
-    reusable call after call on one stream; None: a fresh zeroed one."""
+def _vector_of(name, x):
     torch = _torch()
-    _require_device()
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
-        raise Mi355xError("argmax: x must be a contiguous float32 cuda vector")
-    n = x.numel()
-    out = torch.empty(1, dtype=torch.int32, device=x.device) if out is None else out
-    if not (out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1):
-        raise Mi355xError("argmax: out must be an int32 cuda tensor")
-    if workspace is None:
-        workspace = torch.zeros(argmax_workspace_size(n) or 1, dtype=torch.uint8, device=x.device)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
-    _check(_argmax_lib().mi355x_argmax(x.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                       _stream(stream)), "mi355x_argmax")
-    return out
-
-
-def _argmax_rows_lib():
-    L = lib()
-    if not hasattr(L, "mi355x_argmax_rows"):
-        raise Mi355xError(f"{LIB_PATH} has no mi355x_argmax_rows (a library built before it)")
-    return L
-
-
-def argmax_rows_workspace_size(n, rows):
-    """Bytes of mi355x_argmax_rows' workspace for `rows` rows of n entries (0: n outside 1 .. 2^24
-    or rows outside 1 .. 65535)."""
-    return int(_argmax_rows_lib().mi355x_argmax_rows_workspace_size(n, rows))
-
-
-def argmax_rows(x, out=None, workspace=None, stream=None):
-    """mi355x_argmax_rows: argmax's rule on every row of x, a 2-D f32 cuda tensor [T, n] with unit
-    column stride (the row stride is free: >= n and a multiple of 4 floats), as an int32 cuda
-    tensor [T] (no synchronization). workspace: a uint8 cuda tensor of
-    argmax_rows_workspace_size(n, T) bytes, zeroed once by its owner and reusable call after call
-    on one stream; None: a fresh zeroed one."""
-    torch = _torch()
-    _require_device()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and
-            x.stride(1) == 1):
-        raise Mi355xError("argmax_rows: x must be a 2-D float32 cuda tensor with unit column stride")
-    rows, n = x.shape
-    out = torch.empty(rows, dtype=torch.int32, device=x.device) if out is None else out
-    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= rows):
-        raise Mi355xError("argmax_rows: out must be a contiguous int32 cuda tensor of one entry per row")
-    if workspace is None:
-        workspace = torch.zeros(argmax_rows_workspace_size(n, rows) or 1, dtype=torch.uint8, device=x.device)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
-    stride = x.stride(0) if rows > 1 else (n + 3) & ~3  # (one row: torch's stride of it means nothing)
-    _check(_argmax_rows_lib().mi355x_argmax_rows(x.data_ptr(), n, rows, stride, out.data_ptr(), workspace.data_ptr(),
-                                                 workspace.numel(), _stream(stream)), "mi355x_argmax_rows")
-    return out
-
-
-def _topk_lib():
-    L = lib()
-    if not hasattr(L, "mi355x_topk"):
-        raise Mi355xError(f"{LIB_PATH} has no mi355x_topk (a library built before it)")
-    return L
-
-
-def topk_workspace_size(n, rows=1):
-    """Bytes of the workspace of topk / sample (rows = 1) and topk_rows / sample_rows: 131200 a row
-    whatever n and top_k are (0: n outside 1 .. 2^24 or rows outside 1 .. 65535)."""
-    return int(_topk_lib().mi355x_topk_workspace_size(n, rows))
-
-
-def sampler_params(form, top_k, temp, top_p, min_p):
-    """The SAMPLE nodes' leading op_params."""
-    return [form, top_k, f32_bits(temp), f32_bits(top_p), f32_bits(min_p)]
-
-
-def _topk_workspace(workspace, n, rows, device, stream):
-    torch = _torch()
-    if workspace is None:
-        workspace = torch.zeros(topk_workspace_size(n, rows) or 1, dtype=torch.uint8, device=device)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
-    return workspace
+        raise Mi355xError(f"{name}: x must be a contiguous float32 cuda vector")
+    return x.numel()
 
 
 def _rows_of(name, x):
@@ -867,6 +774,87 @@ def _rows_of(name, x):
     return rows, n, (x.stride(0) if rows > 1 else (n + 3) & ~3)  # (one row: torch's stride of it means nothing)
 
 
+def _int32_out(name, out, device, rows=None):
+    """out, or a new one: [1] (rows None) or one entry per row."""
+    torch = _torch()
+    out = torch.empty(rows or 1, dtype=torch.int32, device=device) if out is None else out
+    if rows is None and not (out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1):
+        raise Mi355xError(f"{name}: out must be an int32 cuda tensor")
+    if rows is not None and not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= rows):
+        raise Mi355xError(f"{name}: out must be a contiguous int32 cuda tensor of one entry per row")
+    return out
+
+
+def _zeroed_workspace(workspace, nbytes, device, stream):
+    """workspace, or a fresh zeroed one of nbytes."""
+    torch = _torch()
+    if workspace is None:
+        workspace = torch.zeros(nbytes or 1, dtype=torch.uint8, device=device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()  # zeroed on torch's stream, used on `stream`
+    return workspace
+
+
+def argmax_plan(n):
+    """(workgroups, slice) of mi355x_argmax over n entries (mi355x_argmax_plan: the host's choice,
+    no device): slice s is [s * slice, min(n, (s + 1) * slice)); or the error code."""
+    wgs, slice_ = ctypes.c_int(0), ctypes.c_int64(0)
+    rc = int(_lib_with("mi355x_argmax").mi355x_argmax_plan(n, ctypes.byref(wgs), ctypes.byref(slice_)))
+    return (wgs.value, slice_.value) if rc == 0 else rc
+
+
+def argmax_workspace_size(n):
+    """Bytes of mi355x_argmax's workspace for n entries (0: n outside 1 .. 2^24)."""
+    return int(_lib_with("mi355x_argmax").mi355x_argmax_workspace_size(n))
+
+
+def argmax(x, out=None, workspace=None, stream=None):
+    """Greedy sampling (mi355x_argmax): the smallest index of the maximum of the non-NaN entries
+    of x, a contiguous f32 cuda vector, as an int32 cuda tensor [1] (no synchronization).
+    workspace: a uint8 cuda tensor of argmax_workspace_size(n) bytes, zeroed once by its owner and
+    reusable call after call on one stream; None: a fresh zeroed one."""
+    _require_device()
+    n = _vector_of("argmax", x)
+    out = _int32_out("argmax", out, x.device)
+    workspace = _zeroed_workspace(workspace, argmax_workspace_size(n), x.device, stream)
+    _check(_lib_with("mi355x_argmax").mi355x_argmax(x.data_ptr(), n, out.data_ptr(), workspace.data_ptr(),
+                                                    workspace.numel(), _stream(stream)), "mi355x_argmax")
+    return out
+
+
+def argmax_rows_workspace_size(n, rows):
+    """Bytes of mi355x_argmax_rows' workspace for `rows` rows of n entries (0: n outside 1 .. 2^24
+    or rows outside 1 .. 65535)."""
+    return int(_lib_with("mi355x_argmax_rows").mi355x_argmax_rows_workspace_size(n, rows))
+
+
+def argmax_rows(x, out=None, workspace=None, stream=None):
+    """mi355x_argmax_rows: argmax's rule on every row of x, a 2-D f32 cuda tensor [T, n] with unit
+    column stride (the row stride is free: >= n and a multiple of 4 floats), as an int32 cuda
+    tensor [T] (no synchronization). workspace: a uint8 cuda tensor of
+    argmax_rows_workspace_size(n, T) bytes, zeroed once by its owner and reusable call after call
+    on one stream; None: a fresh zeroed one."""
+    _require_device()
+    rows, n, stride = _rows_of("argmax_rows", x)
+    out = _int32_out("argmax_rows", out, x.device, rows)
+    workspace = _zeroed_workspace(workspace, argmax_rows_workspace_size(n, rows), x.device, stream)
+    _check(_lib_with("mi355x_argmax_rows").mi355x_argmax_rows(x.data_ptr(), n, rows, stride, out.data_ptr(),
+                                                              workspace.data_ptr(), workspace.numel(), _stream(stream)),
+           "mi355x_argmax_rows")
+    return out
+
+
+def topk_workspace_size(n, rows=1):
+    """Bytes of the workspace of topk / sample (rows = 1) and topk_rows / sample_rows: 131200 a row
+    whatever n and top_k are (0: n outside 1 .. 2^24 or rows outside 1 .. 65535)."""
+    return int(_lib_with("mi355x_topk").mi355x_topk_workspace_size(n, rows))
+
+
+def sampler_params(form, top_k, temp, top_p, min_p):
+    """The SAMPLE nodes' leading op_params."""
+    return [form, top_k, f32_bits(temp), f32_bits(top_p), f32_bits(min_p)]
+
+
 def topk(x, top_k, workspace=None, stream=None):
     """mi355x_topk: the top_k (1 .. 64) largest non-NaN entries of x, a contiguous f32 cuda vector,
     under argmax's order, sorted: (idx int32 [top_k], val f32 [top_k]) cuda tensors, places past
@@ -875,14 +863,12 @@ def topk(x, top_k, workspace=None, stream=None):
     stream, whatever n and top_k are; None: a fresh zeroed one."""
     torch = _torch()
     _require_device()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
-        raise Mi355xError("topk: x must be a contiguous float32 cuda vector")
-    n, k = x.numel(), max(int(top_k), 1)
+    n, k = _vector_of("topk", x), max(int(top_k), 1)
     idx = torch.empty(k, dtype=torch.int32, device=x.device)
     val = torch.empty(k, dtype=torch.float32, device=x.device)
-    workspace = _topk_workspace(workspace, n, 1, x.device, stream)
-    _check(_topk_lib().mi355x_topk(x.data_ptr(), n, int(top_k), idx.data_ptr(), val.data_ptr(), workspace.data_ptr(),
-                                   workspace.numel(), _stream(stream)), "mi355x_topk")
+    workspace = _zeroed_workspace(workspace, topk_workspace_size(n), x.device, stream)
+    _check(_lib_with("mi355x_topk").mi355x_topk(x.data_ptr(), n, int(top_k), idx.data_ptr(), val.data_ptr(),
+                                                workspace.data_ptr(), workspace.numel(), _stream(stream)), "mi355x_topk")
     return idx, val
 
 
@@ -896,9 +882,10 @@ def topk_rows(x, top_k, workspace=None, stream=None):
     k = max(int(top_k), 1)
     idx = torch.empty((rows, k), dtype=torch.int32, device=x.device)
     val = torch.empty((rows, k), dtype=torch.float32, device=x.device)
-    workspace = _topk_workspace(workspace, n, rows, x.device, stream)
-    _check(_topk_lib().mi355x_topk_rows(x.data_ptr(), n, rows, stride, int(top_k), idx.data_ptr(), val.data_ptr(),
-                                        workspace.data_ptr(), workspace.numel(), _stream(stream)), "mi355x_topk_rows")
+    workspace = _zeroed_workspace(workspace, topk_workspace_size(n, rows), x.device, stream)
+    _check(_lib_with("mi355x_topk").mi355x_topk_rows(x.data_ptr(), n, rows, stride, int(top_k), idx.data_ptr(),
+                                                     val.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                     _stream(stream)), "mi355x_topk_rows")
     return idx, val
 
 
@@ -909,18 +896,15 @@ def sample(x, u, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, out=None, workspace
     tensor whose first entry is the draw, meant to lie in [0, 1). workspace: as topk's."""
     torch = _torch()
     _require_device()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
-        raise Mi355xError("sample: x must be a contiguous float32 cuda vector")
+    n = _vector_of("sample", x)
     if not (u.is_cuda and u.dtype == torch.float32 and u.numel() >= 1):
         raise Mi355xError("sample: u must be a float32 cuda tensor")
-    n = x.numel()
-    out = torch.empty(1, dtype=torch.int32, device=x.device) if out is None else out
-    if not (out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1):
-        raise Mi355xError("sample: out must be an int32 cuda tensor")
-    workspace = _topk_workspace(workspace, n, 1, x.device, stream)
+    out = _int32_out("sample", out, x.device)
+    workspace = _zeroed_workspace(workspace, topk_workspace_size(n), x.device, stream)
     sp = SamplerDesc(int(top_k), float(temp), float(top_p), float(min_p))
-    _check(_topk_lib().mi355x_sample(x.data_ptr(), n, ctypes.byref(sp), u.data_ptr(), out.data_ptr(),
-                                     workspace.data_ptr(), workspace.numel(), _stream(stream)), "mi355x_sample")
+    _check(_lib_with("mi355x_topk").mi355x_sample(x.data_ptr(), n, ctypes.byref(sp), u.data_ptr(), out.data_ptr(),
+                                                  workspace.data_ptr(), workspace.numel(), _stream(stream)),
+           "mi355x_sample")
     return out
 
 
@@ -932,14 +916,12 @@ def sample_rows(x, u, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, out=None, work
     rows, n, stride = _rows_of("sample_rows", x)
     if not (u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() >= rows):
         raise Mi355xError("sample_rows: u must be a contiguous float32 cuda tensor of one entry per row")
-    out = torch.empty(rows, dtype=torch.int32, device=x.device) if out is None else out
-    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= rows):
-        raise Mi355xError("sample_rows: out must be a contiguous int32 cuda tensor of one entry per row")
-    workspace = _topk_workspace(workspace, n, rows, x.device, stream)
+    out = _int32_out("sample_rows", out, x.device, rows)
+    workspace = _zeroed_workspace(workspace, topk_workspace_size(n, rows), x.device, stream)
     sp = SamplerDesc(int(top_k), float(temp), float(top_p), float(min_p))
-    _check(_topk_lib().mi355x_sample_rows(x.data_ptr(), n, rows, stride, ctypes.byref(sp), u.data_ptr(), out.data_ptr(),
-                                          workspace.data_ptr(), workspace.numel(), _stream(stream)),
-           "mi355x_sample_rows")
+    _check(_lib_with("mi355x_topk").mi355x_sample_rows(x.data_ptr(), n, rows, stride, ctypes.byref(sp), u.data_ptr(),
+                                                       out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                       _stream(stream)), "mi355x_sample_rows")
     return out
 
 

@@ -238,10 +238,11 @@ def test_plain_node_replays(dev):
     b.close()
 
 
-def ref_step(x, tok, pos, cells, mask, hist, cell_stride, n_kv, n_hist):
-    """The step-inputs form restated (in place); mask and hist as [T, row] arrays, mask as uint32 bits."""
+def ref_step(x, tok, pos, cells, mask, hist, cell_stride, n_kv, n_hist, tokens=None):
+    """The step-inputs form restated (in place); mask and hist as [T, row] arrays, mask as uint32 bits.
+    tokens: the rows' tokens where they are not the argmax (tests/test_gpu_sample.py: the sampled ones)."""
     for i in range(x.shape[0]):
-        t = ref_rows(x[i:i + 1])[0]
+        t = ref_rows(x[i:i + 1])[0] if tokens is None else tokens[i]
         p = np.int32((int(pos[i]) + 1 + 2 ** 31) % 2 ** 32 - 2 ** 31)
         c = np.int32((int(cells[i]) + cell_stride + 2 ** 31) % 2 ** 32 - 2 ** 31)
         tok[i], pos[i], cells[i] = t, p, c

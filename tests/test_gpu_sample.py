@@ -285,3 +285,91 @@ def test_step_inputs_node(dev, use_graph):
     got, hs = step(-1)  # -1 + 1 = 0: entry 0 of each
     assert got[0] == want[0] and got[1] == 0 and (got[2:] == table_h[0].view(np.int32)).all() and hs[0] == want[0]
     b.close()
+
+
+B_T, B_N, B_NKV, B_NHIST, B_HROW, B_NDRAWS, B_DROW = 5, 3076, 64, 40, 44, 20, 24
+B_KW = dict(top_k=40, top_p=1.0, min_p=0.0, temp=4.0)
+B_POS = [5, 0, B_NDRAWS - 1, B_NHIST - 1, -5]
+PAD_DRAW = F(0.999)  # the draws' padding: a kernel that read it would not answer c_0
+
+
+def batch_step_case():
+    """The inputs of test_step_inputs_batch_node and, per run, the tokens of the reference: row i's
+    is ref_sample with the draw draws[i][pos[i] + 1], 0.0 where the table has no such entry."""
+    if not hasattr(batch_step_case, "made"):
+        h = (np.random.default_rng(23).standard_normal((B_T, B_N)) * 4).astype(np.float32)
+        draws = np.full((B_T, B_DROW), PAD_DRAW, np.float32)
+        for i in range(B_T):
+            draws[i, :B_NDRAWS] = R.draws([24, i], B_NDRAWS)
+        tokens = []
+        for run_no in range(2):
+            new = [p + 1 + run_no for p in B_POS]
+            tokens.append([R.ref_sample(h[i], draws[i, p] if 0 <= p < B_NDRAWS else F(0.0), **B_KW)
+                           for i, p in enumerate(new)])
+        batch_step_case.made = h, draws, tokens
+    return batch_step_case.made
+
+
+@pytest.mark.parametrize("use_graph", [True, False], ids=["hipgraph", "eager"])
+@pytest.mark.parametrize("cell_stride", [1, 3])
+def test_step_inputs_batch_node(dev, cell_stride, use_graph):
+    """The step-inputs SAMPLE_BATCH node on a hand-made input block (tokens | pos | cells | mask, the
+    decoder's layout) with sentinels, a history with padded rows and a draws table with padded rows,
+    as tests/test_gpu_argmax_rows.py::test_step_inputs_node drives ARGMAX_BATCH's: two runs, the
+    second from the state the first left. Every word of the block and of the history equals
+    ref_step's rule on the tokens of ref_sample. Rows 0 and 1 advance inside all their arrays; row
+    2's new cell is n_kv (no mask word) and its new position n_draws (the draw is 0.0, the token c_0,
+    the history and the cell are written); row 3's new position is n_hist (no history entry); row 4
+    starts from a negative position and cell."""
+    import torch
+    import ggml_mi355x as g
+    from tests.test_gpu_argmax_rows import SENT, ref_step
+    T, n, n_kv, n_hist = B_T, B_N, B_NKV, B_NHIST
+    h, draws_h, tokens = batch_step_case()
+    c0 = [R.ref_argmax(h[i]) for i in range(T)]
+    # of the reference itself: draws decide (else the greedy tail would pass), and row 2 shows a read of the padding
+    for run_no in range(2):
+        assert sum(tokens[run_no][i] != c0[i] for i in range(T)) >= 2 and tokens[run_no][2] == c0[2]
+    assert R.ref_sample(h[2], PAD_DRAW, **B_KW) != c0[2]
+    b = g.Backend()
+    x = torch.from_numpy(h).to(dev)
+    draws = torch.from_numpy(draws_h).to(dev)
+    inp_h = np.full(3 * T + T * n_kv, SENT, np.int32)
+    inp_h[T:2 * T] = B_POS
+    inp_h[2 * T:3 * T] = [9, 0, n_kv - cell_stride, 20, -1 - 2 * cell_stride]
+    m = inp_h[3 * T:].view(np.float32).reshape(T, n_kv)
+    m[:] = -np.inf
+    m[:, ::5] = np.random.default_rng(25).standard_normal((T, len(range(0, n_kv, 5)))).astype(np.float32)
+    hist_h = np.full((T, B_HROW), SENT, np.int32)
+    inp = torch.from_numpy(inp_h.copy()).to(dev)
+    hist = torch.from_numpy(hist_h.copy()).to(dev)
+    srcs = [g.make_tensor(g.TYPE_F32, n, T, x.data_ptr()),
+            g.make_tensor(g.TYPE_I32, T, 1, inp[T:2 * T].data_ptr()),
+            g.make_tensor(g.TYPE_I32, T, 1, inp[2 * T:3 * T].data_ptr()),
+            g.make_tensor(g.TYPE_F32, n_kv, T, inp[3 * T:].data_ptr()),
+            g.make_tensor(g.TYPE_I32, n_hist, T, hist.data_ptr(), row_stride=4 * B_HROW),
+            g.make_tensor(g.TYPE_F32, B_NDRAWS, T, draws.data_ptr(), row_stride=4 * B_DROW)]
+    node = g.make_tensor(g.TYPE_I32, T, 1, inp.data_ptr(), op=g.OP_SAMPLE_BATCH, srcs=srcs,
+                         op_params=g.sampler_params(g.SAMPLE_STEP_INPUTS, 40, 4.0, 1.0, 0.0) + [cell_stride, n_kv],
+                         flags=g.FLAG_OUTPUT)
+    assert g.supports_op(node)
+    torch.cuda.synchronize()
+    ref_inp, ref_hist = inp_h.copy(), hist_h.copy()
+    for run_no in range(2):
+        assert b.graph_compute([node], use_graph=use_graph) == 0
+        b.synchronize()
+        ref_step(h, ref_inp[:T], ref_inp[T:2 * T], ref_inp[2 * T:3 * T], ref_inp[3 * T:].view(np.uint32).reshape(T, n_kv),
+                 ref_hist, cell_stride, n_kv, n_hist, tokens=tokens[run_no])
+        got, hs = inp.cpu().numpy(), hist.cpu().numpy()
+        # every word: tokens, pos, cells, the mask bit for bit, the history with its padding
+        assert (got.view(np.uint32) == ref_inp.view(np.uint32)).all(), (run_no, np.nonzero(got != ref_inp)[0][:8])
+        assert (hs == ref_hist).all(), run_no
+    # what the restatement did with the rows built for them
+    mask0, mask1 = inp_h[3 * T:].reshape(T, n_kv), ref_inp[3 * T:].reshape(T, n_kv)
+    assert [int((mask0[i] != mask1[i]).sum()) for i in range(T)] == [2, 2, 0, 2, 0]
+    assert ref_inp[2 * T + 2] == n_kv + cell_stride and ref_inp[2 * T + 4] == -1   # cells n_kv ..: no mask word; negative: none
+    assert (ref_hist[2, B_NDRAWS:B_NDRAWS + 2] == c0[2]).all()                     # positions n_draws ..: c_0, filed
+    assert ref_inp[T + 3] == n_hist + 1 and (ref_hist[3] == SENT).all()            # positions n_hist ..: no entry
+    assert ref_inp[T + 4] == -3 and (ref_hist[4] == SENT).all()                    # negative positions: no entry
+    assert (ref_hist[:, n_hist:] == SENT).all()
+    b.close()
