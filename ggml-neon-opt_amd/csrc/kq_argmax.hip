@@ -40,13 +40,6 @@ namespace kq {
 namespace {
 
 constexpr int kArgmaxSlice = 1024;  // entries per workgroup up to 256 workgroups (ARGMAX_SLICE: A/B)
-// kq_argmax_rows: a row's part of the workspace, the counter's line and the words of the largest
-// split. The same for every n, so every counter keeps its place whatever a workspace served
-// before (a place that depended on n would land on another call's leftover words), and a whole
-// number of lines, so no row's words share a line with a counter. Row 0's counter is kq_argmax's
-// and the next is past kq_argmax's words: the backend's one buffer serves both kernels.
-constexpr size_t kArgmaxRowBytes = kArgmaxCounterBytes + 8 * (size_t)kArgmaxMaxWgs;
-static_assert(kArgmaxRowBytes % kArgmaxCounterBytes == 0, "a row's part is a whole number of lines");
 
 struct ArgmaxArgs {
     const float *x;
@@ -164,6 +157,7 @@ struct ArgmaxRowsArgs {
     uint8_t *ws;         // workspace, per row (kArgmaxRowBytes): the counter's line, then the row's words
     int32_t *out;        // [T]: the rows' indices (step form: the sequences' next tokens)
     RowsStepArgs step;
+    int64_t out_stride;  // plain form: entries of out between two rows' indices
 };
 
 __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax_rows(const ArgmaxRowsArgs p) {
@@ -176,7 +170,7 @@ __global__ void __launch_bounds__(kArgmaxThreads) kq_argmax_rows(const ArgmaxRow
     if (!hand_off(slice_word(p.x + row * p.row_stride, lo, hi), part, cnt, (int)blockIdx.x, p.wgs, p.n, &token)) return;
     if (threadIdx.x != 0) return;
     if (!p.step.pos) {
-        p.out[row] = token;
+        p.out[row * p.out_stride] = token;
         return;
     }
     uint32_t np, nc;
@@ -229,10 +223,11 @@ size_t argmax_rows_workspace(int64_t n, int64_t rows) {
 }
 
 int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
-                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream) {
+                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream, int64_t out_stride) {
     int wgs = 0;
     int64_t slice = 0;
-    if (!out || !input_ok(x, n, rows, row_stride, &wgs, &slice) || (step && !step_ok(*step))) return MI355X_E_INVAL;
+    if (!out || out_stride < 1 || !input_ok(x, n, rows, row_stride, &wgs, &slice) || (step && !step_ok(*step)))
+        return MI355X_E_INVAL;
     if (const int rc = workspace_status(ws, ws_size, argmax_rows_workspace(n, rows))) return rc;
     ArgmaxRowsArgs p;
     memset(&p, 0, sizeof(p));
@@ -243,6 +238,7 @@ int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
     p.wgs = wgs;
     p.ws = (uint8_t *)ws;
     p.out = out;
+    p.out_stride = out_stride;
     if (step) p.step = step_args(*step);
     return timed_launch("kq::kq_argmax_rows", (double)rows * (double)n * 4.0, kq_argmax_rows,
                         dim3((unsigned)wgs, (unsigned)rows), dim3(kArgmaxThreads), 0, stream, p);

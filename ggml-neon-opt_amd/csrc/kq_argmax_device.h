@@ -14,6 +14,14 @@ namespace kq {
 constexpr int kArgmaxThreads = 256;
 constexpr int kArgmaxMaxWgs = 256;  // the last arriver reads one word per thread
 constexpr size_t kArgmaxCounterBytes = 128;  // the counter on a line of its own, then the words
+// kq_argmax_rows, kq_logsum_rows: a row's part of the workspace, the counter's line and the words
+// of the largest split. The same for every n, so every counter keeps its place whatever a
+// workspace served before (a place that depended on n would land on another call's leftover
+// words), and a whole number of lines, so no row's words share a line with a counter. Row 0's
+// counter is kq_argmax's and the next is past kq_argmax's words: the backend's one buffer serves
+// these kernels.
+constexpr size_t kArgmaxRowBytes = kArgmaxCounterBytes + 8 * (size_t)kArgmaxMaxWgs;
+static_assert(kArgmaxRowBytes % kArgmaxCounterBytes == 0, "a row's part is a whole number of lines");
 
 __device__ __forceinline__ uint32_t ord_key(uint32_t b) {
     if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;  // NaN: below -inf's key (0x007fffff)

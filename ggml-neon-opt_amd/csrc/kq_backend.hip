@@ -54,7 +54,7 @@ struct mi355x_backend {
     void *fx = nullptr;      // its arrival counters (zeroed at allocation) and records
     size_t fx_size = 0;
     int fx_nsb = 0;          // the superblock count the counters' rounds are aligned to
-    void *am = nullptr;      // the ARGMAX / ARGMAX_BATCH nodes' arrival counters and partials (kq_argmax.hip), zeroed at
+    void *am = nullptr;      // the ARGMAX / ARGMAX_BATCH / LOGPROB_BATCH nodes' arrival counters and partials, zeroed at
     size_t am_size = 0;      // allocation; every launch leaves them ready for the next
     void *sm = nullptr;      // the SAMPLE / SAMPLE_BATCH nodes' counters and words (kq_sample.hip), as am
     size_t sm_size = 0;
@@ -381,6 +381,12 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             return kq::launch_topk_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0], 0, nullptr, nullptr, &sp,
                                         (const float *)draws->data, (int32_t *)t->data, &step, b->sm, b->sm_size, st);
         }
+        case MI355X_OP_LOGPROB_BATCH: {  // two launches: kq_argmax_rows, kq_logsum_rows
+            const mi355x_tensor *x = t->src[0];
+            return kq::launch_logprob_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0],
+                                           (const int32_t *)t->src[1]->data, (mi355x_logprob *)t->data, b->am, b->am_size,
+                                           st);
+        }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(t, d);
@@ -611,7 +617,8 @@ int ensure_attn_oproj_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, con
     return MI355X_OK;
 }
 
-// the ARGMAX and ARGMAX_BATCH nodes' counters and partials: sized for the largest, zeroed when (re)allocated.
+// the ARGMAX, ARGMAX_BATCH and LOGPROB_BATCH nodes' counters and partials: sized for the largest, zeroed when
+// (re)allocated.
 // The nodes of a graph run one after the other on the backend stream, so they share it.
 int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
     size_t need = 0;
@@ -619,6 +626,8 @@ int ensure_argmax_buffer(mi355x_backend *b, mi355x_tensor *const *nodes, int n_n
         if (nodes[i]->op == MI355X_OP_ARGMAX) need = std::max(need, kq::argmax_workspace(nodes[i]->src[0]->ne[0]));
         else if (nodes[i]->op == MI355X_OP_ARGMAX_BATCH)
             need = std::max(need, kq::argmax_rows_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
+        else if (nodes[i]->op == MI355X_OP_LOGPROB_BATCH)
+            need = std::max(need, kq::logprob_workspace(nodes[i]->src[0]->ne[0], nodes[i]->src[0]->ne[1]));
     return grow_buffer(b, &b->am, &b->am_size, need, true);
 }
 

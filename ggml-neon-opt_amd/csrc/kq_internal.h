@@ -298,7 +298,8 @@ struct ArgmaxRowsStep {
 };
 size_t argmax_rows_workspace(int64_t n, int64_t rows);
 int launch_argmax_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int32_t *out,
-                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream);
+                       const ArgmaxRowsStep *step, void *ws, size_t ws_size, hipStream_t stream,
+                       int64_t out_stride = 1);  // plain form: row i's index goes to out[i * out_stride]
 // What the launchers of kq_argmax.hip and kq_sample.hip check first. Their statuses come in this
 // order: E_INVAL (input_ok, the launcher's own outputs, step_ok), then workspace_status'
 // E_WORKSPACE, then its E_NODEVICE.
@@ -342,6 +343,15 @@ int launch_topk(const float *x, int64_t n, int top_k, int32_t *idx, float *val, 
 int launch_topk_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, int top_k, int32_t *idx, float *val,
                      const mi355x_sampler *sp, const float *u, int32_t *out, const SampleRowsStep *step, void *ws,
                      size_t ws_size, hipStream_t stream);
+
+// ---------------------------------------------------------------- kq_logprob.hip
+// The record of log softmax(x)[target] for each row of an f32 matrix (include/ggml_mi355x.h, the
+// rule): launch_argmax_rows, then kq_logsum_rows, both on the one workspace of
+// argmax_rows_workspace's layout (logprob_workspace: 0 outside 1 <= n <= 262144, 1 <= rows <= 65535).
+constexpr int64_t kLogprobMaxN = MI355X_LOGPROB_MAX_N;
+size_t logprob_workspace(int64_t n, int64_t rows);
+int launch_logprob_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, const int32_t *targets,
+                        mi355x_logprob *out, void *ws, size_t ws_size, hipStream_t stream);
 
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from

@@ -723,6 +723,20 @@ bool supports_op(const mi355x_tensor *op) {
             return u->ne[0] >= 1 && u->ne[0] <= 0x7fffffff && u->ne[1] == T && nelem(u) == u->ne[0] * T &&
                    (T == 1 || (u->nb[1] % 4 == 0 && u->nb[1] >= (size_t)u->ne[0] * 4));
         }
+        case MI355X_OP_LOGPROB_BATCH: {
+            // f32 [n, T] of mi355x_logprob_rows' sizes, rows packed and 16-B aligned, and I32 targets
+            // [T] -> I32 [6, T], 8-B aligned: the rows' records
+            const mi355x_tensor *x = op->src[0], *tg = op->src[1];
+            if (!x || x->type != MI355X_TYPE_F32 || !x->data || ((uintptr_t)x->data & 15u) || x->nb[0] != 4) return false;
+            const int64_t n = x->ne[0], T = x->ne[1];
+            if (n < 1 || n > kLogprobMaxN || n % 4 || T < 1 || T > kArgmaxMaxRows || nelem(x) != n * T) return false;
+            if (x->nb[1] != (size_t)n * 4) return false;
+            if (!tg || tg->type != MI355X_TYPE_I32 || !tg->data || ((uintptr_t)tg->data & 3u) || tg->nb[0] != 4 ||
+                tg->ne[0] != T || nelem(tg) != T)
+                return false;
+            return op->type == MI355X_TYPE_I32 && op->data && !((uintptr_t)op->data & 7u) && op->nb[0] == 4 &&
+                   op->ne[0] == 6 && op->ne[1] == T && nelem(op) == 6 * T && op->nb[1] == sizeof(mi355x_logprob);
+        }
         default:
             return false;
     }

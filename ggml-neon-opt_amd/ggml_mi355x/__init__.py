@@ -34,6 +34,8 @@ OP_ARGMAX_BATCH = 13  # the argmax of every row; op_params[0]: ARGMAX_PLAIN / AR
 OP_SAMPLE, OP_SAMPLE_BATCH = 14, 15
 SAMPLE_PLAIN, SAMPLE_STEP_INPUTS = 0, 1
 SAMPLE_MAX_K = 64
+OP_LOGPROB_BATCH = 16  # src0 the logits [n, T], src1 I32 targets [T] -> I32 [6, T]: the rows' records (LOGPROB_DTYPE)
+LOGPROB_MAX_N = 262144
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -81,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_argmax_plan", "mi355x_argmax_workspace_size", "mi355x_argmax",
     "mi355x_argmax_rows_workspace_size", "mi355x_argmax_rows",
     "mi355x_topk_workspace_size", "mi355x_topk", "mi355x_topk_rows", "mi355x_sample", "mi355x_sample_rows",
+    "mi355x_logprob_workspace_size", "mi355x_logprob_rows",
 )
 
 
@@ -288,6 +291,11 @@ def lib():
         L.mi355x_sample.restype = i32
         L.mi355x_sample_rows.argtypes = [vp, i64, i64, i64, ctypes.POINTER(SamplerDesc), vp, vp, vp, sz, vp]
         L.mi355x_sample_rows.restype = i32
+    if hasattr(L, "mi355x_logprob_rows"):
+        L.mi355x_logprob_workspace_size.argtypes = [i64, i64]
+        L.mi355x_logprob_workspace_size.restype = sz
+        L.mi355x_logprob_rows.argtypes = [vp, i64, i64, i64, vp, vp, vp, sz, vp]
+        L.mi355x_logprob_rows.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -923,6 +931,59 @@ def sample_rows(x, u, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, out=None, work
                                                        out.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                                        _stream(stream)), "mi355x_sample_rows")
     return out
+
+
+def logprob_dtype():
+    """struct mi355x_logprob as a numpy structured dtype (24 bytes)."""
+    import numpy as np
+    return np.dtype([("max", "<f4"), ("x_target", "<f4"), ("argmax", "<i4"), ("pad", "<i4"), ("sum", "<f8")])
+
+
+def logprob_workspace_size(n, rows):
+    """Bytes of mi355x_logprob_rows' workspace for `rows` rows of n entries: argmax_rows' 2176 a row
+    (0: n outside 1 .. 262144 or rows outside 1 .. 65535)."""
+    return int(_lib_with("mi355x_logprob_rows").mi355x_logprob_workspace_size(n, rows))
+
+
+def logprob_rows(x, targets, workspace=None, stream=None):
+    """mi355x_logprob_rows: for every row of x, a 2-D f32 cuda tensor [T, n] of logits with unit
+    column stride (the row stride >= n and a multiple of 4 floats), and its target index (targets:
+    T ints, or an int32 cuda tensor [T]) the record of log softmax(x)[target]: a structured numpy
+    array [T] of logprob_dtype() (max, x_target, argmax, pad, sum; the exact rule is in
+    include/ggml_mi355x.h), after one synchronization; logprob_value(records) finishes it.
+    workspace: a uint8 cuda tensor of logprob_workspace_size(n, T) bytes, zeroed once by its owner
+    and reusable call after call on one stream, argmax_rows calls included; None: a fresh zeroed one."""
+    import numpy as np
+    torch = _torch()
+    _require_device()
+    rows, n, stride = _rows_of("logprob_rows", x)
+    if not torch.is_tensor(targets):
+        targets = torch.from_numpy(np.ascontiguousarray(targets, dtype=np.int32)).to(x.device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()  # copied on torch's stream, read on `stream`
+    if not (targets.is_cuda and targets.dtype == torch.int32 and targets.is_contiguous() and targets.numel() == rows):
+        raise Mi355xError("logprob_rows: targets must be one int32 per row")
+    out = torch.empty(rows * 24, dtype=torch.uint8, device=x.device)
+    workspace = _zeroed_workspace(workspace, logprob_workspace_size(n, rows), x.device, stream)
+    _check(_lib_with("mi355x_logprob_rows").mi355x_logprob_rows(x.data_ptr(), n, rows, stride, targets.data_ptr(),
+                                                                out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                                _stream(stream)), "mi355x_logprob_rows")
+    if stream is not None:
+        torch.cuda.synchronize()
+    return out.cpu().numpy().view(logprob_dtype()).copy()
+
+
+def logprob_value(records):
+    """mi355x_logprob_value over records of logprob_dtype(): float64 log-probabilities,
+    x_target - max - log(sum), the logarithm taken on the host (a target outside its row: NaN)."""
+    import math
+    import numpy as np
+    r = np.asarray(records)
+    # libm's log, one value at a time, as the header's inline function takes it
+    logs = np.array([math.log(s) if s > 0 else (-math.inf if s == 0 else math.nan) for s in r["sum"].ravel().tolist()],
+                    dtype=np.float64).reshape(r.shape)
+    with np.errstate(all="ignore"):
+        return r["x_target"].astype(np.float64) - r["max"].astype(np.float64) - logs
 
 
 def block_partials(type_, w, K, q8_row, stream=None):

@@ -27,15 +27,19 @@ layer body and the one head below (LlamaDecoder._layers, ._head) over a _Graph:
   generate,       the token graph / the batch graph plus one ARGMAX / ARGMAX_BATCH node
   generate_batch  that stages the next step's inputs on the device; with a Sampler that last
                   node is a SAMPLE / SAMPLE_BATCH, which reads its draws from a device table
+  logprobs,       _prompt_graph(n_tok, all_rows=True): the prompt's layers with no row selection,
+  perplexity      the head over all n_tok rows and one LOGPROB_BATCH node on the logits and the
+                  targets: 24 bytes a token come back, not a row of the vocabulary
 """
 from __future__ import annotations
 
 import ctypes
 
-from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE, OP_ARGMAX,
-               OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_MUL, OP_MUL_MAT, OP_RMS_NORM,
-               OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32,
-               TYPE_I32, Backend, Mi355xError, f32_bits, make_tensor, rope_table, sampler_params)
+from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, LOGPROB_MAX_N, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE,
+               OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_LOGPROB_BATCH, OP_MUL,
+               OP_MUL_MAT, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS,
+               TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, logprob_dtype, logprob_value, make_tensor,
+               rope_table, sampler_params)
 
 
 def torch_tensor(values):
@@ -58,6 +62,15 @@ LLAMA3_8B = hparams(4096, 32, 32, 8, 14336, 128256, eps=1e-5, freq_base=500000.0
 def _check(rc, what):
     if rc:
         raise Mi355xError(f"{what} failed ({rc})")
+
+
+def ppl_of(nll, count):
+    """exp(nll / count), the perplexity of `count` scored tokens (inf where the double overflows)."""
+    import math
+    try:
+        return math.exp(nll / count)
+    except OverflowError:
+        return math.inf
 
 
 def _node_array(nodes):
@@ -295,21 +308,45 @@ class LlamaDecoder:
         return self._gather(g, split, lg, lb, self.hp["n_vocab"] // split.world, flags=FLAG_OUTPUT)[1]
 
     # ------------------------------------------------------------ prompt processing
-    def _prompt_graph(self, n_tok: int):
+    def _prompt_graph(self, n_tok: int, all_rows: bool = False):
         """Node list of a prompt batch of n_tok tokens (llm_build_llama over a ubatch,
         ggml's batched non-flash attention; llama-bench pp): the same weights, caches and
         rope table as the decode token. MUL_MATs take ne11 = n_tok columns (the int8-MFMA
         GEMMs), RMS_NORM/MUL/ADD/SWIGLU run on [n, n_tok], the attention node writes the
         batch's cells then runs every query causally, and only the last token's row goes
         through the output norm and head (llama.cpp computes the logits of the last token
-        of a prompt)."""
+        of a prompt).
+        all_rows: the graph of logprobs, a cache entry of its own: the same layers with no row
+        selection, the head over all n_tok rows and a LOGPROB_BATCH node (flagged output) on the
+        logits and one more input section, the rows' targets: token ids | positions | targets."""
         import torch
-        cached = self._prompts.get(n_tok)
+        cached = self._prompts.get(("all_rows", n_tok) if all_rows else n_tok)
         if cached is not None:
             return cached
         if self.split is not None:
             raise Mi355xError("prompt processing runs on one GPU (no row split)")
         g = _Graph(self.hp, self.w)
+        if all_rows:
+            inp = torch.zeros(3 * n_tok, dtype=torch.int32, device=g.dev)
+            tok = g.leaf(inp[:n_tok], TYPE_I32, n_tok)
+            pos = g.leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
+            targets = g.leaf(inp[2 * n_tok:], TYPE_I32, n_tok)
+            tab = g.leaf(self.table, TYPE_F32, self.hp["head_dim"], self.n_ctx)
+            x, hidden = self._layers(g, tok, pos, tab)
+            logits = self._head(g, x)
+            rec = torch.zeros(6 * n_tok, dtype=torch.int32, device=g.dev)  # [n_tok] struct mi355x_logprob
+            lp = make_tensor(TYPE_I32, 6, n_tok, rec.data_ptr(), op=OP_LOGPROB_BATCH, srcs=[g.nodes[-1], targets],
+                             flags=FLAG_OUTPUT)
+            g.tensors.append(lp)
+            g.nodes.append(lp)
+            on_dev = self.b is not None
+            pg = dict(graph=g, inp=inp, nodes=g.nodes, logits=logits.view(n_tok, self.hp["n_vocab"]), hidden=hidden,
+                      rec=rec, arr=g.arr(), host=torch.zeros(3 * n_tok, dtype=torch.int32).pin_memory() if on_dev else None,
+                      rec_host=torch.zeros(6 * n_tok, dtype=torch.int32).pin_memory() if on_dev else None)
+            self._prompts[("all_rows", n_tok)] = pg
+            if on_dev:
+                torch.cuda.synchronize()  # zeroed buffers (torch's stream) before the backend stream runs
+            return pg
         inp = torch.zeros(2 * n_tok + 1, dtype=torch.int32, device=g.dev)  # token ids | positions | out id
         tok = g.leaf(inp[:n_tok], TYPE_I32, n_tok)
         pos = g.leaf(inp[n_tok:2 * n_tok], TYPE_I32, n_tok)
@@ -346,6 +383,92 @@ class LlamaDecoder:
         self._run(L, g, use_graph)
         self.prompt_hidden = g["hidden"]
         return g["logits"]
+
+    # ------------------------------------------------------------ log-probabilities and perplexity
+    def _check_logprobs(self, who: str, tokens):
+        """What logprobs and perplexity refuse whatever the positions are, in the name of `who`."""
+        V = self.hp["n_vocab"]
+        if self.split is not None:
+            raise Mi355xError(f"{who} runs on one GPU (no row split)")
+        if V % 4 or V > LOGPROB_MAX_N:
+            raise Mi355xError(f"{who}: the vocabulary must be a multiple of 4 entries up to {LOGPROB_MAX_N} "
+                              "(LOGPROB_BATCH's rows)")
+        if any(not 0 <= t < V for t in tokens):
+            raise Mi355xError(f"{who}: token outside the vocabulary")
+
+    def logprobs(self, tokens, start_pos: int = 0, targets=None, use_graph: bool = True, records: bool = False):
+        """The log-probabilities of given tokens under the model: runs the tokens as one prompt batch
+        at positions start_pos .. (writing their KV cells as prompt does), the head over every row
+        and mi355x_logprob_rows on the logits, synchronizes and copies back 24 bytes a token.
+        targets None: row i is scored on tokens[i + 1]; returns len(tokens) - 1 float64 values,
+        log softmax(logits of row i)[tokens[i + 1]]. targets: one index per row (an index outside
+        the vocabulary scores NaN); returns len(tokens) values. records: the rows' records
+        themselves (ggml_mi355x.logprob_dtype(): max, x_target, argmax, pad, sum) instead of
+        logprob_value of them. The rule is exact (include/ggml_mi355x.h): the records equal
+        tests/logprob_ref.py's on the logits step() produces token by token, bit for bit."""
+        n_tok = len(tokens)
+        self._check_logprobs("logprobs", tokens)
+        if n_tok < 1 or start_pos < 0 or start_pos + n_tok > self.n_ctx:
+            raise Mi355xError(f"logprobs: {n_tok} tokens at {start_pos} outside the KV cache (n_ctx {self.n_ctx})")
+        tg = list(tokens[1:]) + [-1] if targets is None else [int(t) for t in targets]  # (-1: no target, NaN)
+        if len(tg) != n_tok or any(not -2 ** 31 <= t < 2 ** 31 for t in tg):
+            raise Mi355xError("logprobs: targets need one int32 per token")
+        from . import lib
+        g = self._prompt_graph(n_tok, all_rows=True)
+        self.b.synchronize()  # the pinned staging rows are reused: the previous call's copies are done
+        host = g["host"]
+        host[:n_tok] = torch_tensor(tokens)
+        host[n_tok:2 * n_tok] = torch_tensor(range(start_pos, start_pos + n_tok))
+        host[2 * n_tok:] = torch_tensor(tg)
+        L = lib()
+        _check(L.mi355x_backend_set_tensor(self.b.h, g["inp"].data_ptr(), host.data_ptr(), 4 * host.numel()),
+               "set_tensor")
+        self._run(L, g, use_graph)
+        _check(L.mi355x_backend_get_tensor(self.b.h, g["rec_host"].data_ptr(), g["rec"].data_ptr(), 24 * n_tok),
+               "get_tensor")
+        self.b.synchronize()
+        rec = g["rec_host"].numpy().view(logprob_dtype()).copy()
+        if targets is None:
+            rec = rec[:-1]
+        return rec if records else logprob_value(rec)
+
+    def perplexity(self, tokens, n_ctx=None, n_batch: int = 512, bos=None, progress=None):
+        """llama-perplexity's procedure [U] over a text of token ids: len(tokens) // n_ctx chunks of
+        n_ctx tokens (n_ctx None: the decoder's), each run from position 0 in batches of n_batch
+        (a batch continues its chunk at start_pos; the cells a previous chunk left above the
+        position are never read by the causal attention); bos: that id replaces each chunk's first
+        token. Scored are the rows n_ctx // 2 .. n_ctx - 2 of each chunk, row i on the chunk's
+        token i + 1; the negative log-likelihood is summed in float64 in that order. Returns
+        dict(ppl=exp(nll / count), nll, count, top1): top1 the share of scored rows whose argmax is
+        their target. progress(chunks done, chunks, nll, count) is called after each chunk."""
+        n_ctx = self.n_ctx if n_ctx is None else int(n_ctx)
+        if not 3 <= n_ctx <= self.n_ctx or n_batch < 1:
+            raise Mi355xError(f"perplexity: n_ctx {n_ctx} must lie in [3, {self.n_ctx}] and n_batch {n_batch} be >= 1")
+        n_chunk = len(tokens) // n_ctx
+        if n_chunk < 1:
+            raise Mi355xError(f"perplexity: {len(tokens)} tokens are less than one chunk of {n_ctx}")
+        if bos is not None and not 0 <= bos < self.hp["n_vocab"]:
+            raise Mi355xError("perplexity: bos outside the vocabulary")
+        self._check_logprobs("perplexity", tokens[:n_chunk * n_ctx])
+        first, nll, count, hits = n_ctx // 2, 0.0, 0, 0
+        for c in range(n_chunk):
+            chunk = [int(t) for t in tokens[c * n_ctx:(c + 1) * n_ctx]]
+            tg = chunk[1:] + [-1]
+            if bos is not None:
+                chunk[0] = bos
+            for j in range(0, n_ctx, n_batch):
+                rec = self.logprobs(chunk[j:j + n_batch], start_pos=j, targets=tg[j:j + n_batch], records=True)
+                lo, hi = max(first, j), min(n_ctx - 1, j + len(rec))  # the scored rows of this batch
+                if lo >= hi:
+                    continue
+                lp = logprob_value(rec[lo - j:hi - j])
+                for v in lp.tolist():
+                    nll += -v
+                count += hi - lo
+                hits += int((rec["argmax"][lo - j:hi - j] == tg[lo:hi]).sum())
+            if progress is not None:
+                progress(c + 1, n_chunk, nll, count)
+        return dict(ppl=ppl_of(nll, count), nll=nll, count=count, top1=hits / count)
 
     # ------------------------------------------------------------ several sequences per step
     def _batch_graph(self, n_tok: int, n_kv: int):

@@ -26,6 +26,7 @@
 #ifndef GGML_MI355X_H
 #define GGML_MI355X_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -580,6 +581,46 @@ int mi355x_sample_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
                        const float *u /* [rows] */, int32_t *out /* [rows] */, void *workspace, size_t workspace_size,
                        void *stream);
 
+/* Log-probabilities on the device: for each of `rows` rows of f32 logits and a target index per
+ * row, the exact ingredients of log softmax(x)[target], in two launches in stream order
+ * (csrc/kq_logprob.hip): mi355x_argmax_rows, then kq_logsum_rows, in which no workgroup waits for
+ * another. llama.cpp's log_softmax (llama-perplexity [U]) sums scalar expf sequentially in f64;
+ * this rule differs from it only in the association of that f64 sum and in v_expf for expf.
+ * The rule (exact: the same record as tests/logprob_ref.py, bit for bit). For a row x of n
+ * entries, 1 <= n <= MI355X_LOGPROB_MAX_N, and its target t:
+ *   a   = mi355x_argmax's index, m = x[a]
+ *   d_i = x_i - m, one f32 subtraction
+ *   e_i = 0 if d_i == -inf, else v_expf(d_i) (ggml_v_expf, as the attention's and the sampler's)
+ *   q_j = (e_{4j} + e_{4j+1}) + (e_{4j+2} + e_{4j+3}) in f32, as ggml_vec_soft_max_f32 forms its
+ *         group sums; entries past n count as +0.0f
+ *   S   = the sum of (double)q_j over a perfect binary tree of adjacent pairs with 65536 leaves,
+ *         absent leaves +0.0: level 1 adds leaves (0, 1), (2, 3), ..., level 2 those results
+ *         pairwise, and so on, each node one f64 add. Adding +0.0 is exact and no e is negative,
+ *         so S depends neither on n's padding nor on how the launch is split.
+ *   the record: max = m, x_target = x[t], argmax = a, pad = 0, sum = S. A target outside [0, n)
+ *         (unsigned compare) gives x_target = the NaN 0x7fc00000 and reads nothing outside the row.
+ * The logarithm is the host's: the device's log is not correctly rounded, so the device stops at
+ * the record and mi355x_logprob_value finishes it: (double)x_target - (double)max - log(sum).
+ * A row holding a NaN or +inf yields what this arithmetic yields (a NaN sum).
+ * row_stride in floats, >= n and a multiple of 4; x 16-B aligned; 1 <= rows <= 65535; targets
+ * [rows], 4-B aligned; out [rows], 8-B aligned. mi355x_logprob_workspace_size:
+ * mi355x_argmax_rows_workspace_size's bytes and layout (2176 a row whatever n is; 0 for an n or
+ * rows outside the ranges): both launches use the one workspace, kq_logsum_rows a row's words for
+ * its workgroups' f64 sums and 4 bytes of the row's counter line for a. The caller owns it (8-B
+ * aligned), zeroes it once, and may hand it to mi355x_argmax_rows between calls; two calls that
+ * can run concurrently must not share one. Returns MI355X_E_INVAL (a null or misaligned pointer,
+ * n, rows or row_stride outside its range), MI355X_E_WORKSPACE (missing, misaligned or too small)
+ * or MI355X_E_NODEVICE, in that order, before any device access. */
+#define MI355X_LOGPROB_MAX_N 262144
+struct mi355x_logprob { float max, x_target; int32_t argmax, pad; double sum; };  /* 24 bytes */
+size_t mi355x_logprob_workspace_size(int64_t n, int64_t rows);
+int mi355x_logprob_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, const int32_t *targets,
+                        struct mi355x_logprob *out, void *workspace, size_t workspace_size, void *stream);
+/* (defined here, no symbol of the library: the name stands in parentheses) */
+static inline double (mi355x_logprob_value)(const struct mi355x_logprob *r) {
+    return (double)r->x_target - (double)r->max - log(r->sum);
+}
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -664,13 +705,20 @@ int mi355x_sample_rows(const float *x, int64_t n, int64_t rows, int64_t row_stri
  *                n_kv}. form 0: src1 F32 u [T] -> I32 [T]. form 1: src1 .. src4 as ARGMAX_BATCH's
  *                pos, cells, mask and history, src5 F32 draws [n_draws, T] (nb[1] the row stride)
  *                -> I32 [T]: ARGMAX_BATCH's writes with row i's sampled token, its draw
- *                draws[i][pos[i] + 1] where that entry exists, else 0.0f. */
+ *                draws[i][pos[i] + 1] where that entry exists, else 0.0f.
+ *   LOGPROB_BATCH mi355x_logprob_rows of src0, f32 [n, T] with packed rows (nb[1] = 4 n, n % 4 == 0,
+ *                1 <= n <= 262144, 1 <= T <= 65535), 16-B aligned, and src1 I32 targets [T]
+ *                -> I32 [6, T], 8-B aligned: row i is the struct mi355x_logprob of logits row i
+ *                and targets[i] (LlamaDecoder.logprobs). One launch unit of two launches
+ *                (kq_argmax_rows, kq_logsum_rows), never fused or elided; its workspace is the
+ *                backend's ARGMAX buffer. Captured and replayed like any node: the targets are
+ *                read on the device at run time. */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
     MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
-    MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15,
+    MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15, MI355X_OP_LOGPROB_BATCH = 16,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */
