@@ -27,6 +27,7 @@
 using kq::attn_batch_desc_of;
 using kq::attn_desc_of;
 using kq::rows_step_of;
+using kq::penalties_of;
 using kq::sampler_of;
 using kq::token_step_of;
 using kq::f_of;
@@ -386,6 +387,17 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             return kq::launch_logprob_rows((const float *)x->data, x->ne[0], x->ne[1], x->ne[0],
                                            (const int32_t *)t->src[1]->data, (mi355x_logprob *)t->data, b->am, b->am_size,
                                            st);
+        }
+        case MI355X_OP_PENALIZE: {  // in place on the logits; end, the history and the lists read on the device
+            const mi355x_tensor *x = t->src[0], *hist = t->src[2];
+            mi355x_penalties pen;
+            const int n_bias = penalties_of(t, pen);
+            const bool win = pen.last_n > 0;
+            return kq::launch_penalize_rows((float *)x->data, x->ne[0], x->ne[1], x->ne[0], &pen,
+                                            win ? (const int32_t *)hist->data : nullptr, win ? (int64_t)(hist->nb[1] / 4) : 0,
+                                            win ? hist->ne[0] : 0, win ? (const int32_t *)t->src[1]->data : nullptr,
+                                            n_bias ? (const int32_t *)t->src[3]->data : nullptr,
+                                            n_bias ? (const float *)t->src[4]->data : nullptr, n_bias, st);
         }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;

@@ -353,6 +353,16 @@ size_t logprob_workspace(int64_t n, int64_t rows);
 int launch_logprob_rows(const float *x, int64_t n, int64_t rows, int64_t row_stride, const int32_t *targets,
                         mi355x_logprob *out, void *ws, size_t ws_size, hipStream_t stream);
 
+// ---------------------------------------------------------------- kq_penalize.hip
+// The sampler's penalties and logit bias, in place on each row of an f32 matrix (include/ggml_mi355x.h,
+// the rule): one launch of one workgroup a row, no workspace. penalties_ok: the parameters' ranges.
+constexpr int kPenaltyMaxLastN = MI355X_PENALTY_MAX_LAST_N;
+constexpr int kLogitBiasMax = MI355X_LOGIT_BIAS_MAX;
+bool penalties_ok(const mi355x_penalties *p, int n_bias);
+int launch_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, const mi355x_penalties *p,
+                         const int32_t *hist, int64_t hist_stride, int64_t n_hist, const int32_t *end,
+                         const int32_t *bias_tok, const float *bias_val, int n_bias, hipStream_t stream);
+
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from
 // checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /

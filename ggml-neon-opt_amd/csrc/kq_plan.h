@@ -63,6 +63,7 @@ bool kv_epilogue(mi355x_tensor *const *nodes, const Launch &l, const Launch &nex
 void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a);  // rope_row left to the caller
 void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d);
 void sampler_of(const mi355x_tensor *t, mi355x_sampler &s);  // SAMPLE / SAMPLE_BATCH: op_params[1 .. 4]
+int penalties_of(const mi355x_tensor *t, mi355x_penalties &p);  // PENALIZE: op_params[0 .. 3]; returns n_bias ([4])
 // the step-inputs forms' operands: ARGMAX / SAMPLE (pos, rope table, history: src1 .. 3), and
 // ARGMAX_BATCH / SAMPLE_BATCH (pos, cells, mask, history: src1 .. 4; cell_stride and n_kv at
 // op_params[first_param], [first_param + 1])

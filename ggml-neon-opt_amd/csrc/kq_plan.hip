@@ -249,6 +249,15 @@ void sampler_of(const mi355x_tensor *t, mi355x_sampler &s) {
     s.min_p = f_of(t->op_params[4]);
 }
 
+// PENALIZE: op_params = {last_n, the bits of repeat, freq, present, n_bias}; returns n_bias
+int penalties_of(const mi355x_tensor *t, mi355x_penalties &p) {
+    p.last_n = t->op_params[0];
+    p.repeat = f_of(t->op_params[1]);
+    p.freq = f_of(t->op_params[2]);
+    p.present = f_of(t->op_params[3]);
+    return t->op_params[4];
+}
+
 ArgmaxStep token_step_of(const mi355x_tensor *t) {
     const mi355x_tensor *tab = t->src[2], *hist = t->src[3];
     return {(const int32_t *)t->src[1]->data, (const float *)tab->data, (int32_t *)hist->data, tab->ne[1], hist->ne[0],
@@ -736,6 +745,37 @@ bool supports_op(const mi355x_tensor *op) {
                 return false;
             return op->type == MI355X_TYPE_I32 && op->data && !((uintptr_t)op->data & 7u) && op->nb[0] == 4 &&
                    op->ne[0] == 6 && op->ne[1] == T && nelem(op) == 6 * T && op->nb[1] == sizeof(mi355x_logprob);
+        }
+        case MI355X_OP_PENALIZE: {
+            // in place on src0, f32 [n, T] of mi355x_penalize_rows' sizes with packed rows; end I32 [T]
+            // and the history I32 [n_hist, T] (null at last_n 0); the bias lists I32 / F32 [n_bias]
+            // (null at n_bias 0)
+            const mi355x_tensor *x = op->src[0], *end = op->src[1], *hist = op->src[2], *bt = op->src[3], *bv = op->src[4];
+            if (!x || x->type != MI355X_TYPE_F32 || !x->data || ((uintptr_t)x->data & 3u) || x->nb[0] != 4) return false;
+            const int64_t n = x->ne[0], T = x->ne[1];
+            if (n < 1 || n > kArgmaxMaxN || T < 1 || T > kArgmaxMaxRows || nelem(x) != n * T || x->nb[1] != (size_t)n * 4)
+                return false;
+            if (op->data != x->data || op->type != x->type || memcmp(op->ne, x->ne, sizeof(op->ne)) ||
+                memcmp(op->nb, x->nb, sizeof(op->nb)))
+                return false;
+            mi355x_penalties pen;
+            const int n_bias = penalties_of(op, pen);
+            if (!penalties_ok(&pen, n_bias)) return false;
+            if (pen.last_n > 0) {
+                if (!end || end->type != MI355X_TYPE_I32 || !end->data || end->nb[0] != 4 || end->ne[0] != T || nelem(end) != T)
+                    return false;
+                if (!hist || hist->type != MI355X_TYPE_I32 || !hist->data || hist->nb[0] != 4 || hist->ne[0] < 1 ||
+                    hist->ne[0] > 0x7fffffff || hist->ne[1] != T || nelem(hist) != hist->ne[0] * T || hist->nb[1] % 4 ||
+                    hist->nb[1] < (size_t)hist->ne[0] * 4)
+                    return false;
+            }
+            if (n_bias > 0) {
+                auto list = [n_bias](const mi355x_tensor *t, int type) {
+                    return t && t->type == type && t->data && t->nb[0] == 4 && t->ne[0] == n_bias && nelem(t) == n_bias;
+                };
+                if (!list(bt, MI355X_TYPE_I32) || !list(bv, MI355X_TYPE_F32)) return false;
+            }
+            return true;
         }
         default:
             return false;

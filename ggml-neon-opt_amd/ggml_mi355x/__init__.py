@@ -36,6 +36,10 @@ SAMPLE_PLAIN, SAMPLE_STEP_INPUTS = 0, 1
 SAMPLE_MAX_K = 64
 OP_LOGPROB_BATCH = 16  # src0 the logits [n, T], src1 I32 targets [T] -> I32 [6, T]: the rows' records (LOGPROB_DTYPE)
 LOGPROB_MAX_N = 262144
+# in place on src0, the logits [n, T]; src1 I32 end [T], src2 I32 history [n_hist, T], src3 / src4 the bias lists
+# [n_bias]; op_params: penalize_params(...)
+OP_PENALIZE = 17
+PENALTY_MAX_LAST_N, LOGIT_BIAS_MAX = 1024, 256
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -84,6 +88,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_argmax_rows_workspace_size", "mi355x_argmax_rows",
     "mi355x_topk_workspace_size", "mi355x_topk", "mi355x_topk_rows", "mi355x_sample", "mi355x_sample_rows",
     "mi355x_logprob_workspace_size", "mi355x_logprob_rows",
+    "mi355x_penalize_rows",
 )
 
 
@@ -95,6 +100,12 @@ class SamplerDesc(ctypes.Structure):
     """struct mi355x_sampler"""
     _fields_ = [("top_k", ctypes.c_int32), ("temp", ctypes.c_float), ("top_p", ctypes.c_float),
                 ("min_p", ctypes.c_float)]
+
+
+class PenaltiesDesc(ctypes.Structure):
+    """struct mi355x_penalties"""
+    _fields_ = [("last_n", ctypes.c_int32), ("repeat", ctypes.c_float), ("freq", ctypes.c_float),
+                ("present", ctypes.c_float)]
 
 
 class GemvDesc(ctypes.Structure):
@@ -296,6 +307,10 @@ def lib():
         L.mi355x_logprob_workspace_size.restype = sz
         L.mi355x_logprob_rows.argtypes = [vp, i64, i64, i64, vp, vp, vp, sz, vp]
         L.mi355x_logprob_rows.restype = i32
+    if hasattr(L, "mi355x_penalize_rows"):
+        L.mi355x_penalize_rows.argtypes = [vp, i64, i64, i64, ctypes.POINTER(PenaltiesDesc), vp, i64, i64, vp, vp, vp, i32,
+                                           vp]
+        L.mi355x_penalize_rows.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -984,6 +999,82 @@ def logprob_value(records):
                     dtype=np.float64).reshape(r.shape)
     with np.errstate(all="ignore"):
         return r["x_target"].astype(np.float64) - r["max"].astype(np.float64) - logs
+
+
+def penalize_params(last_n, repeat, freq, present, n_bias):
+    """The PENALIZE node's op_params."""
+    return [last_n, f32_bits(repeat), f32_bits(freq), f32_bits(present), n_bias]
+
+
+def bias_pairs(bias):
+    """A logit bias, None, a dict {token: bias} or a list of (token, bias) pairs, as the list of
+    (int, float) pairs in its order."""
+    if bias is None:
+        return []
+    pairs = [(int(t), float(v)) for t, v in (bias.items() if isinstance(bias, dict) else bias)]
+    if len(pairs) > LOGIT_BIAS_MAX or any(not -2 ** 31 <= t < 2 ** 31 for t, _ in pairs):
+        raise Mi355xError(f"logit bias: at most {LOGIT_BIAS_MAX} (int32 token, bias) pairs")
+    return pairs
+
+
+def penalize_rows(x, hist=None, end=None, last_n=0, repeat=1.0, freq=0.0, present=0.0, bias=None, stream=None):
+    """mi355x_penalize_rows: the sampler's repetition / frequency / presence penalties and logit bias
+    (the exact rule is in include/ggml_mi355x.h), in place on x, a contiguous f32 cuda vector [n]
+    or a 2-D one [rows, n] with unit column stride (any row stride >= n); returns x (no
+    synchronization). hist: an int32 cuda tensor [n_hist] or [rows, n_hist] with unit column
+    stride, the rows' past tokens; end: one int per row (or an int32 cuda tensor [rows]): row i's
+    window is hist[i][end[i] - last_n + 1 .. end[i]], clipped to the row. bias: None, a dict
+    {token: bias}, a list of (token, bias) pairs (added in list order; float("-inf") bans a
+    token), or a pair of cuda tensors (int32 [n_bias], float32 [n_bias]). last_n 0: hist and end
+    are not needed. With a `stream` and an end or bias given on the host, the call synchronizes."""
+    import numpy as np
+    torch = _torch()
+    _require_device()
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (1, 2) and x.numel() >= 1 and
+            x.stride(-1) == 1):
+        raise Mi355xError("penalize_rows: x must be a float32 cuda vector or matrix with unit column stride")
+    rows, n = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    stride = x.stride(0) if x.dim() == 2 and rows > 1 else n
+    copied = False
+    hist_ptr, hist_stride, n_hist, end_ptr = None, 0, 0, None
+    if last_n > 0:
+        if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() in (1, 2) and
+                hist.numel() >= 1 and hist.stride(-1) == 1 and (hist.shape[0] if hist.dim() == 2 else 1) == rows):
+            raise Mi355xError("penalize_rows: hist must be an int32 cuda tensor [n_hist] or [rows, n_hist] with unit "
+                              "column stride")
+        n_hist = hist.shape[-1]
+        hist_stride = hist.stride(0) if hist.dim() == 2 and rows > 1 else n_hist
+        if end is None:
+            raise Mi355xError("penalize_rows: end is needed with last_n > 0")
+        if not torch.is_tensor(end):
+            end = torch.from_numpy(np.ascontiguousarray(np.atleast_1d(end), dtype=np.int32)).to(x.device)
+            copied = True
+        if not (end.is_cuda and end.dtype == torch.int32 and end.is_contiguous() and end.numel() == rows):
+            raise Mi355xError("penalize_rows: end must be one int32 per row")
+        hist_ptr, end_ptr = hist.data_ptr(), end.data_ptr()
+    if isinstance(bias, tuple) and len(bias) == 2 and torch.is_tensor(bias[0]):
+        bt, bv = bias
+        if not (bt.is_cuda and bt.dtype == torch.int32 and bt.is_contiguous() and bv.is_cuda and bv.dtype == torch.float32 and
+                bv.is_contiguous() and bt.numel() == bv.numel()):
+            raise Mi355xError("penalize_rows: bias tensors must be int32 / float32 cuda vectors of one length")
+        n_bias = bt.numel()
+    else:
+        pairs = bias_pairs(bias)
+        n_bias = len(pairs)
+        if n_bias:
+            bt = torch.tensor([t for t, _ in pairs], dtype=torch.int32).to(x.device)
+            bv = torch.tensor([v for _, v in pairs], dtype=torch.float32).to(x.device)
+            copied = True
+    if copied and stream is not None:
+        torch.cuda.current_stream().synchronize()  # copied on torch's stream, read on `stream`
+    pen = PenaltiesDesc(int(last_n), float(repeat), float(freq), float(present))
+    _check(_lib_with("mi355x_penalize_rows").mi355x_penalize_rows(
+        x.data_ptr(), n, rows, stride, ctypes.byref(pen), hist_ptr, hist_stride, n_hist, end_ptr,
+        bt.data_ptr() if n_bias else None, bv.data_ptr() if n_bias else None, n_bias, _stream(stream)),
+        "mi355x_penalize_rows")
+    if copied and stream is not None:
+        torch.cuda.synchronize()  # the copies made here are read on `stream`: they stay until it is done
+    return x
 
 
 def block_partials(type_, w, K, q8_row, stream=None):

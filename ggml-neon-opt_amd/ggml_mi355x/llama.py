@@ -26,7 +26,9 @@ layer body and the one head below (LlamaDecoder._layers, ._head) over a _Graph:
                   cells and mask from the inputs, logits of every row
   generate,       the token graph / the batch graph plus one ARGMAX / ARGMAX_BATCH node
   generate_batch  that stages the next step's inputs on the device; with a Sampler that last
-                  node is a SAMPLE / SAMPLE_BATCH, which reads its draws from a device table
+                  node is a SAMPLE / SAMPLE_BATCH, which reads its draws from a device table; with
+                  a Sampler that edits the logits (penalties, logit bias) a PENALIZE node stands
+                  between the logits and that node and reads the history the steps write
   logprobs,       _prompt_graph(n_tok, all_rows=True): the prompt's layers with no row selection,
   perplexity      the head over all n_tok rows and one LOGPROB_BATCH node on the logits and the
                   targets: 24 bytes a token come back, not a row of the vocabulary
@@ -35,11 +37,11 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, LOGPROB_MAX_N, OP_ADD, OP_ALL_GATHER, OP_ALL_REDUCE,
-               OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_LOGPROB_BATCH, OP_MUL,
-               OP_MUL_MAT, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS,
-               TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, f32_bits, logprob_dtype, logprob_value, make_tensor,
-               rope_table, sampler_params)
+from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, LOGIT_BIAS_MAX, LOGPROB_MAX_N, OP_ADD, OP_ALL_GATHER,
+               OP_ALL_REDUCE, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_LOGPROB_BATCH,
+               OP_MUL, OP_MUL_MAT, OP_PENALIZE, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, PENALTY_MAX_LAST_N,
+               QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, bias_pairs,
+               f32_bits, logprob_dtype, logprob_value, make_tensor, penalize_params, rope_table, sampler_params)
 
 
 def torch_tensor(values):
@@ -73,6 +75,15 @@ def ppl_of(nll, count):
         return math.inf
 
 
+def _as_f32(v):
+    """v rounded to float32, as a Python float (inf where it overflows)."""
+    import struct
+    try:
+        return struct.unpack("<f", struct.pack("<f", float(v)))[0]
+    except OverflowError:
+        return float("inf") if v > 0 else float("-inf")
+
+
 def _node_array(nodes):
     return (ctypes.POINTER(type(nodes[0])) * len(nodes))(*[ctypes.pointer(n) for n in nodes])
 
@@ -82,15 +93,54 @@ class Sampler:
     its defaults [U] (the exact rule: include/ggml_mi355x.h, mi355x_sample). seed: the draws of
     generate / generate_batch are numpy's PCG64(seed) float32 stream (sequence i of a batch:
     PCG64([seed, i])), entry p the draw of the token that will stand at position p, so the same
-    seed and context give the same tokens whatever chunk, n or use_graph is."""
+    seed and context give the same tokens whatever chunk, n or use_graph is.
+    Before the chain the logits can be edited on the device (mi355x_penalize_rows' rule; llama.cpp's
+    logit-bias and penalties samplers [U], in its order: the bias, then the penalties, then top-k):
+    repeat_penalty, freq_penalty and presence_penalty over the last repeat_last_n tokens (defaults:
+    off, as llama.cpp's [U]) and logit_bias, a dict {token: bias} or a list of (token, bias) pairs
+    of at most 256 entries, added in list order; float("-inf") bans a token. Greedy decoding with
+    penalties is temp=0."""
 
-    def __init__(self, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, seed=0):
+    def __init__(self, top_k=40, top_p=0.95, min_p=0.05, temp=0.8, seed=0, repeat_last_n=64, repeat_penalty=1.0,
+                 freq_penalty=0.0, presence_penalty=0.0, logit_bias=None):
         import math
         self.top_k, self.top_p, self.min_p, self.temp, self.seed = int(top_k), float(top_p), float(min_p), float(temp), seed
         if not (1 <= self.top_k <= SAMPLE_MAX_K and math.isfinite(self.temp) and self.temp >= 0 and
                 0 < self.top_p <= 1 and 0 <= self.min_p <= 1):
             raise Mi355xError(f"Sampler: top_k {top_k} in [1, {SAMPLE_MAX_K}], temp {temp} finite and >= 0, top_p {top_p} "
                               f"in (0, 1] and min_p {min_p} in [0, 1] are required")
+        self.repeat_last_n = int(repeat_last_n)
+        # the values the device takes: float32
+        self.repeat_penalty, self.freq_penalty, self.presence_penalty = (_as_f32(v) for v in (repeat_penalty, freq_penalty,
+                                                                                            presence_penalty))
+        if not (0 <= self.repeat_last_n <= PENALTY_MAX_LAST_N and self.repeat_last_n == repeat_last_n and
+                math.isfinite(self.repeat_penalty) and self.repeat_penalty > 0 and math.isfinite(self.freq_penalty) and
+                math.isfinite(self.presence_penalty)):
+            raise Mi355xError(f"Sampler: repeat_last_n {repeat_last_n} an integer in [0, {PENALTY_MAX_LAST_N}], repeat_penalty "
+                              f"{repeat_penalty} finite and > 0 (as float32), freq_penalty {freq_penalty} and "
+                              f"presence_penalty {presence_penalty} finite are required")
+        try:
+            self.logit_bias = [(t, _as_f32(v)) for t, v in bias_pairs(logit_bias)]
+        except (TypeError, ValueError) as e:
+            raise Mi355xError(f"Sampler: logit_bias must be a dict {{token: bias}} or a list of (token, bias) pairs ({e})")
+        if any(math.isnan(v) for _, v in self.logit_bias):
+            raise Mi355xError("Sampler: a logit bias is NaN")
+
+    def penalizes(self):
+        """True when the window penalty is not the identity."""
+        return self.repeat_last_n > 0 and (self.repeat_penalty != 1.0 or self.freq_penalty != 0.0 or
+                                           self.presence_penalty != 0.0)
+
+    def edits(self):
+        """True when the sampler edits the logits before the chain: a window penalty that is not the
+        identity or a bias list that is not empty (a PENALIZE node then precedes the SAMPLE node)."""
+        return self.penalizes() or bool(self.logit_bias)
+
+    def penalize_params(self):
+        """The PENALIZE node's op_params (the graphs are cached by them too): last_n is 0 where the
+        window penalty is the identity, so that node reads no window."""
+        return penalize_params(self.repeat_last_n if self.penalizes() else 0, self.repeat_penalty, self.freq_penalty,
+                               self.presence_penalty, len(self.logit_bias))
 
     def params(self, form=SAMPLE_STEP_INPUTS):
         """The SAMPLE nodes' leading op_params (the graphs are cached by them: the seed is not part)."""
@@ -183,7 +233,7 @@ class LlamaDecoder:
         self.gathers = []  # (node output buffer) of every ALL_GATHER, in graph order
         self.reduces = []  # (input partial, output) buffers of every ALL_REDUCE (split mode "reduce")
         self._prompts, self._batches, self._gen_batches, self._batch_hists, self._gen = {}, {}, {}, {}, None
-        self._gen_sampled, self._draws, self._batch_draws, self.history = {}, None, {}, None
+        self._gen_sampled, self._draws, self._batch_draws, self.history, self._bias = {}, None, {}, None, None
         # inp_tokens, inp_pos and the rope row of that position side by side: one
         # set_tensor of 8 + 4*head_dim bytes per token. The attention reads its cos/sin
         # with q/k/v instead of after the position (one dependent round trip less);
@@ -583,6 +633,69 @@ class LlamaDecoder:
         torch.cuda.synchronize()
         d["seed"] = (sampler.seed,)
 
+    # ------------------------------------------------------------ the samplers' edits of the logits
+    def _bias_lists(self):
+        """The device lists every PENALIZE node reads the logit bias from: LOGIT_BIAS_MAX (token, bias)
+        entries a decoder, shared by all rows and graphs. Allocated once (the graphs hold its
+        address), filled by _set_bias."""
+        import torch
+        if self._bias is None:
+            dev = self.inp.device
+            self._bias = dict(tok=torch.full((LOGIT_BIAS_MAX,), -1, dtype=torch.int32, device=dev),
+                              val=torch.zeros(LOGIT_BIAS_MAX, dtype=torch.float32, device=dev), held=[])
+        return self._bias
+
+    def _set_bias(self, sampler):
+        """Fills the bias lists with sampler.logit_bias unless they hold it already, as _seed fills the
+        draws: the backend is synchronized first (a run may still read them), torch's stream after."""
+        import torch
+        d = self._bias_lists()
+        if d["held"] == sampler.logit_bias:
+            return
+        self.b.synchronize()
+        n = len(sampler.logit_bias)
+        if n:
+            d["tok"][:n].copy_(torch.tensor([t for t, _ in sampler.logit_bias], dtype=torch.int32))
+            d["val"][:n].copy_(torch.tensor([v for _, v in sampler.logit_bias], dtype=torch.float32))
+        torch.cuda.synchronize()
+        d["held"] = list(sampler.logit_bias)
+
+    def _penalize_node(self, sampler, logits, end, hist):
+        """sampler's PENALIZE node in place on the node `logits`, with the positions `end` and the
+        history `hist` (both left out where the node reads no window): (the node, the descriptors it
+        keeps alive). The SAMPLE node that follows takes it as its src0."""
+        pp = sampler.penalize_params()
+        d, n_bias, win = self._bias_lists(), pp[4], pp[0] > 0
+        srcs = [logits, end if win else None, hist if win else None,
+                make_tensor(TYPE_I32, n_bias, 1, d["tok"].data_ptr()) if n_bias else None,
+                make_tensor(TYPE_F32, n_bias, 1, d["val"].data_ptr()) if n_bias else None]
+        pen = make_tensor(TYPE_F32, logits.ne[0], logits.ne[1], logits.data, op=OP_PENALIZE, srcs=srcs, op_params=pp,
+                          flags=FLAG_OUTPUT)
+        return pen, [s for s in srcs[1:] if s is not None]
+
+    def _check_context(self, who: str, context, pos: int):
+        """The sampler's memory of the tokens before `pos` as a list of ints (None: empty)."""
+        ctx = [] if context is None else [int(t) for t in context]
+        if len(ctx) > pos or any(not -2 ** 31 <= t < 2 ** 31 for t in ctx):
+            raise Mi355xError(f"{who}: the context holds at most pos ({pos}) int32 tokens, the last at pos - 1")
+        return ctx
+
+    def _stage_history(self, L, host, dev, token: int, pos: int, ctx, last_n: int):
+        """What an editing sampler's first window reads, from the pinned row `host` into the history
+        row `dev` with one copy: entries [max(0, pos - last_n + 1), pos] = the context's tail, -1
+        where the context does not reach, and the start token at pos."""
+        import torch
+        if last_n < 1:
+            return
+        lo = max(0, pos - last_n + 1)
+        k = min(len(ctx), pos - lo)
+        host[lo:pos - k] = -1
+        if k:
+            host[pos - k:pos] = torch_tensor(ctx[len(ctx) - k:])
+        host[pos] = token
+        _check(L.mi355x_backend_set_tensor(self.b.h, dev[lo:].data_ptr(), host[lo:].data_ptr(), 4 * (pos - lo + 1)),
+               "set_tensor")
+
     # ------------------------------------------------------------ greedy generation of several sequences
     def _generate_batch_graph(self, n_tok: int, n_kv: int, cell_stride: int, sampler=None):
         """_batch_graph(n_tok, n_kv)'s nodes plus one step-inputs ARGMAX_BATCH on the logits: it ends
@@ -590,7 +703,9 @@ class LlamaDecoder:
         input block, showing the new cell in the sequence's mask row and filing the token in
         self.batch_history[i][pos + 1], so the one captured graph is replayed with no host copy."""
         import torch
-        key = (n_tok, n_kv, cell_stride) + (() if sampler is None else tuple(sampler.params()))
+        edits = sampler is not None and sampler.edits()
+        key = (n_tok, n_kv, cell_stride) + (() if sampler is None else tuple(sampler.params())) + \
+            (tuple(sampler.penalize_params()) if edits else ())
         cached = self._gen_batches.get(key)
         if cached is not None:
             return cached
@@ -610,16 +725,21 @@ class LlamaDecoder:
                              op_params=[ARGMAX_STEP_INPUTS, cell_stride, n_kv], flags=FLAG_OUTPUT)
         else:  # the same writes with sampled tokens: one more source, the sequences' draws
             srcs.append(make_tensor(TYPE_F32, self.n_ctx + 1, T, self._draws_table(T)["dev"].data_ptr()))
+            keep = []
+            if edits:  # ... logits, PENALIZE, SAMPLE_BATCH(src0 = PENALIZE): the edit in place, before the top-k
+                pen, keep = self._penalize_node(sampler, srcs[0], srcs[1], srcs[4])
+                srcs[0] = pen
             am = make_tensor(TYPE_I32, T, 1, inp.data_ptr(), op=OP_SAMPLE_BATCH, srcs=srcs,
                              op_params=sampler.params() + [cell_stride, n_kv], flags=FLAG_OUTPUT)
-        nodes = g["nodes"] + [am]
+            srcs = srcs + keep
+        nodes = g["nodes"] + ([srcs[0]] if edits else []) + [am]
         gg = dict(batch=g, nodes=nodes, keep=srcs + [am], hist=hists[n_tok], arr=_node_array(nodes))
         self._gen_batches[key] = gg
         torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
         return gg
 
     def generate_batch(self, tokens, pos, cells, mask, n: int, n_kv: int, cell_stride: int = 1, eos=None,
-                       chunk: int = 32, use_graph: bool = True, sampler=None):
+                       chunk: int = 32, use_graph: bool = True, sampler=None, contexts=None):
         """Greedy decoding of n steps of T sequences together: sequence i starts from tokens[i] at
         position pos[i] in cache cell cells[i] under mask[i] (step_batch's inputs), and its step k
         runs at position pos[i] + k in cell cells[i] + k * cell_stride. Returns a list of T lists of
@@ -638,7 +758,10 @@ class LlamaDecoder:
         entries are written too. A following step_batch or generate_batch works as ever: it
         restages the whole input block.
         sampler: a Sampler: every token is sampled on the device instead (a SAMPLE_BATCH node ends
-        the step), sequence i's token for position p with entry p of its own row of draws."""
+        the step), sequence i's token for position p with entry p of its own row of draws.
+        contexts: with a sampler that edits the logits (Sampler.edits()), sequence i's tokens before
+        pos[i] as generate's `context` (None, or one list or None per sequence); every row's window
+        is its own. Ignored otherwise. The logits buffer then holds the edited logits after a step."""
         import numpy as np
         if self.split is not None:
             raise Mi355xError("generate_batch runs on one GPU (no row split)")
@@ -660,12 +783,23 @@ class LlamaDecoder:
         if not np.isneginf(m[:, :n_kv].numpy()[:, written[:, 1:].ravel()]).all():
             raise Mi355xError("generate_batch: a cell that a later step writes is visible in the mask (every such cell "
                               "must be -inf in every row; the device shows it to its own sequence)")
+        edits = sampler is not None and sampler.edits()
+        if edits:
+            if contexts is not None and len(contexts) != T:
+                raise Mi355xError("generate_batch: contexts needs one entry per sequence")
+            ctxs = [self._check_context("generate_batch", None if contexts is None else contexts[i], pos[i])
+                    for i in range(T)]
         g = self._generate_batch_graph(T, n_kv, cell_stride, sampler)
         if sampler is not None:
             self._seed(sampler, T)
+        if edits:
+            self._set_bias(sampler)
         self.batch_history = g["hist"]["dev"]
         L = self._stage_batch(g["batch"], tokens, pos, cells, m)
         dev, host = g["hist"]["dev"], g["hist"]["host"]
+        if edits:
+            for i in range(T):
+                self._stage_history(L, host[i], dev[i], tokens[i], pos[i], ctxs[i], sampler.repeat_last_n)
         out, live, done = [[] for _ in range(T)], [True] * T, 0
         while done < n and any(live):
             c = min(chunk, n - done)
@@ -723,7 +857,8 @@ class LlamaDecoder:
         sampler the last node is a step-inputs SAMPLE instead: the same writes with the sampled
         token, one more source (the draws); one graph per sampler parameters."""
         import torch
-        key = None if sampler is None else tuple(sampler.params())
+        edits = sampler is not None and sampler.edits()
+        key = None if sampler is None else tuple(sampler.params()) + (tuple(sampler.penalize_params()) if edits else ())
         cached = self._gen if sampler is None else self._gen_sampled.get(key)
         if cached is not None:
             return cached
@@ -739,9 +874,14 @@ class LlamaDecoder:
                              op_params=[ARGMAX_STEP_INPUTS], flags=FLAG_OUTPUT)
         else:
             srcs.append(make_tensor(TYPE_F32, self.n_ctx + 1, 1, self._draws_table()["dev"].data_ptr()))
+            keep = []
+            if edits:  # ... logits, PENALIZE, SAMPLE(src0 = PENALIZE): the edit in place, before the top-k
+                pen, keep = self._penalize_node(sampler, srcs[0], srcs[1], srcs[3])
+                srcs[0] = pen
             am = make_tensor(TYPE_I32, 2 + hd, 1, self.inp.data_ptr(), op=OP_SAMPLE, srcs=srcs,
                              op_params=sampler.params(), flags=FLAG_OUTPUT)
-        nodes = self.nodes + [am]
+            srcs = srcs + keep
+        nodes = self.nodes + ([srcs[0]] if edits else []) + [am]
         g = dict(nodes=nodes, keep=srcs + [am], arr=_node_array(nodes))
         if sampler is None:
             self._gen = g
@@ -752,7 +892,8 @@ class LlamaDecoder:
             torch.cuda.synchronize()  # the zeroed history (torch's stream) before the backend stream runs
         return g
 
-    def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True, sampler=None):
+    def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True, sampler=None,
+                 context=None):
         """Greedy decoding of n tokens at positions pos .. pos + n - 1, starting from `token` at
         `pos`: returns the generated tokens as a list of ints (the token picked after position p
         is the argmax of that step's logits, mi355x_argmax's rule). The inputs are staged from the
@@ -762,7 +903,17 @@ class LlamaDecoder:
         run on to the end of that chunk: its later cells and history entries are then written
         too). A following step() works as ever: it restages the whole input block.
         sampler: a Sampler: every token is sampled on the device instead (mi355x_sample's rule; a
-        SAMPLE node ends the token), the token for position p with entry p of the seed's draws."""
+        SAMPLE node ends the token), the token for position p with entry p of the seed's draws.
+        A sampler that edits the logits (Sampler.edits(): penalties, logit bias) puts a PENALIZE node
+        between the logits and the SAMPLE node: mi355x_penalize_rows' rule on the window
+        history[pos - repeat_last_n + 1 .. pos] of every step, which the steps themselves extend.
+        context: the sampler's memory of the tokens before `pos` (llama.cpp's accepted tokens): at
+        most pos tokens, the last standing at pos - 1; it is not checked against the cache. Before
+        the first step the host writes the history entries [max(0, pos - repeat_last_n + 1), pos]
+        with one copy: the context's tail, -1 where the context does not reach, `token` at pos.
+        Without such a sampler context is ignored and the history below pos + 1 is not written.
+        Under an editing sampler the logits buffer holds the edited logits after a step (llama.cpp
+        edits a copy; here a copy would cost another pass over the row)."""
         if self.split is not None:
             raise Mi355xError("generate runs on one GPU (no row split)")
         if n < 0 or chunk < 1:
@@ -771,11 +922,18 @@ class LlamaDecoder:
             raise Mi355xError(f"generate: {n} tokens from position {pos} outside the KV cache (n_ctx {self.n_ctx})")
         if n == 0:
             return []
+        edits = sampler is not None and sampler.edits()
+        if edits:
+            ctx = self._check_context("generate", context, pos)
         g = self._generate_graph(sampler)
         if sampler is not None:
             self._seed(sampler)
+        if edits:
+            self._set_bias(sampler)
         L = self._stage_inputs(token, pos)
         host, out, done = g["host"], [], 0
+        if edits:
+            self._stage_history(L, host, self.history, token, pos, ctx, sampler.repeat_last_n)
         while done < n:
             c = min(chunk, n - done)
             self._run(L, g, use_graph, times=c)

@@ -621,6 +621,49 @@ static inline double (mi355x_logprob_value)(const struct mi355x_logprob *r) {
     return (double)r->x_target - (double)r->max - log(r->sum);
 }
 
+/* Sampler penalties and logit bias on the device: each of `rows` rows of f32 logits is edited in
+ * place, before a top-k / sample / argmax call reads it, from the row's window of past tokens and
+ * a list of (token, bias) pairs, in one launch of one workgroup a row (csrc/kq_penalize.hip): no
+ * atomics, no workgroup waits for another, no workspace.
+ * The rule (exact: the same bits as tests/penalize_ref.py).
+ *   Parameters: last_n in [0, MI355X_PENALTY_MAX_LAST_N], repeat finite and > 0, freq and present
+ *   finite, n_bias in [0, MI355X_LOGIT_BIAS_MAX] pairs (bias_tok[k], bias_val[k]), a bias_val may
+ *   be +-inf; anything else is MI355X_E_INVAL.
+ *   Window of row i: the history entries hist[i * hist_stride + j] for the j with
+ *   end[i] - last_n < j <= end[i] and 0 <= j < n_hist, j computed in 64 bits. end is an int32 on
+ *   the device, read at run time; any end, INT32_MIN and INT32_MAX included, reads nothing outside
+ *   the row of hist. last_n == 0: no window.
+ *   A token id outside [0, n) (unsigned compare), in the window or in the bias list, is ignored
+ *   (-1 is the "no token" filler). For a token t, c(t) is the number of window entries equal to
+ *   t and B(t) the bias entries with bias_tok[k] == t, in the order of k. If c(t) == 0 and B(t)
+ *   is empty, x[t] keeps its bits (a NaN's payload too). For every other t, in f32, every
+ *   operation rounded once, nothing contracted, the division correctly rounded:
+ *     1. v = x[t]
+ *     2. for each k in B(t), in order: v = v + bias_val[k]
+ *     3. if c(t) > 0: v = (v <= 0) ? v * repeat : v / repeat, then
+ *        v = v - ((float)c(t) * freq + present): one multiply, one add, one subtract
+ *     4. x[t] = v
+ *   So a NaN logit stays NaN, -inf stays -inf, -0.0 counts as <= 0, and repeat 1 with freq 0 and
+ *   present 0 leaves every non-NaN value's bits unchanged.
+ *   Against llama.cpp [U]: the bias comes before the penalties, as in its chain (logit-bias,
+ *   penalties, top-k); its penalty line is logit -= float(count) * penalty_freq +
+ *   float(count > 0) * penalty_present, which is step 3 with the contraction pinned.
+ * Every distinct token is written by exactly one thread, which has loaded it before; nothing in
+ * global memory is read after another thread's store.
+ * 1 <= n <= 2^24, 1 <= rows <= 65535, row_stride >= n in floats, x 4-B aligned. last_n == 0: hist
+ * and end may be null; n_bias == 0: the lists may be null; both zero: MI355X_OK, no launch.
+ * Returns MI355X_E_INVAL, in this order: a null x or p; n, rows or row_stride outside its range
+ * or a misaligned x; last_n, repeat, freq, present or n_bias outside the rule's ranges; last_n > 0
+ * with a null hist or end, n_hist < 1, n_hist > 0x7fffffff or hist_stride < n_hist; n_bias > 0
+ * with a null list. Then MI355X_E_NODEVICE. All statuses come before any device access. */
+#define MI355X_PENALTY_MAX_LAST_N 1024
+#define MI355X_LOGIT_BIAS_MAX 256
+struct mi355x_penalties { int32_t last_n; float repeat, freq, present; };
+int mi355x_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, const struct mi355x_penalties *p,
+                         const int32_t *hist, int64_t hist_stride, int64_t n_hist,
+                         const int32_t *end /* [rows], device */, const int32_t *bias_tok, const float *bias_val,
+                         int n_bias, void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -712,13 +755,24 @@ static inline double (mi355x_logprob_value)(const struct mi355x_logprob *r) {
  *                and targets[i] (LlamaDecoder.logprobs). One launch unit of two launches
  *                (kq_argmax_rows, kq_logsum_rows), never fused or elided; its workspace is the
  *                backend's ARGMAX buffer. Captured and replayed like any node: the targets are
- *                read on the device at run time. */
+ *                read on the device at run time.
+ *   PENALIZE     mi355x_penalize_rows in place on src0, the logits, f32 [n, T] with packed rows
+ *                (1 <= n <= 2^24, 1 <= T <= 65535), as ARGMAX_BATCH takes them (T 1 in the token
+ *                graph): data == src0->data, with src0's type, ne and nb. src1 I32 end [T] (the
+ *                graph's positions), src2 I32 history [n_hist, T] (nb[1] the row stride), src3 I32
+ *                bias_tok [n_bias], src4 F32 bias_val [n_bias]; src1 / src2 may be null at last_n 0,
+ *                src3 / src4 at n_bias 0. op_params = {last_n, the bits of repeat, freq, present,
+ *                n_bias}. One launch, never fused or elided, captured and replayed like any node:
+ *                end, the history and the lists are read on the device at run time. A SAMPLE /
+ *                SAMPLE_BATCH / ARGMAX* node that follows names the PENALIZE node as its src0 (the
+ *                same address; the stream gives the order). */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
     MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
     MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15, MI355X_OP_LOGPROB_BATCH = 16,
+    MI355X_OP_PENALIZE = 17,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */

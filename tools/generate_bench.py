@@ -29,6 +29,14 @@ and kq_topk's own launch time (event timing, behind the launch that wrote the ve
 128256 entries for the plain top-k (k 40) and the sampled token, next to kq_argmax on the same
 vector in the same run. Under a KQ_SAMPLE_DIAG variant library (make variant-sample) the same
 launch stops early, which splits its time: 1: no merge on the last arriver, 2: no sampling tail.
+
+--penalties: the penalties' leg, three timings in one session, rounds interleaved:
+  s  LlamaDecoder.generate(sampler=Sampler()): no edits, the node list without PENALIZE
+  p  the same with repeat_penalty 1.1 over the last 64 tokens (a PENALIZE node before the SAMPLE node)
+  h  the host-sampling loop of --sampler with the penalties' rule in numpy float32 before the top-k
+and kq_penalize_rows' own launch time (event timing, behind the launch that wrote the logits) at
+last_n 64 / 256 / 1024 and n_bias 0 / 256 for 1 x 32000, 1 x 128256 and 8 x 128256 logits (every
+window entry another token: the most owners), next to kq_topk on the same vector sizes in the same run.
 """
 import argparse
 import json
@@ -224,6 +232,103 @@ def sampler_leg(args, dev, be, tk):
     print(json.dumps(out))
 
 
+def host_penalize(x, win, sp):
+    """mi355x_penalize_rows' rule without a bias list on one row, in place, vectorized over the
+    window's distinct tokens (float32, one rounding per operation)."""
+    F = np.float32
+    w = np.asarray(win, dtype=np.int64)
+    t, c = np.unique(w[(w >= 0) & (w < x.size)], return_counts=True)
+    v = x[t]
+    v = np.where(v <= 0, v * F(sp.repeat_penalty), v / F(sp.repeat_penalty))
+    x[t] = v - (c.astype(F) * F(sp.freq_penalty) + F(sp.presence_penalty))
+    return x
+
+
+def host_penalized_loop(tk, be, tok, pos, n, sp, draws, hist):
+    from tests import sample_ref as R
+    for p in range(pos, pos + n):
+        tk.dec.step(tok, p)
+        be.synchronize()
+        hist[p] = tok
+        x = host_penalize(tk.dec.logits.cpu().numpy(), hist[max(0, p - sp.repeat_last_n + 1):p + 1], sp)
+        tok = R.chain(x, host_topk(x, sp.top_k), draws[p + 1], sp.top_p, sp.min_p, sp.temp, expf=np.exp)["token"]
+    return tok
+
+
+def penalize_launch_us(dev, n, rows, last_n, n_bias, reps=200):
+    """Median event time of the kq_penalize_rows launch on [rows, n] logits that an elementwise
+    launch writes just before; every window entry and every list entry names another token."""
+    gen = torch.Generator().manual_seed(n + rows + last_n + n_bias)
+    a, b = torch.randn((rows, n), device=dev) * 4, torch.randn((rows, n), device=dev) * 4
+    x = torch.empty((rows, n), device=dev)
+    n_hist = 2048
+    hist = torch.stack([torch.randperm(n, generator=gen)[:n_hist] for _ in range(rows)]).to(torch.int32).to(dev)
+    end = torch.full((rows,), n_hist - 1, dtype=torch.int32, device=dev)
+    bias = None
+    if n_bias:
+        bias = (torch.randperm(n, generator=gen)[:n_bias].to(torch.int32).to(dev), torch.randn(n_bias, device=dev))
+    torch.cuda.synchronize()
+
+    def fn():
+        g.add(a.view(-1), b.view(-1), out=x.view(-1))
+        g.penalize_rows(x, hist, end, last_n=last_n, repeat=1.1, bias=bias)
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    g.timing_enable(True)
+    for _ in range(reps):
+        fn()
+    rows_ = g.timing_read()
+    g.timing_enable(False)
+    ms = [r[2] for r in rows_ if "penalize" in r[0]]
+    assert len(ms) == reps
+    return {"us_p50": round(statistics.median(ms) * 1e3, 2), "us_min": round(min(ms) * 1e3, 2)}
+
+
+def penalties_leg(args, dev, be, tk):
+    from ggml_mi355x.llama import Sampler
+    s0, sp = Sampler(seed=1), Sampler(seed=1, repeat_penalty=1.1, repeat_last_n=64)
+    assert not s0.edits() and sp.edits()
+    draws = sp.draws(tk.dec.n_ctx + 1)
+
+    def run_gen(t, b, s):
+        t.dec.reset()
+        torch.cuda.synchronize()
+        toks = t.dec.generate(t.tokens[0], 0, WARM, sampler=s)
+        return timed(b, lambda: t.dec.generate(toks[-1], WARM, STEPS, chunk=args.chunk, sampler=s,
+                                               context=[t.tokens[0]] + toks[:-1]))
+
+    def run_h(t, b):
+        t.dec.reset()
+        torch.cuda.synchronize()
+        hist = [-1] * (t.dec.n_ctx + 1)
+        tok = host_penalized_loop(t, b, t.tokens[0], 0, WARM, sp, draws, hist)
+        return timed(b, lambda: host_penalized_loop(t, b, tok, WARM, STEPS, sp, draws, hist))
+
+    fns = {"s": lambda t, b: run_gen(t, b, s0), "p": lambda t, b: run_gen(t, b, sp), "h": run_h}
+    for fn in fns.values():  # capture + warm
+        fn(tk, be)
+    res = {v: [] for v in fns}
+    for _ in range(args.rounds):
+        for v, fn in fns.items():
+            res[v].append(fn(tk, be))
+    med = {v: statistics.median(x) for v, x in res.items()}
+    launch = {}
+    for rows, n in ((1, 32000), (1, 128256), (8, 128256)):
+        launch[f"{rows}x{n}"] = {f"last_n{ln}_bias{nb}": penalize_launch_us(dev, n, rows, ln, nb)
+                                 for ln in (64, 256, 1024) for nb in (0, 256)}
+    out = {"model": "tinyllama-1.1b", "leg": "penalties", "tokens": STEPS, "warmup": WARM, "rounds": args.rounds,
+           "chunk": args.chunk, "lib": os.path.relpath(g.LIB_PATH, ROOT),
+           "penalties": dict(repeat_penalty=sp.repeat_penalty, repeat_last_n=sp.repeat_last_n),
+           "ms_per_token": {v: [round(x, 4) for x in r] for v, r in res.items()},
+           "median_ms_per_token": {v: round(m, 4) for v, m in med.items()},
+           "p_minus_s_ms": round(med["p"] - med["s"], 4), "h_minus_p_ms": round(med["h"] - med["p"], 4),
+           "penalised_generate_below_host_loop_in_every_round": bool(max(res["p"]) < min(res["h"])),
+           "kq_penalize_rows_us": launch,
+           "kq_topk_us": {str(n): topk_launch_us(dev, n) for n in (32000, 128256)}}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -232,6 +337,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=32, help="generate's steps between two synchronizations")
     ap.add_argument("--sampler", action="store_true", help="the sampling leg: generate greedy / sampled / the host loop")
     ap.add_argument("--launch-only", action="store_true", help="with --sampler: only the launches alone (diag variants)")
+    ap.add_argument("--penalties", action="store_true", help="the penalties' leg: sampled generate without / with, the host loop")
     args = ap.parse_args()
     variants = args.variants.split(",")
     dev = torch.device("cuda:0")
@@ -241,8 +347,8 @@ def main():
         return
     be = g.Backend(0)
     tk = bench.Token("tinyllama-1.1b", dev, 0x51A7, be, 160)
-    if args.sampler:
-        sampler_leg(args, dev, be, tk)
+    if args.sampler or args.penalties:
+        (sampler_leg if args.sampler else penalties_leg)(args, dev, be, tk)
         be.close()
         return
     fns = {"a": run_a, "b": lambda t, b: run_b(t, b, args.chunk), "c": run_c}
