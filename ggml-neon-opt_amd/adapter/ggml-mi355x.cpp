@@ -321,12 +321,18 @@ bool cells_match_checked(Backend *ctx, const std::vector<ggml_tensor *> &nodes) 
 
 // The rope table the lowering's ROPE nodes are checked against: created on the backend
 // for the graph's (n_dims, freq_base, freq_scale) and at least as many positions as the
-// K cache has cells (every SET_ROWS destination's storage), kept while those hold.
+// K cache has cells (every SET_ROWS destination's storage, and the cache a K-shift graph's f16
+// ROPE rotates: such a graph may arrive before any decode graph), kept while those hold.
+const ggml_tensor *alias_root(const ggml_tensor *t);
 bool rope_table_for(Backend *ctx, const std::vector<ggml_tensor *> &nodes) {
     const ggml_tensor *rope = nullptr;
     int64_t cells = 0;
     for (const ggml_tensor *t : nodes) {
         if (!rope && is_op(t, "ROPE")) rope = t;
+        if (is_op(t, "ROPE") && t->src[0] && t->src[0]->type == GGML_TYPE_F16) {  // a K-shift: the cache it rotates
+            const ggml_tensor *root = alias_root(t->src[0]);
+            cells = root && root->ne[1] > cells ? root->ne[1] : cells;
+        }
         if (is_op(t, "SET_ROWS")) {
             const ggml_tensor *root = t;
             while (root->view_src) root = root->view_src;
@@ -476,6 +482,21 @@ bool attn_f16_mul_mat(const ggml_tensor *op) {
     return is_op(rb, "ROPE") || is_op(rb, "SOFT_MAX");
 }
 
+// The f16 ROPE the lowering takes is the K-shift graph's only (kq_lower.cpp kshift()): in place,
+// mode NORMAL, no freq factors, over a view [head_dim, n_head_kv, n_cells] from cell 0 of an f16
+// KV-cache leaf with contiguous rows of the cache's width, src1 an I32 tensor of ne[2] deltas.
+bool kshift_rope(const ggml_tensor *op) {
+    const ggml_tensor *a = op->src[0], *b = op->src[1];
+    if (!a || !b || op->src[2] || op->op_params[2] != 0 || op->type != GGML_TYPE_F16) return false;
+    if (!a->view_src || a->view_offs != 0 || op->data != a->data) return false;
+    const ggml_tensor *cache = alias_root(a);
+    if (!cache || !is_op(cache, "NONE") || cache->type != GGML_TYPE_F16) return false;
+    if (a->nb[0] != 2 || a->nb[1] != (size_t)a->ne[0] * 2 || a->nb[2] != cache->nb[1] || a->ne[3] != 1 ||
+        a->ne[0] * a->ne[1] != cache->ne[0] || cache->nb[1] != (size_t)cache->ne[0] * 2 || a->ne[2] > cache->ne[1])
+        return false;
+    return b->type == GGML_TYPE_I32 && ggml_nelements(b) == a->ne[2];
+}
+
 // What the lowering takes (mi355x_lower_ggml_graph): the scheduler places these nodes
 // here; a graph whose attention block is not the non-flash llm_build_llama pattern
 // fails in graph_compute (GGML_STATUS_FAILED), it is never computed wrongly.
@@ -516,6 +537,7 @@ bool dev_supports_op(ggml_backend_dev_t, const struct ggml_tensor *op) {
             return op->op_params[0] == GGML_GLU_OP_SWIGLU && op->op_params[1] == 0 && f32_rows(a) && f32_rows(b) &&
                    f32_rows(op);
         case MI355X_GOP_ROPE:
+            if (a && a->type == GGML_TYPE_F16) return kshift_rope(op);  // the K-shift graph's, and no other
             return op->op_params[2] == 0 && f32_rows(a) && b && b->type == GGML_TYPE_I32;  // mode NORMAL
         case MI355X_GOP_SET_ROWS:
             return op->type == GGML_TYPE_F16 && f32_rows(a) && b &&

@@ -27,6 +27,7 @@
 using kq::attn_batch_desc_of;
 using kq::attn_desc_of;
 using kq::rows_step_of;
+using kq::kv_shift_desc_of;
 using kq::penalties_of;
 using kq::sampler_of;
 using kq::token_step_of;
@@ -398,6 +399,11 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
                                             win ? hist->ne[0] : 0, win ? (const int32_t *)t->src[1]->data : nullptr,
                                             n_bias ? (const int32_t *)t->src[3]->data : nullptr,
                                             n_bias ? (const float *)t->src[4]->data : nullptr, n_bias, st);
+        }
+        case MI355X_OP_KV_SHIFT: {  // in place on the caches; the deltas read on the device
+            mi355x_kv_shift_desc d;
+            kv_shift_desc_of(t, d);
+            return kq::launch_kv_shift(&d, st);
         }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;

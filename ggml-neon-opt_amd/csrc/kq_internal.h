@@ -363,6 +363,11 @@ int launch_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, 
                          const int32_t *hist, int64_t hist_stride, int64_t n_hist, const int32_t *end,
                          const int32_t *bias_tok, const float *bias_val, int n_bias, hipStream_t stream);
 
+// ---------------------------------------------------------------- kq_kv_shift.hip
+// The context shift (include/ggml_mi355x.h, the rule): every check of mi355x_kv_shift, then one
+// launch of kq_kv_shift in the descriptor's form, or none for an empty range. No workspace.
+int launch_kv_shift(const mi355x_kv_shift_desc *d, hipStream_t stream);
+
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from
 // checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /

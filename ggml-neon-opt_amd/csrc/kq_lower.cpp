@@ -16,6 +16,9 @@
 //    adapter's cells_eq_pos promise), or one ATTN_BATCH node that also takes the K store's
 //    cell indices and the soft_max mask from the graph (cells_from_graph: several
 //    sequences in the cache, or cells that are not positions);
+//  * the K-shift graph's in-place ROPE over a view of the f16 K cache with an I32 delta per
+//    cell (build_rope_shift [U]) becomes one KV_SHIFT node in DELTAS form; any other f16 ROPE
+//    is refused, never dropped;
 //  * the [up, gate] MUL_MAT pair build_ffn emits before SWIGLU(gate, up) [U] is put in
 //    [gate, up] order (the two nodes are independent) so the gate/up launch fuses.
 // Anything else returns MI355X_E_UNSUPPORTED: the caller hands the graph to another
@@ -208,16 +211,8 @@ struct Lower {
             vcache->ne[1] != (int64_t)nkv * hd || vcache->ne[0] != kcache->ne[1])
             return false;
         if (!opts->rope_table || opts->rope_n_pos < kcache->ne[1]) return false;
-        mi355x_tensor *tab = alloc();
+        mi355x_tensor *tab = table_leaf(hd);
         if (!tab) return false;
-        tab->type = kTypeF32;
-        tab->ne[0] = hd;
-        tab->ne[1] = opts->rope_n_pos;
-        tab->ne[2] = tab->ne[3] = 1;
-        tab->nb[0] = 4;
-        tab->nb[1] = (size_t)hd * 4;
-        tab->nb[2] = tab->nb[3] = tab->nb[1] * (size_t)opts->rope_n_pos;
-        tab->data = opts->rope_table;
         mi355x_tensor *a;
         if (batch) {
             // the mask: an F16 / F32 leaf with a row of >= n_kv entries per token; n_kv: the
@@ -249,6 +244,58 @@ struct Lower {
         return true;
     }
 
+    // The caller's rope table as a leaf [hd, n_pos]
+    mi355x_tensor *table_leaf(int hd) {
+        mi355x_tensor *tab = alloc();
+        if (!tab) return nullptr;
+        tab->type = kTypeF32;
+        tab->ne[0] = hd;
+        tab->ne[1] = opts->rope_n_pos;
+        tab->ne[2] = tab->ne[3] = 1;
+        tab->nb[0] = 4;
+        tab->nb[1] = (size_t)hd * 4;
+        tab->nb[2] = tab->nb[3] = tab->nb[1] * (size_t)opts->rope_n_pos;
+        tab->data = opts->rope_table;
+        return tab;
+    }
+
+    // An F16 ROPE node `r`: llama.cpp's K-shift (build_rope_shift [U]: ggml_rope_ext_inplace over
+    // the view [hd, n_head_kv, n_cells] from cell 0 of an F16 K-cache leaf, an I32 leaf of one
+    // delta per cell) -> one KV_SHIFT node in DELTAS form over ne[2] cells, in place on the cache.
+    bool kshift(const mi355x_gtensor *r) {
+        const mi355x_gtensor *view = r->src[0], *kc = root(view), *dl = r->src[1];
+        if (!kc || kc->op != MI355X_GOP_NONE || kc->type != kTypeF16 || r->type != kTypeF16) return false;
+        if (!r->data || r->data != view->data || view->data != kc->data) return false;  // in place, from cell 0
+        const int64_t hd = r->ne[0], nkv = r->ne[1], n_cells = r->ne[2], kvw = kc->ne[0];
+        if ((hd != 64 && hd != 128) || !rope_ok(r, (int)hd)) return false;
+        if (hd * nkv != kvw || n_cells > kc->ne[1] || kc->ne[2] != 1 || kc->ne[3] != 1 || kc->nb[0] != 2 ||
+            kc->nb[1] != (size_t)kvw * 2)
+            return false;
+        for (const mi355x_gtensor *t : {r, view})  // contiguous rows of the cache's width
+            if (t->ne[0] != hd || t->ne[1] != nkv || t->ne[2] != n_cells || t->ne[3] != 1 || t->nb[0] != 2 ||
+                t->nb[1] != (size_t)hd * 2 || t->nb[2] != kc->nb[1])
+                return false;
+        if (!dl || dl->op != MI355X_GOP_NONE || dl->type != kTypeI32 || dl->ne[0] != n_cells || dl->ne[1] != 1 ||
+            dl->ne[2] != 1 || dl->ne[3] != 1)
+            return false;
+        if (!opts->rope_table || opts->rope_n_pos < kc->ne[1]) return false;
+        mi355x_tensor *k = leaf(kc), *tab = table_leaf((int)hd), *d = leaf(dl), *m = alloc();
+        if (!k || !tab || !d || !m) return false;
+        *m = *k;
+        m->op = MI355X_OP_KV_SHIFT;
+        m->src[0] = k;
+        m->src[2] = tab;
+        m->src[3] = d;
+        m->op_params[0] = (int32_t)nkv;
+        m->op_params[1] = (int32_t)hd;
+        m->op_params[2] = MI355X_KV_SHIFT_DELTAS;
+        m->op_params[3] = (int32_t)n_cells;
+        m->flags = r->flags & MI355X_TENSOR_FLAG_OUTPUT;
+        val[r] = m;
+        out.push_back(m);
+        return true;
+    }
+
     int run() {
         for (int i = 0; i < n; ++i) {  // reads through aliases count once, at the real reader
             if (is_alias(g[i]->op)) continue;
@@ -265,6 +312,9 @@ struct Lower {
                 case MI355X_GOP_TRANSPOSE:
                     break;  // aliases (and leaves listed among the nodes)
                 case MI355X_GOP_ROPE:
+                    // an F16 ROPE belongs to no attention block: the K-shift, or nothing this backend takes
+                    if (t->src[0] && t->src[0]->type == kTypeF16 && !kshift(t)) return err ? err : MI355X_E_UNSUPPORTED;
+                    break;
                 case MI355X_GOP_SET_ROWS:
                 case MI355X_GOP_SOFT_MAX:
                     break;  // members of an attention block, lowered at its CONT

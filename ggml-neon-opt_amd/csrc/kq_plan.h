@@ -64,6 +64,7 @@ void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a);  // rope_row lef
 void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d);
 void sampler_of(const mi355x_tensor *t, mi355x_sampler &s);  // SAMPLE / SAMPLE_BATCH: op_params[1 .. 4]
 int penalties_of(const mi355x_tensor *t, mi355x_penalties &p);  // PENALIZE: op_params[0 .. 3]; returns n_bias ([4])
+void kv_shift_desc_of(const mi355x_tensor *t, mi355x_kv_shift_desc &d);  // KV_SHIFT: its sources and op_params
 // the step-inputs forms' operands: ARGMAX / SAMPLE (pos, rope table, history: src1 .. 3), and
 // ARGMAX_BATCH / SAMPLE_BATCH (pos, cells, mask, history: src1 .. 4; cell_stride and n_kv at
 // op_params[first_param], [first_param + 1])

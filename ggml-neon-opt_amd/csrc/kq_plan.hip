@@ -258,6 +258,28 @@ int penalties_of(const mi355x_tensor *t, mi355x_penalties &p) {
     return t->op_params[4];
 }
 
+// KV_SHIFT: src0 .. src3 = K cache, V cache, rope table, deltas; op_params = {n_head_kv, head_dim,
+// form, n_cells} (DELTAS) or {n_head_kv, head_dim, form, keep, discard, n_past} (DISCARD)
+void kv_shift_desc_of(const mi355x_tensor *t, mi355x_kv_shift_desc &d) {
+    memset(&d, 0, sizeof(d));
+    d.k_cache = (uint16_t *)t->src[0]->data;
+    d.v_cache = t->src[1] ? (uint16_t *)t->src[1]->data : nullptr;
+    d.rope_table = (const float *)t->src[2]->data;
+    d.delta = t->src[3] ? (const int32_t *)t->src[3]->data : nullptr;
+    d.n_ctx = (int)t->src[0]->ne[1];
+    d.n_head_kv = t->op_params[0];
+    d.head_dim = t->op_params[1];
+    d.n_pos = (int)t->src[2]->ne[1];
+    d.form = t->op_params[2];
+    if (d.form == MI355X_KV_SHIFT_DELTAS) {
+        d.n_cells = t->op_params[3];
+    } else {
+        d.keep = t->op_params[3];
+        d.discard = t->op_params[4];
+        d.n_past = t->op_params[5];
+    }
+}
+
 ArgmaxStep token_step_of(const mi355x_tensor *t) {
     const mi355x_tensor *tab = t->src[2], *hist = t->src[3];
     return {(const int32_t *)t->src[1]->data, (const float *)tab->data, (int32_t *)hist->data, tab->ne[1], hist->ne[0],
@@ -776,6 +798,36 @@ bool supports_op(const mi355x_tensor *op) {
                 if (!list(bt, MI355X_TYPE_I32) || !list(bv, MI355X_TYPE_F32)) return false;
             }
             return true;
+        }
+        case MI355X_OP_KV_SHIFT: {
+            // in place on src0, the K cache F16 [kvw, n_ctx], packed rows, 16-B aligned; the V cache F16
+            // [n_ctx, kvw] (DISCARD; optional in DELTAS); the table f32 [hd, n_pos]; I32 deltas [n_cells]
+            // (DELTAS); the parameters in mi355x_kv_shift's ranges
+            const mi355x_tensor *kc = op->src[0], *vc = op->src[1], *tab = op->src[2], *dl = op->src[3];
+            const int nkv = op->op_params[0], hd = op->op_params[1], form = op->op_params[2];
+            if ((hd != 64 && hd != 128) || nkv < 1 || (int64_t)nkv * hd > 0x7fffffff) return false;
+            if (!kc || kc->type != MI355X_TYPE_F16 || !kc->data || ((uintptr_t)kc->data & 15u)) return false;
+            const int64_t kvw = (int64_t)nkv * hd, n_ctx = kc->ne[1];
+            if (kc->ne[0] != kvw || n_ctx < 1 || n_ctx > 0x7fffffff || nelem(kc) != kvw * n_ctx || kc->nb[0] != 2 ||
+                kc->nb[1] != (size_t)kvw * 2)
+                return false;
+            if (op->data != kc->data || op->type != kc->type || memcmp(op->ne, kc->ne, sizeof(op->ne)) ||
+                memcmp(op->nb, kc->nb, sizeof(op->nb)))
+                return false;
+            if (!contig_f32(tab) || ((uintptr_t)tab->data & 15u) || tab->ne[0] != hd || tab->ne[1] < 1 ||
+                tab->ne[1] > 0x7fffffff || nelem(tab) != tab->ne[0] * tab->ne[1] || tab->nb[1] != (size_t)hd * 4)
+                return false;
+            if (vc && (vc->type != MI355X_TYPE_F16 || !vc->data || vc->ne[0] != n_ctx || vc->ne[1] != kvw ||
+                       nelem(vc) != kvw * n_ctx || vc->nb[0] != 2 || vc->nb[1] != (size_t)n_ctx * 2))
+                return false;
+            if (form == MI355X_KV_SHIFT_DELTAS) {
+                const int n_cells = op->op_params[3];
+                return n_cells >= 0 && n_cells <= n_ctx && dl && dl->type == MI355X_TYPE_I32 && dl->data &&
+                       !((uintptr_t)dl->data & 3u) && dl->nb[0] == 4 && dl->ne[0] == n_cells && nelem(dl) == n_cells;
+            }
+            if (form != MI355X_KV_SHIFT_DISCARD || !vc || dl) return false;
+            const int64_t keep = op->op_params[3], discard = op->op_params[4], n_past = op->op_params[5];
+            return keep >= 0 && discard >= 1 && keep + discard <= n_past && n_past <= n_ctx && discard < tab->ne[1];
         }
         default:
             return false;

@@ -40,6 +40,10 @@ LOGPROB_MAX_N = 262144
 # [n_bias]; op_params: penalize_params(...)
 OP_PENALIZE = 17
 PENALTY_MAX_LAST_N, LOGIT_BIAS_MAX = 1024, 256
+# in place on src0, the K cache F16 [kvw, n_ctx]; src1 the V cache F16 [n_ctx, kvw] (DISCARD), src2 the rope table
+# [head_dim, n_pos], src3 I32 deltas [n_cells] (DELTAS); op_params: kv_shift_params(...)
+OP_KV_SHIFT = 18
+KV_SHIFT_DELTAS, KV_SHIFT_DISCARD = 0, 1
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -89,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_topk_workspace_size", "mi355x_topk", "mi355x_topk_rows", "mi355x_sample", "mi355x_sample_rows",
     "mi355x_logprob_workspace_size", "mi355x_logprob_rows",
     "mi355x_penalize_rows",
+    "mi355x_kv_shift",
 )
 
 
@@ -106,6 +111,14 @@ class PenaltiesDesc(ctypes.Structure):
     """struct mi355x_penalties"""
     _fields_ = [("last_n", ctypes.c_int32), ("repeat", ctypes.c_float), ("freq", ctypes.c_float),
                 ("present", ctypes.c_float)]
+
+
+class KvShiftDesc(ctypes.Structure):
+    """mi355x_kv_shift_desc"""
+    _fields_ = [("k_cache", ctypes.c_void_p), ("v_cache", ctypes.c_void_p), ("rope_table", ctypes.c_void_p),
+                ("delta", ctypes.c_void_p), ("n_ctx", ctypes.c_int), ("n_head_kv", ctypes.c_int),
+                ("head_dim", ctypes.c_int), ("n_pos", ctypes.c_int), ("form", ctypes.c_int), ("n_cells", ctypes.c_int),
+                ("keep", ctypes.c_int), ("discard", ctypes.c_int), ("n_past", ctypes.c_int)]
 
 
 class GemvDesc(ctypes.Structure):
@@ -311,6 +324,9 @@ def lib():
         L.mi355x_penalize_rows.argtypes = [vp, i64, i64, i64, ctypes.POINTER(PenaltiesDesc), vp, i64, i64, vp, vp, vp, i32,
                                            vp]
         L.mi355x_penalize_rows.restype = i32
+    if hasattr(L, "mi355x_kv_shift"):
+        L.mi355x_kv_shift.argtypes = [ctypes.POINTER(KvShiftDesc), vp]
+        L.mi355x_kv_shift.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
@@ -1075,6 +1091,57 @@ def penalize_rows(x, hist=None, end=None, last_n=0, repeat=1.0, freq=0.0, presen
     if copied and stream is not None:
         torch.cuda.synchronize()  # the copies made here are read on `stream`: they stay until it is done
     return x
+
+
+def kv_shift_params(n_head_kv, head_dim, n_cells=None, keep=None, discard=None, n_past=None):
+    """The KV_SHIFT node's op_params: the DELTAS form over n_cells cells, or the DISCARD form."""
+    if n_cells is not None:
+        return [n_head_kv, head_dim, KV_SHIFT_DELTAS, n_cells]
+    return [n_head_kv, head_dim, KV_SHIFT_DISCARD, keep, discard, n_past]
+
+
+def kv_shift(k_cache, table, n_head_kv, head_dim, v_cache=None, delta=None, n_cells=None, keep=None, discard=None,
+             n_past=None, stream=None):
+    """mi355x_kv_shift: the context shift in place on the caches (the exact rule is in
+    include/ggml_mi355x.h); no synchronization. k_cache: a contiguous 2-byte cuda tensor
+    [n_ctx, n_head_kv * head_dim] (f16 bits); table: rope_table(n_pos, head_dim). With `delta`, an
+    int32 cuda tensor, the DELTAS form: K cell c in [0, n_cells) (default: every delta) is re-roped
+    by delta[c]; V is not touched. Otherwise the DISCARD form: cells [keep, keep + discard) are
+    dropped and the cells up to n_past slide down over them, K re-roped by -discard, V (v_cache, a
+    contiguous 2-byte cuda tensor [n_head_kv * head_dim, n_ctx]) moved."""
+    torch = _torch()
+    _require_device()
+    kvw = n_head_kv * head_dim
+
+    def cache(name, x, shape1):
+        if not (torch.is_tensor(x) and x.is_cuda and x.element_size() == 2 and x.dim() == 2 and x.is_contiguous() and
+                x.shape[1] == shape1):
+            raise Mi355xError(f"kv_shift: {name} must be a contiguous 2-byte cuda tensor [*, {shape1}]")
+        return x.shape[0]
+
+    n_ctx = cache("k_cache", k_cache, kvw)
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and
+            table.numel() >= head_dim and table.numel() % head_dim == 0):
+        raise Mi355xError("kv_shift: table must be a contiguous float32 cuda tensor of whole rope rows")
+    d = KvShiftDesc(k_cache.data_ptr(), None, table.data_ptr(), None, n_ctx, n_head_kv, head_dim,
+                    table.numel() // head_dim, KV_SHIFT_DELTAS, 0, 0, 0, 0)
+    if v_cache is not None:
+        if cache("v_cache", v_cache, n_ctx) != kvw:
+            raise Mi355xError(f"kv_shift: v_cache must have {kvw} rows")
+        d.v_cache = v_cache.data_ptr()
+    if delta is not None:
+        if not (torch.is_tensor(delta) and delta.is_cuda and delta.dtype == torch.int32 and delta.dim() == 1 and
+                delta.is_contiguous()):
+            raise Mi355xError("kv_shift: delta must be a contiguous int32 cuda vector")
+        d.delta = delta.data_ptr()
+        d.n_cells = delta.numel() if n_cells is None else n_cells
+        if d.n_cells > delta.numel():
+            raise Mi355xError("kv_shift: n_cells exceeds the deltas")
+    else:
+        if v_cache is None or keep is None or discard is None or n_past is None:
+            raise Mi355xError("kv_shift: the DISCARD form needs v_cache, keep, discard and n_past")
+        d.form, d.keep, d.discard, d.n_past = KV_SHIFT_DISCARD, keep, discard, n_past
+    _check(_lib_with("mi355x_kv_shift").mi355x_kv_shift(ctypes.byref(d), _stream(stream)), "mi355x_kv_shift")
 
 
 def block_partials(type_, w, K, q8_row, stream=None):

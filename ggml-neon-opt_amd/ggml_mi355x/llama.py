@@ -29,6 +29,8 @@ layer body and the one head below (LlamaDecoder._layers, ._head) over a _Graph:
                   node is a SAMPLE / SAMPLE_BATCH, which reads its draws from a device table; with
                   a Sampler that edits the logits (penalties, logit bias) a PENALIZE node stands
                   between the logits and that node and reads the history the steps write
+  shift           one KV_SHIFT node a layer (DISCARD form) over the caches: llama.cpp's context
+                  shift, which generate(keep=) runs whenever the cache is full
   logprobs,       _prompt_graph(n_tok, all_rows=True): the prompt's layers with no row selection,
   perplexity      the head over all n_tok rows and one LOGPROB_BATCH node on the logits and the
                   targets: 24 bytes a token come back, not a row of the vocabulary
@@ -38,10 +40,11 @@ from __future__ import annotations
 import ctypes
 
 from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, LOGIT_BIAS_MAX, LOGPROB_MAX_N, OP_ADD, OP_ALL_GATHER,
-               OP_ALL_REDUCE, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_LOGPROB_BATCH,
-               OP_MUL, OP_MUL_MAT, OP_PENALIZE, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, PENALTY_MAX_LAST_N,
-               QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, bias_pairs,
-               f32_bits, logprob_dtype, logprob_value, make_tensor, penalize_params, rope_table, sampler_params)
+               OP_ALL_REDUCE, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_KV_SHIFT,
+               OP_LOGPROB_BATCH, OP_MUL, OP_MUL_MAT, OP_PENALIZE, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU,
+               PENALTY_MAX_LAST_N, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32, TYPE_I32, Backend,
+               Mi355xError, bias_pairs, f32_bits, kv_shift_params, logprob_dtype, logprob_value, make_tensor,
+               penalize_params, rope_table, sampler_params)
 
 
 def torch_tensor(values):
@@ -93,7 +96,10 @@ class Sampler:
     its defaults [U] (the exact rule: include/ggml_mi355x.h, mi355x_sample). seed: the draws of
     generate / generate_batch are numpy's PCG64(seed) float32 stream (sequence i of a batch:
     PCG64([seed, i])), entry p the draw of the token that will stand at position p, so the same
-    seed and context give the same tokens whatever chunk, n or use_graph is.
+    seed and context give the same tokens whatever chunk, n or use_graph is. A generate(keep=)
+    call that shifts the context refills the table after its e-th shift (e >= 1) with the draws of
+    epoch e, PCG64([seed, 0, e]), so the positions that repeat after a shift get fresh draws;
+    epoch 0 is PCG64(seed).
     Before the chain the logits can be edited on the device (mi355x_penalize_rows' rule; llama.cpp's
     logit-bias and penalties samplers [U], in its order: the bias, then the penalties, then top-k):
     repeat_penalty, freq_penalty and presence_penalty over the last repeat_last_n tokens (defaults:
@@ -146,9 +152,11 @@ class Sampler:
         """The SAMPLE nodes' leading op_params (the graphs are cached by them: the seed is not part)."""
         return sampler_params(form, self.top_k, self.temp, self.top_p, self.min_p)
 
-    def draws(self, n, row=None):
+    def draws(self, n, row=None, epoch=0):
         import numpy as np
         seed = self.seed if row is None else [self.seed, row]
+        if epoch:  # after the epoch-th context shift of a generate call
+            seed = [self.seed, 0 if row is None else row, epoch]
         return np.random.Generator(np.random.PCG64(seed)).random(n, dtype=np.float32)
 
 
@@ -234,6 +242,7 @@ class LlamaDecoder:
         self.reduces = []  # (input partial, output) buffers of every ALL_REDUCE (split mode "reduce")
         self._prompts, self._batches, self._gen_batches, self._batch_hists, self._gen = {}, {}, {}, {}, None
         self._gen_sampled, self._draws, self._batch_draws, self.history, self._bias = {}, None, {}, None, None
+        self._shifts = {}  # (n_past, keep, discard) -> the KV_SHIFT node list of shift()
         # inp_tokens, inp_pos and the rope row of that position side by side: one
         # set_tensor of 8 + 4*head_dim bytes per token. The attention reads its cos/sin
         # with q/k/v instead of after the position (one dependent round trip less);
@@ -618,20 +627,22 @@ class LlamaDecoder:
                                                            device=self.inp.device), seed=None)
         return self._batch_draws[rows]
 
-    def _seed(self, sampler, rows=None):
+    def _seed(self, sampler, rows=None, epoch=0):
         """Fills the draws table for sampler.seed unless it holds that seed's draws already: the
-        backend is synchronized first (a run may still read the table), torch's stream after."""
+        backend is synchronized first (a run may still read the table), torch's stream after.
+        epoch >= 1 (the token graph's table): the draws after that many context shifts."""
         import numpy as np
         import torch
         d = self._draws_table(rows)
-        if d["seed"] is not None and d["seed"] == (sampler.seed,):
+        held = (sampler.seed,) if epoch == 0 else (sampler.seed, epoch)
+        if d["seed"] is not None and d["seed"] == held:
             return
         n = self.n_ctx + 1
-        host = sampler.draws(n) if rows is None else np.stack([sampler.draws(n, i) for i in range(rows)])
+        host = sampler.draws(n, epoch=epoch) if rows is None else np.stack([sampler.draws(n, i) for i in range(rows)])
         self.b.synchronize()
         d["dev"].copy_(torch.from_numpy(host))
         torch.cuda.synchronize()
-        d["seed"] = (sampler.seed,)
+        d["seed"] = held
 
     # ------------------------------------------------------------ the samplers' edits of the logits
     def _bias_lists(self):
@@ -893,7 +904,7 @@ class LlamaDecoder:
         return g
 
     def generate(self, token: int, pos: int, n: int, eos=None, chunk: int = 32, use_graph: bool = True, sampler=None,
-                 context=None):
+                 context=None, keep=None, discard=None):
         """Greedy decoding of n tokens at positions pos .. pos + n - 1, starting from `token` at
         `pos`: returns the generated tokens as a list of ints (the token picked after position p
         is the argmax of that step's logits, mi355x_argmax's rule). The inputs are staged from the
@@ -913,13 +924,32 @@ class LlamaDecoder:
         with one copy: the context's tail, -1 where the context does not reach, `token` at pos.
         Without such a sampler context is ignored and the history below pos + 1 is not written.
         Under an editing sampler the logits buffer holds the edited logits after a step (llama.cpp
-        edits a copy; here a copy would cost another pass over the row)."""
+        edits a copy; here a copy would cost another pass over the row).
+        keep: None: n tokens must fit the cache from pos. An integer in [0, n_ctx - 1): generation
+        goes on past the end of the cache by llama.cpp's context shift [U]: the chunks are cut so
+        that one ends with the step on cell n_ctx - 1; then, the host being synchronized for that
+        chunk, shift(n_ctx, keep, d) drops the cells [keep, keep + d), d = discard or
+        (n_ctx - keep) // 2 (llama.cpp main's n_left / 2), the history moves with the cells, the
+        inputs are restaged with the last token at position n_ctx - d, and the steps go on. Under a
+        sampler the draws after the e-th shift of the call are those of epoch e (Sampler).
+        discard: an integer in [1, n_ctx - keep]; it needs keep."""
         if self.split is not None:
             raise Mi355xError("generate runs on one GPU (no row split)")
         if n < 0 or chunk < 1:
             raise Mi355xError(f"generate: n {n} and chunk {chunk} must be >= 0 and >= 1")
-        if not 0 <= pos < self.n_ctx or n > self.n_ctx - pos:
-            raise Mi355xError(f"generate: {n} tokens from position {pos} outside the KV cache (n_ctx {self.n_ctx})")
+        n_ctx = self.n_ctx
+        if keep is None:
+            if discard is not None:
+                raise Mi355xError("generate: discard needs keep")
+            if not 0 <= pos < n_ctx or n > n_ctx - pos:
+                raise Mi355xError(f"generate: {n} tokens from position {pos} outside the KV cache (n_ctx {n_ctx})")
+        else:
+            if not 0 <= pos < n_ctx:
+                raise Mi355xError(f"generate: position {pos} outside the KV cache (n_ctx {n_ctx})")
+            if not 0 <= keep < n_ctx - 1 or keep != int(keep):
+                raise Mi355xError(f"generate: keep {keep} must be an integer in [0, n_ctx - 1 = {n_ctx - 1})")
+            if discard is not None and (not 1 <= discard <= n_ctx - keep or discard != int(discard)):
+                raise Mi355xError(f"generate: discard {discard} must be an integer in [1, n_ctx - keep = {n_ctx - keep}]")
         if n == 0:
             return []
         edits = sampler is not None and sampler.edits()
@@ -931,21 +961,21 @@ class LlamaDecoder:
         if edits:
             self._set_bias(sampler)
         L = self._stage_inputs(token, pos)
-        host, out, done = g["host"], [], 0
+        host, out, done, epoch = g["host"], [], 0, 0
         if edits:
             self._stage_history(L, host, self.history, token, pos, ctx, sampler.repeat_last_n)
         while done < n:
-            c = min(chunk, n - done)
+            c = min(chunk, n - done, n_ctx - pos)  # (a chunk ends with the step on the last cell)
             self._run(L, g, use_graph, times=c)
             # the chunk's tokens: history[p + 1] for the step at p; the step on the last cell has
             # no history entry, its token is the input block's
-            lo, hi = pos + done + 1, pos + done + c + 1
-            in_hist = min(hi, self.n_ctx) - lo
+            lo, hi = pos + 1, pos + c + 1
+            in_hist = min(hi, n_ctx) - lo
             if in_hist > 0:
                 _check(L.mi355x_backend_get_tensor(self.b.h, host[lo:].data_ptr(), self.history[lo:].data_ptr(),
                                                    4 * in_hist), "get_tensor")
-            if hi > self.n_ctx:
-                _check(L.mi355x_backend_get_tensor(self.b.h, host[self.n_ctx:].data_ptr(), self.inp.data_ptr(), 4),
+            if hi > n_ctx:
+                _check(L.mi355x_backend_get_tensor(self.b.h, host[n_ctx:].data_ptr(), self.inp.data_ptr(), 4),
                        "get_tensor")
             self.b.synchronize()
             for t in host[lo:hi].tolist():
@@ -953,4 +983,63 @@ class LlamaDecoder:
                 if eos is not None and t == eos:
                     return out
             done += c
+            pos += c
+            if done < n and pos == n_ctx:  # the cache is full (keep is set: n fits it otherwise)
+                epoch += 1
+                pos = self._shift_context(L, g, out[-1], keep, discard or (n_ctx - keep) // 2, use_graph)
+                if sampler is not None:
+                    self._seed(sampler, epoch=epoch)
+                L = self._stage_inputs(out[-1], pos)
         return out
+
+    # ------------------------------------------------------------ context shift
+    def shift(self, n_past: int, keep: int, discard: int, use_graph: bool = True):
+        """llama.cpp's context shift on every layer's caches (mi355x_kv_shift's DISCARD form): the
+        cells [keep, keep + discard) are dropped, the cells up to n_past slide down over them and
+        their K rows are re-roped by -discard, so the sequence goes on at position
+        n_past - discard. One KV_SHIFT node a layer over the decoder's own caches and table,
+        enqueued without synchronization; the node list is built once per (n_past, keep, discard).
+        self.history, the draws and the input block are not touched."""
+        if self.split is not None:
+            raise Mi355xError("shift runs on one GPU (no row split)")
+        if not (0 <= keep and 1 <= discard and keep + discard <= n_past <= self.n_ctx):
+            raise Mi355xError(f"shift: keep {keep} >= 0, discard {discard} >= 1 and keep + discard <= n_past {n_past} <= "
+                              f"n_ctx {self.n_ctx} are required")
+        if keep + discard == n_past:
+            return  # no cell moves
+        key = (n_past, keep, discard)
+        g = self._shifts.get(key)
+        if g is None:
+            hd, n_ctx = self.hp["head_dim"], self.n_ctx
+            kvw = self.k_cache[0].shape[1]
+            tab = make_tensor(TYPE_F32, hd, n_ctx, self.table.data_ptr())
+            keep_alive, nodes = [tab], []
+            for k, v in zip(self.k_cache, self.v_cache):
+                kt = make_tensor(TYPE_F16, kvw, n_ctx, k.data_ptr())
+                vt = make_tensor(TYPE_F16, n_ctx, kvw, v.data_ptr())
+                nodes.append(make_tensor(TYPE_F16, kvw, n_ctx, k.data_ptr(), op=OP_KV_SHIFT, srcs=[kt, vt, tab],
+                                         op_params=kv_shift_params(kvw // hd, hd, keep=keep, discard=discard,
+                                                                   n_past=n_past)))
+                keep_alive += [kt, vt]
+            g = self._shifts[key] = dict(nodes=nodes, keep=keep_alive, arr=_node_array(nodes))
+        if self.b is None:  # (describe only: no device work)
+            return
+        from . import lib
+        self._run(lib(), g, use_graph)
+
+    def _shift_context(self, L, g, last: int, keep: int, d: int, use_graph: bool) -> int:
+        """generate's step at a full cache (the host is synchronized): shift(n_ctx, keep, d), and the
+        history follows the cells: the tokens of positions [keep + d, n_ctx) move down by d and
+        `last`, the token picked on the last cell, stands at the new position n_ctx - d, which is
+        returned. So the penalty window goes on reading the tokens that stand before the position."""
+        n_ctx = self.n_ctx
+        self.shift(n_ctx, keep, d, use_graph)
+        host, new = g["host"], n_ctx - d
+        if new > keep:
+            _check(L.mi355x_backend_get_tensor(self.b.h, host[keep:].data_ptr(), self.history[keep + d:].data_ptr(),
+                                               4 * (new - keep)), "get_tensor")
+            self.b.synchronize()
+        host[new] = last
+        _check(L.mi355x_backend_set_tensor(self.b.h, self.history[keep:].data_ptr(), host[keep:].data_ptr(),
+                                           4 * (new - keep + 1)), "set_tensor")
+        return new

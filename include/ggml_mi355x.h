@@ -664,6 +664,53 @@ int mi355x_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, 
                          const int32_t *end /* [rows], device */, const int32_t *bias_tok, const float *bias_val,
                          int n_bias, void *stream);
 
+/* Context shift on the device: a full KV cache makes room without a new prefill (llama.cpp's
+ * llama_memory_seq_rm + llama_memory_seq_add and its K-shift graph, build_rope_shift: a
+ * ggml_rope_ext_inplace over the f16 K cache with an I32 delta per cell [U]). One launch of
+ * kq_kv_shift (csrc/kq_kv_shift.hip): no atomics, no workgroup waits for another, no workspace.
+ * The rule (exact: the same bits as tests/kv_shift_ref.py). A cached K element pair (k0, k1), the
+ * f16 bits at channels 2i, 2i + 1 of a KV head, shifted by an integer delta:
+ *     x0 = f32(k0); x1 = f32(k1)
+ *     (c, s) = rope_table[|delta|][i]      the caller's mi355x_rope_table row, cos then sin
+ *     if delta < 0: s = -s
+ *     k0' = f16_rne(fmaf(x0, c, -(x1 * s)))
+ *     k1' = f16_rne(fmaf(x0, s, x1 * c))
+ *   every operation rounded once: what ggml_compute_forward_rope_f16 does with the cos/sin cache
+ *   of position delta [U]. delta == 0 leaves the cell untouched: it is not rewritten (ggml
+ *   rewrites it with cos 1, sin 0, which differs only for a non-finite cached value: a NaN's
+ *   payload, or inf * 0). |delta| >= n_pos (the table's rows) writes NaN bits (0x7e00) to every
+ *   element of the cell's K row, as mi355x_rope does: never a silent result (the deltas live on
+ *   the device and cannot be checked on the host).
+ * MI355X_KV_SHIFT_DELTAS (ggml's K-shift): every K cell c in [0, n_cells) is shifted in place by
+ *   delta[c], a device int32 read at run time. V is not touched (v_cache may be NULL). A cell's
+ *   delta is loaded together with its K row, so a delta-0 cell is read and never written.
+ * MI355X_KV_SHIFT_DISCARD (a cache whose cell is its position, LlamaDecoder): the cells
+ *   [keep, keep + discard) are dropped and the cells up to n_past slide down over them: for c in
+ *   [keep, n_past - discard), K cell c becomes K cell c + discard shifted by -discard and V cell c
+ *   becomes V cell c + discard (a slide along each channel's row of the transposed cache). Cells
+ *   below keep and cells at or above n_past - discard keep their bits (the causal attention never
+ *   reads past the position). Source and destination overlap; every workgroup owns channels, not
+ *   cells, and loads a chunk of cells before it stores it, so none reads what another writes.
+ * head_dim 64 or 128 (else MI355X_E_UNSUPPORTED); f16 caches, k_cache and rope_table 16-B aligned.
+ * Returns MI355X_E_INVAL for a null descriptor, an unknown form, a null k_cache or rope_table, a
+ * null delta (DELTAS) or v_cache (DISCARD), a misaligned pointer, n_ctx, n_head_kv, n_pos or
+ * head_dim < 1, n_cells outside [0, n_ctx], keep < 0, discard < 1, keep + discard > n_past,
+ * n_past > n_ctx or discard >= n_pos; then MI355X_E_UNSUPPORTED; n_cells == 0 or an empty moved
+ * range returns MI355X_OK with no launch; then MI355X_E_NODEVICE. All before any device access. */
+#define MI355X_KV_SHIFT_DELTAS 0
+#define MI355X_KV_SHIFT_DISCARD 1
+typedef struct {
+    uint16_t *k_cache;          /* f16 [n_ctx][n_head_kv*head_dim] */
+    uint16_t *v_cache;          /* f16 [n_head_kv*head_dim][n_ctx]; may be NULL in the DELTAS form */
+    const float *rope_table;    /* mi355x_rope_table(n_pos, head_dim) */
+    const int32_t *delta;       /* DELTAS form: device int32 [n_cells]; else NULL */
+    int n_ctx, n_head_kv, head_dim, n_pos;
+    int form;                   /* MI355X_KV_SHIFT_DELTAS 0 / MI355X_KV_SHIFT_DISCARD 1 */
+    int n_cells;                /* DELTAS: cells [0, n_cells) */
+    int keep, discard, n_past;  /* DISCARD */
+} mi355x_kv_shift_desc;
+int mi355x_kv_shift(const mi355x_kv_shift_desc *d, void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -765,14 +812,23 @@ int mi355x_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, 
  *                n_bias}. One launch, never fused or elided, captured and replayed like any node:
  *                end, the history and the lists are read on the device at run time. A SAMPLE /
  *                SAMPLE_BATCH / ARGMAX* node that follows names the PENALIZE node as its src0 (the
- *                same address; the stream gives the order). */
+ *                same address; the stream gives the order).
+ *   KV_SHIFT     mi355x_kv_shift in place on src0, the K cache, F16 [kvw, n_ctx] with packed rows,
+ *                16-B aligned: data == src0->data, with src0's type, ne and nb. src1 the V cache,
+ *                F16 [n_ctx, kvw] (transposed), or null in the DELTAS form; src2 the rope table
+ *                [head_dim, n_pos]; src3 I32 deltas [n_cells], DELTAS form only. op_params =
+ *                {n_head_kv, head_dim, form, n_cells} (DELTAS) or {n_head_kv, head_dim, form, keep,
+ *                discard, n_past} (DISCARD), with mi355x_kv_shift's ranges; any n_ctx >= 1. Launches
+ *                of its own in graph order (none for an empty range), never fused, elided or moved
+ *                across an attention node on the same caches; captured and replayed like any node
+ *                (every replay shifts again): the deltas are read on the device at run time. */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
     MI355X_OP_ATTN_DECODE = 8, MI355X_OP_ALL_GATHER = 9, MI355X_OP_ALL_REDUCE = 10,
     MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
     MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15, MI355X_OP_LOGPROB_BATCH = 16,
-    MI355X_OP_PENALIZE = 17,
+    MI355X_OP_PENALIZE = 17, MI355X_OP_KV_SHIFT = 18,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */
@@ -872,6 +928,11 @@ int mi355x_backend_graph_compute(mi355x_backend_t backend, mi355x_tensor *const 
  *   (V cache), MUL_MAT(K cache, Q), SOFT_MAX(kq, mask, scale), MUL_MAT(V cache, kq),
  *   PERMUTE, CONT — becomes ONE ATTN_DECODE node (rope table from the caller), or ONE
  *   ATTN_BATCH node under mi355x_lower_opts.cells_from_graph;
+ *   llama.cpp's K-shift graph (build_rope_shift [U]) — per layer an in-place ROPE over a view
+ *   [head_dim, n_head_kv, n_cells] from cell 0 of an F16 K-cache leaf, with an I32 leaf of one
+ *   delta per cell, mode NORMAL, n_dims == head_dim, the table's base and scale, no freq
+ *   factors — becomes ONE KV_SHIFT node in DELTAS form over ne[2] cells; any other F16 ROPE is
+ *   MI355X_E_UNSUPPORTED, never dropped;
  *   [up, gate] MUL_MAT pairs read by SWIGLU(gate, up) are emitted as [gate, up]
  *   (independent nodes; the order the fused gate/up launch takes).
  * The op numbering is this library's (the adapter maps GGML_OP_* by name). */
