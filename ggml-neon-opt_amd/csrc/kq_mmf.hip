@@ -11,11 +11,28 @@
 //           + sum_g A'_g(r) * f16(yd * bsum16_g)                               (per group)
 // with dsc_g = f16(d * sc_g), A' = -f16(dmin * m_j) (Q4_K/Q5_K mins, one per 16-element
 // half of sub-block j) or -32 * dsc_g (Q6_K's q - 32 offset). Every weight operand is one
-// rounding of an exact product (v_pk_fma_f16 of the magic-exponent quant 1024 + q with
-// dsc and the exact -1024 * dsc), every activation operand one rounding of the reference's
-// own d * q. Tolerance (tests/test_gpu_mmf.py): |y - y_ref| <= 2^-8 * sum_k |w_k| |x^_k|
+// rounding of an exact product (the magic-exponent quant 1024 + q minus 1024 is q exactly,
+// v_pk_add_f16; times dsc, v_pk_mul_f16), every activation operand one rounding of the
+// reference's own d * q. Tolerance (tests/test_gpu_mmf.py): |y - y_ref| <= 2^-8 * sum_k |w_k| |x^_k|
 // + 2^-24 * K * max|w| max|x^| (w, x^ the dequantized operands; mmf_bound of the tests' numpy checker), y_ref the oracle's
 // bit-exact mul_mat.
+//
+// Input domain: the results are finite and within that tolerance while every f16 operand is
+// finite, that is while
+//   |d * sc| * max(q) <= 65504 and |dmin * m| <= 65504   on the weight side (max(q) = 15 / 31 / 63
+//                                                        for Q4_K / Q5_K / Q6_K),
+//   16 * max|x| <= 65504                                 on the activation side (|yd * bsum16|; it
+//                                                        covers |yd * q8| <= max|x|).
+// Beyond it an operand rounds to inf and the path returns non-finite values; there is no
+// fallback. The bit-exact path (kq_mmq, the default) has no such limit. fp16 subnormal, zero,
+// negative and mixed-sign d / dmin and saturated scale bytes are inside the domain, and so are
+// |d| <= 4 and activation rows with 1e3 outliers; d = +-65504 is outside it (f16(d * sc) is
+// inf from sc = 2 on), as is an activation outlier of 1e5 (tests/test_gpu_block_edges.py,
+// tests/test_oracle.py). A d of +-inf or NaN stays in its row: that row's outputs are
+// non-finite, every other row is within the tolerance. The weight operand costs a subtract and
+// a multiply and not one fma with the addend -1024 * dsc: that addend is past 65504 from
+// |dsc| = 64 on, which made every row with such a scale non-finite (1-4 % of kq_mmf's time at
+// pp512 for the whole stated domain).
 //
 // Tiles: a workgroup of 4 waves owns 128 weight rows (32 per wave: the MFMA's columns)
 // x 128 activation columns (4 MFMA tiles of 32 per wave, fed by ONE dequantized weight
@@ -93,7 +110,7 @@ __device__ __forceinline__ void mmf_load(MmfW &w, const uint8_t *blk, int h) {
 // uses (Q4_K/Q5_K: sub-blocks 2p, 2p+1; Q6_K: groups 4p+h, 4p+2+h), and the group
 // operand of the per-group MFMA (k' = 8h + j <-> group 8h + j).
 struct MmfS {
-    h2v dlo[4], dhi[4], nlo[4], nhi[4];
+    h2v dlo[4], dhi[4];
     f16x8 wg;
 };
 
@@ -108,15 +125,13 @@ __device__ __forceinline__ MmfS mmf_setup(const MmfW &w, int h) {
         const uint32_t m47 = ((hdr.w >> 4) & 0x0f0f0f0fu) | ((hdr.z >> 2) & 0x30303030u);
         const h2v d2 = as_h2((hdr.x & 0xffffu) * 0x00010001u);
         const h2v dm2 = as_h2((hdr.x >> 16) * 0x00010001u);
-        const h2v k1024 = {(_Float16)1024.0f, (_Float16)1024.0f}, km1024 = {(_Float16)-1024.0f, (_Float16)-1024.0f};
+        const h2v k1024 = {(_Float16)1024.0f, (_Float16)1024.0f};
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const uint32_t sw = p < 2 ? s03 : s47;
             // f16(d * sc): the magic pair minus 1024 is sc exactly, one rounding in the multiply
             s.dlo[p] = (magic_bcast(sw, 2 * (p & 1)) - k1024) * d2;
             s.dhi[p] = (magic_bcast(sw, 2 * (p & 1) + 1) - k1024) * d2;
-            s.nlo[p] = s.dlo[p] * km1024;  // exact
-            s.nhi[p] = s.dhi[p] * km1024;
         }
         const uint32_t mw = h ? m47 : m03;  // sub-blocks 4h .. 4h+3
         const h2v ndm2 = -dm2;
@@ -138,8 +153,6 @@ __device__ __forceinline__ MmfS mmf_setup(const MmfW &w, int h) {
             const _Float16 a = dsc(4 * p + h), b = dsc(4 * p + 2 + h);
             s.dlo[p] = h2_bcast(a);
             s.dhi[p] = h2_bcast(b);
-            s.nlo[p] = h2_bcast(a * (_Float16)-1024.0f);
-            s.nhi[p] = h2_bcast(b * (_Float16)-1024.0f);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) s.wg[j] = dsc(8 * h + j) * (_Float16)-32.0f;  // exact
@@ -167,10 +180,13 @@ __device__ __forceinline__ f16x8 mmf_frag(const MmfW &w, const MmfS &s, int p, i
         lo = ((l0 >> sh) & 0x0f0f0f0fu) | (((qh >> sh) & 0x03030303u) << 4);
         hi = ((l1 >> sh) & 0x0f0f0f0fu) | (((qh >> (sh + 2u)) & 0x03030303u) << 4);
     }
-    const h2v a0 = __builtin_elementwise_fma(as_h2(__builtin_amdgcn_perm(MAGIC, lo, 0x04010400u)), s.dlo[p], s.nlo[p]);
-    const h2v a1 = __builtin_elementwise_fma(as_h2(__builtin_amdgcn_perm(MAGIC, lo, 0x04030402u)), s.dlo[p], s.nlo[p]);
-    const h2v a2 = __builtin_elementwise_fma(as_h2(__builtin_amdgcn_perm(MAGIC, hi, 0x04010400u)), s.dhi[p], s.nhi[p]);
-    const h2v a3 = __builtin_elementwise_fma(as_h2(__builtin_amdgcn_perm(MAGIC, hi, 0x04030402u)), s.dhi[p], s.nhi[p]);
+    // f16(q * dsc): the magic pair minus 1024 is q exactly, one rounding in the multiply. (One fma with the
+    // addend -1024 * dsc would give the same bits for |dsc| < 64 only: beyond, the addend is past 65504.)
+    const h2v k1024 = {(_Float16)1024.0f, (_Float16)1024.0f};
+    const h2v a0 = (as_h2(__builtin_amdgcn_perm(MAGIC, lo, 0x04010400u)) - k1024) * s.dlo[p];
+    const h2v a1 = (as_h2(__builtin_amdgcn_perm(MAGIC, lo, 0x04030402u)) - k1024) * s.dlo[p];
+    const h2v a2 = (as_h2(__builtin_amdgcn_perm(MAGIC, hi, 0x04010400u)) - k1024) * s.dhi[p];
+    const h2v a3 = (as_h2(__builtin_amdgcn_perm(MAGIC, hi, 0x04030402u)) - k1024) * s.dhi[p];
     return f16x8{a0[0], a0[1], a1[0], a1[1], a2[0], a2[1], a3[0], a3[1]};
 }
 

@@ -313,7 +313,13 @@ int mi355x_mmq_impl(int impl);
  * unpacking, the accumulated dot on the f16 matrix core, csrc/kq_mmf.hip -- on the shapes
  * where it is the faster kernel, kq_mmq elsewhere) or MI355X_PREFILL_F16_ALL (kq_mmf on
  * every shape; A/B and tests). The north_star's "within a stated fp32 tolerance on the
- * accumulated dot". Replaces no reference interface (ggml-cpu has one precision); a
+ * accumulated dot". The f16 path's input domain: its results are finite and within the
+ * tolerance while |d * sc| * max(q) <= 65504 and |dmin * m| <= 65504 on the weight side and
+ * 16 * max|x| <= 65504 on the activation side (its f16 operands f16(d * sc) * q,
+ * f16(dmin * m), f16(yd * q8) and f16(yd * bsum16) stay finite); beyond that it returns
+ * non-finite values, with no fallback. Subnormal, zero and negative block scales, |d| <= 4 and
+ * activation rows with 1e3 outliers are inside the domain; d = +-65504 and a 1e5 outlier are
+ * outside it. The exact path has no such limit. Replaces no reference interface (ggml-cpu has one precision); a
  * backend option like llama.cpp's GGML_CUDA_FORCE_MMQ / cuBLAS choice. A negative value
  * queries. The library reads no environment: the precision changes only through this
  * call (process-wide; a graph captured before it is re-planned, and a caller sizing its
@@ -351,7 +357,10 @@ int mi355x_debug_knob(const char *name, double value, double *previous);
  * out.folded:103-104): dst[r][0..ne0) = row ids[r] of `table` as f32. type F32 /
  * Q4_K / Q5_K / Q6_K; `n_rows` rows (ne01) of `row_stride` bytes; ids: device int32[n_ids].
  * An id outside [0, n_rows) (ggml: GGML_ASSERT(i01 >= 0 && i01 < ne01)) reads nothing
- * and writes a NaN row. */
+ * and writes a NaN row. Precondition for the K-quant types: the kernel loads whole 16-byte
+ * granules around each 2048-element chunk of a row, so the up to 15 bytes below a row's first
+ * byte and above its last (to the enclosing 16-byte boundaries) must be readable device
+ * memory: any table inside an allocation with 16 spare bytes on both sides qualifies. */
 int mi355x_get_rows(int type, const void *table, int64_t ne0, size_t row_stride, int64_t n_rows,
                     const int32_t *ids, int64_t n_ids, float *dst, void *stream);
 /* GGML_OP_RMS_NORM (ggml_compute_forward_rms_norm_f32, out.folded:189-193) over

@@ -265,6 +265,125 @@ def random_blocks(rng, type_, N, K, d_lo=2.0 ** -14, d_hi=2.0 ** -6):
     return raw.reshape(N, nb * B)
 
 
+# ------------------------------------------- super-block scale edges (d / dmin)
+# What real GGUF files hold and random_blocks never draws: Q6_K's d is negative in about
+# half of all blocks (the quantizer's iscale = -128 / max_scale), Q4_K / Q5_K's d and dmin
+# are routinely fp16 subnormals (d = max_scale / 63), all-zero blocks carry d = 0, scale
+# bytes saturate. Row r of edge_blocks is of category cats[r % len(cats)], so a failing
+# row index names its category (edge_category).
+EDGE_CATS = ("control", "subnormal", "zero", "negzero", "negative", "mixed", "saturated", "large", "maxf16")
+EDGE_CATS_F16 = EDGE_CATS[:-1]  # the f16 prefill path's input domain (csrc/kq_mmf.hip header)
+
+
+def edge_category(row, cats=EDGE_CATS):
+    return cats[int(row) % len(cats)]
+
+
+def _scale_offsets(type_):
+    """Byte offsets of the fp16 super-block scales in a block: (d, dmin) or (d,)."""
+    return (0, 2) if type_ in (Q4_K, Q5_K) else (208,)
+
+
+def _log_uniform_f16(rng, shape, lo_exp, hi_exp, bits_lo, bits_hi):
+    """fp16 bits of 2^U[lo_exp, hi_exp), held inside [bits_lo, bits_hi] after rounding."""
+    v = np.exp2(rng.uniform(lo_exp, hi_exp, size=shape)).astype(np.float16).view(np.uint16)
+    return np.clip(v, bits_lo, bits_hi).astype(np.uint16)
+
+
+def edge_blocks(rng, type_, N, K, cats=EDGE_CATS):
+    """random_blocks with d (and dmin of Q4_K / Q5_K) overwritten per row by category; values
+    log-uniform over the stated range, independent per block and for d and dmin:
+      control    unchanged
+      subnormal  [2^-24, 2^-14), positive
+      zero       every other block +0.0 (the phase differs between d and dmin and from one
+                 row of the category to the next), the rest as drawn by random_blocks
+      negzero    the same with 0x8000
+      negative   -[2^-14, 2^-6]
+      mixed      +-[2^-24, 2^-6], a random sign per block
+      saturated  d = dmin = 2^-6; Q4_K / Q5_K: every byte after the header 0xFF (scales and
+                 mins 63, quants maximal); Q6_K: ql / qh 0xFF, int8 scales 0x7F / 0x80 in turn
+      large      +-[2^-6, 4]
+      maxf16     +-65504"""
+    nb = K // QK_K
+    B = BLOCK_BYTES[type_]
+    raw = random_blocks(rng, type_, N, K).reshape(N, nb, B)
+    offs = _scale_offsets(type_)
+    blk = np.arange(nb)
+    for r in range(N):
+        cat = edge_category(r, cats)
+        rep = r // len(cats)
+        for fi, off in enumerate(offs):
+            cur = raw[r, :, off:off + 2].copy().view("<u2")[:, 0]
+            sign = (rng.integers(0, 2, size=nb) << 15).astype(np.uint16)
+            if cat == "control":
+                h = cur
+            elif cat == "subnormal":
+                h = _log_uniform_f16(rng, nb, -24, -14, 0x0001, 0x03FF)
+            elif cat in ("zero", "negzero"):
+                z = (blk + rep + fi) % 2 == 0
+                h = np.where(z, np.uint16(0x8000 if cat == "negzero" else 0), cur).astype(np.uint16)
+            elif cat == "negative":
+                h = _log_uniform_f16(rng, nb, -14, -6, 0x0400, 0x2400) | np.uint16(0x8000)
+            elif cat == "mixed":
+                h = _log_uniform_f16(rng, nb, -24, -6, 0x0001, 0x2400) | sign
+            elif cat == "saturated":
+                h = np.full(nb, 0x2400, np.uint16)
+            elif cat == "large":
+                h = _log_uniform_f16(rng, nb, -6, 2, 0x2400, 0x4400) | sign
+            elif cat == "maxf16":
+                h = np.full(nb, 0x7BFF, np.uint16) | sign
+            else:
+                raise ValueError(cat)
+            raw[r, :, off:off + 2] = h.astype("<u2")[:, None].view(np.uint8)
+        if cat == "saturated":
+            if type_ in (Q4_K, Q5_K):
+                raw[r, :, 4:] = 0xFF
+            else:
+                raw[r, :, 0:192] = 0xFF
+                raw[r, :, 192:208:2] = 0x7F
+                raw[r, :, 193:208:2] = 0x80
+    return raw.reshape(N, nb * B)
+
+
+def poison_blocks(w, type_, K, rows, bits, block=None):
+    """A copy of w with the fp16 pattern bits[i] (0x7C00 +inf, 0xFC00 -inf, 0x7E00 NaN) as the d
+    of one superblock (the middle one unless `block` says otherwise) of row rows[i]."""
+    nb = K // QK_K
+    B = BLOCK_BYTES[type_]
+    out = np.array(w, np.uint8).reshape(-1, nb, B)
+    b = nb // 2 if block is None else block
+    off = _scale_offsets(type_)[0]
+    for r, h in zip(rows, bits):
+        out[r, b, off] = h & 0xFF
+        out[r, b, off + 1] = (h >> 8) & 0xFF
+    return out.reshape(-1, nb * B)
+
+
+EDGE_ACTS = ("normal", "zero_block", "ones", "alternating", "outliers")
+
+
+def edge_activations(rng, M, K, first=0):
+    """The activation rows that go with edge_blocks, row i of form EDGE_ACTS[(first + i) % 5]:
+    standard normal; standard normal with the middle superblock all zero (Q8_K d = 0); constant
+    +1.0 and alternating +-1.0 (every q8 is +-127: the largest integer sums against the
+    `saturated` rows); standard normal with every 7th element x 1e3."""
+    nb = K // QK_K
+    x = np.empty((M, K), F32)
+    for i in range(M):
+        form = EDGE_ACTS[(first + i) % len(EDGE_ACTS)]
+        if form == "ones":
+            x[i] = 1.0
+        elif form == "alternating":
+            x[i] = np.where(np.arange(K) % 2 == 0, F32(1.0), F32(-1.0))
+        else:
+            x[i] = rng.standard_normal(K).astype(F32)
+            if form == "zero_block":
+                x[i, (nb // 2) * QK_K:(nb // 2 + 1) * QK_K] = 0.0
+            elif form == "outliers":
+                x[i, ::7] *= F32(1e3)
+    return x
+
+
 # ------------------------------------------- f16 prefill path (kq_mmf), stated tolerance
 def mmf_operands(w, type_, K, x):
     """The operands kq_mmf feeds the f16 matrix core, as float64 of their f16 values, and

@@ -87,15 +87,17 @@ MIXES = [(Q4_K, Q4_K, Q4_K), (Q4_K, Q4_K, Q6_K), (Q5_K, Q5_K, Q6_K)]
 
 
 @functools.lru_cache(maxsize=None)
-def qkv_case(mix):
+def qkv_case(mix, edges=False):
     """q / k / v = MUL_MAT(w, x) on one activation, then the prompt attention: the oracle's mul_mat per
     matrix and tests/attn_prompt_ref.py (equal to decoding the tokens one by one, outputs and caches:
-    tests/test_ops_oracle.py::test_prompt_reference_equals_sequential_decode)."""
+    tests/test_ops_oracle.py::test_prompt_reference_equals_sequential_decode). edges: the weights with the
+    scale edges of tests/llama_model.py (tests/test_gpu_block_edges.py); off, those of every earlier run."""
     from oracle import kq_oracle, kq_ops_oracle
     from tests import llama_model as LM
     hd, nh, nkv, n_ctx, T, E = QKV_HD, QKV_NH, QKV_NKV, QKV_CTX, QKV_T, QKV_E
     rng = np.random.default_rng([QKV_T, QKV_E, *mix])
-    ws = [LM.kquant(rng, mix[0], nh * hd, E), LM.kquant(rng, mix[1], nkv * hd, E), LM.kquant(rng, mix[2], nkv * hd, E)]
+    ws = [LM.kquant(rng, mix[0], nh * hd, E, edges=edges), LM.kquant(rng, mix[1], nkv * hd, E, edges=edges),
+          LM.kquant(rng, mix[2], nkv * hd, E, edges=edges)]
     x = rng.standard_normal((T, E)).astype(np.float32)
     pos = np.arange(20, 20 + T, dtype=np.int32)
     kc0, vc0 = rand_caches(rng, n_ctx, nkv * hd)
@@ -116,11 +118,16 @@ def test_qkv_in_one_launch_on_every_tile(dev, forced, mix, impl):
     bits of q and k are what shows the fallback was taken). The launch stores the KV cells
     (no kq_kv_store). Eager and replayed, from junk caches each time: q, k, v, the attention rows and both
     caches on bits."""
+    forced(impl)
+    check_qkv_launch(dev, mix, qkv_case(mix))
+
+
+def check_qkv_launch(dev, mix, case):
+    """The body of test_qkv_in_one_launch_on_every_tile on one qkv_case, under the selector in force."""
     import torch
     import ggml_mi355x as g
-    forced(impl)
     hd, nh, nkv, n_ctx, T, E = QKV_HD, QKV_NH, QKV_NKV, QKV_CTX, QKV_T, QKV_E
-    ws, x, pos, kc0, vc0, refs, att_ref, kc_ref, vc_ref = qkv_case(mix)
+    ws, x, pos, kc0, vc0, refs, att_ref, kc_ref, vc_ref = case
     rows = [nh * hd, nkv * hd, nkv * hd]
     tab = g.rope_table(n_ctx, hd, 10000.0, 1.0, device=dev)
     wd = [t(w, dev) for w in ws]

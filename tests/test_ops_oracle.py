@@ -497,3 +497,54 @@ def test_prompt_softmax_cases_reach_both_sums(O, hd, nh, nkv):
                 exact = {_softmax_sum_is_exact(O, kc, q16, pos[i], n_ctx, g, h, nkv, hd, scale_of(hd))
                          for h in range(g * gsz, (g + 1) * gsz)}
                 assert exact == want, (qscale, "token", i, "group", g, exact)
+
+
+# ---------------------------------------------------------------- super-block scale edges
+@pytest.mark.parametrize("type_", [12, 13, 14])
+def test_get_rows_on_edge_blocks(O, type_):
+    """get_rows over every scale category (oracle/kq_oracle_np.py edge_blocks): finite, and equal
+    to the float64 dequantization within the float roundings of the row's two products and
+    their sum (3 x 2^-24 of the terms' magnitudes)."""
+    from oracle import kq_oracle_np as npo
+    K = 768
+    ncat = len(npo.EDGE_CATS)
+    w = npo.edge_blocks(np.random.default_rng(70 + type_), type_, 3 * ncat, K)
+    ids = np.arange(3 * ncat, dtype=np.int32)[::-1].copy()
+    got = O.get_rows(type_, w, K, ids)
+    assert np.isfinite(got).all()
+    ref = npo.dequantize(w, type_, K)[ids]
+    q, sc, mn, f = npo.weights_int(w, type_, K)
+    d = np.abs(npo.fp16_to_f32(f["d"]).astype(np.float64))[..., None]
+    if type_ == 14:
+        mag = d * np.repeat(np.abs(sc), 16, -1) * np.abs(q - 32)
+    else:
+        dm = np.abs(npo.fp16_to_f32(f["dmin"]).astype(np.float64))[..., None]
+        mag = d * np.repeat(sc, 32, -1) * q + dm * np.repeat(mn, 32, -1)
+    mag = mag.reshape(len(w), K)[ids]
+    err = np.abs(got.astype(np.float64) - ref)
+    bad = np.argwhere(err > 3 * 2.0 ** -24 * mag)
+    assert not len(bad), (npo.edge_category(ids[bad[0][0]]), bad[0].tolist())
+    # the signs survive: a negative-d row is the negation of the same row with |d|
+    assert (got[np.array([npo.edge_category(i) == "negative" for i in ids])] != 0).any()
+
+
+@pytest.mark.parametrize("mix", ["q4_k_m", "q5_k_m"])
+def test_edge_model_decodes_finite(O, mix):
+    """tests/llama_model.py build(edges=True): signs, +-0 and subnormals on every matrix's scales;
+    the oracle's token stays finite over 8 tokens, and edges=False is the model of before."""
+    from tests import llama_model as LM
+    import ggml_mi355x.llama as LL
+    hp = LL.hparams(256, 2, 4, 2, 512, 300)
+    w = LM.build(hp, 5, mix=mix, edges=True)
+    plain, again = LM.build(hp, 5, mix=mix), LM.build(hp, 5, mix=mix, edges=False)
+    assert all(np.array_equal(plain[k][1] if isinstance(plain[k], tuple) else plain[k],
+                              again[k][1] if isinstance(again[k], tuple) else again[k]) for k in plain)
+    from oracle import kq_oracle_np as npo
+    ty, q = w["blk.0.attn_q"]
+    bits = npo.split_blocks(q, ty, 256)["d"]
+    assert (bits >> 15).any() and not (bits >> 15).all() and ((bits & 0x7FFF) == 0).any()
+    model, cache = LM.oracle_model(hp, w, 32)
+    for p, tok in enumerate([3, 299, 3, 0, 17, 150, 151, 42]):
+        logits, trace = O.decode_token(model, tok, p, cache, n_threads=2)
+        assert np.isfinite(logits).all() and all(np.isfinite(t).all() for t in trace), p
+    assert float(np.abs(logits).max()) > 0

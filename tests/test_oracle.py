@@ -207,3 +207,154 @@ def test_unpinned_choice_flip_rates(oracle, npo):
             y1 = oracle.mul_mat_q8(13, w5, q, K)[0]
         f5 = (y0.view(np.uint32) != y1.view(np.uint32)).mean()
         assert lo < f5 < hi, (v, f5)
+
+
+# ---------------------------------------------------------------- super-block scale edges
+def _scales_f16(npo, w, type_, K):
+    """The fp16 bit patterns of d (and dmin) per row and block: list of (N, nb) uint16."""
+    f = npo.split_blocks(w, type_, K)
+    return [f["d"]] + ([f["dmin"]] if type_ in (12, 13) else [])
+
+
+@pytest.mark.parametrize("type_", TYPES)
+@pytest.mark.parametrize("K", [256, 768])
+def test_edge_blocks_produces_every_category(npo, type_, K):
+    """Decoded back: sign, zero-ness, subnormality and range of d / dmin per category, so that an
+    edit cannot quietly turn edge_blocks back into random_blocks."""
+    ncat = len(npo.EDGE_CATS)
+    N = 8 * ncat
+    w = npo.edge_blocks(np.random.default_rng(type_ + K), type_, N, K)
+    nb = K // 256
+    assert w.shape == (N, nb * npo.BLOCK_BYTES[type_]) and w.dtype == np.uint8
+    assert npo.EDGE_CATS_F16 == npo.EDGE_CATS[:-1] and npo.EDGE_CATS[-1] == "maxf16"
+    fields = _scales_f16(npo, w, type_, K)
+    seen_neg = {c: False for c in npo.EDGE_CATS}
+    seen_pos = dict(seen_neg)
+    zero_pairs = set()
+    for r in range(N):
+        cat = npo.edge_category(r)
+        assert cat == npo.EDGE_CATS[r % ncat]
+        for fi, h in enumerate(fields):
+            bits = h[r]
+            v = npo.fp16_to_f32(bits).astype(np.float64)
+            mag, neg = bits & 0x7FFF, (bits >> 15).astype(bool)
+            seen_neg[cat] |= bool(neg.any())
+            seen_pos[cat] |= bool((~neg).any())
+            if cat == "control":
+                assert (~neg).all() and (mag >= 0x0400).all() and (v <= 2.0 ** -6).all()
+            elif cat == "subnormal":
+                assert (~neg).all() and (mag >= 1).all() and (mag < 0x0400).all()
+                assert (v >= 2.0 ** -24).all() and (v < 2.0 ** -14).all()
+            elif cat in ("zero", "negzero"):
+                z = mag == 0
+                want = np.arange(nb) % 2 == (r // ncat + fi) % 2
+                assert (z == want).all(), (r, fi, bits)
+                assert (bits[z] == (0x8000 if cat == "negzero" else 0)).all()
+                assert (mag[~z] >= 0x0400).all() and (~neg[~z]).all()
+            elif cat == "negative":
+                assert neg.all() and (-v >= 2.0 ** -14).all() and (-v <= 2.0 ** -6).all()
+            elif cat == "mixed":
+                assert (np.abs(v) >= 2.0 ** -24).all() and (np.abs(v) <= 2.0 ** -6).all()
+            elif cat == "saturated":
+                assert (bits == 0x2400).all() and (v == 2.0 ** -6).all()
+            elif cat == "large":
+                assert (np.abs(v) >= 2.0 ** -6).all() and (np.abs(v) <= 4.0).all()
+            elif cat == "maxf16":
+                assert (np.abs(v) == 65504.0).all()
+        if cat in ("zero", "negzero") and len(fields) == 2:
+            for b in range(nb):
+                zero_pairs.add((bool(fields[0][r, b] & 0x7FFF == 0), bool(fields[1][r, b] & 0x7FFF == 0)))
+    for cat in ("mixed", "large", "maxf16"):
+        assert seen_neg[cat] and seen_pos[cat], cat
+    assert seen_neg["negative"] and seen_neg["negzero"] and not seen_neg["subnormal"] and not seen_neg["zero"]
+    if type_ in (12, 13):
+        assert zero_pairs == {(True, False), (False, True)}  # d = 0 with dmin != 0, and the reverse
+    # the mixed rows reach the subnormals as well as the normals
+    mixed = np.concatenate([h[5::ncat].ravel() for h in fields]) & 0x7FFF
+    assert (mixed < 0x0400).any() and (mixed >= 0x0400).any()
+    # saturated: scales, mins and quants at their maxima
+    q, sc, mn, _ = npo.weights_int(w[6::ncat], type_, K)
+    if type_ in (12, 13):
+        assert (sc == 63).all() and (mn == 63).all() and (q == (15 if type_ == 12 else 31)).all()
+    else:
+        assert (q == 63).all() and (sc[..., 0::2] == 127).all() and (sc[..., 1::2] == -128).all()
+    # the control rows are random_blocks' rows, byte for byte
+    ref = npo.random_blocks(np.random.default_rng(type_ + K), type_, N, K)
+    assert (w[0::ncat] == ref[0::ncat]).all()
+
+
+def test_poison_blocks_and_edge_activations(npo):
+    K = 768
+    w = npo.random_blocks(np.random.default_rng(3), 14, 10, K)
+    p = npo.poison_blocks(w, 14, K, [0, 4, 9], [0x7C00, 0xFC00, 0x7E00])
+    d, d0 = npo.split_blocks(p, 14, K)["d"], npo.split_blocks(w, 14, K)["d"]
+    assert d[0, 1] == 0x7C00 and d[4, 1] == 0xFC00 and d[9, 1] == 0x7E00
+    d[[0, 4, 9], 1] = d0[[0, 4, 9], 1]
+    assert (d == d0).all() and (p != w).sum() <= 6
+    x = npo.edge_activations(np.random.default_rng(4), 7, K)
+    assert x.dtype == np.float32 and x.shape == (7, K) and np.isfinite(x).all()
+    assert (x[1, 256:512] == 0).all() and (x[1, :256] != 0).any()
+    assert (x[2] == 1.0).all() and (x[3, 0::2] == 1.0).all() and (x[3, 1::2] == -1.0).all()
+    assert np.abs(x[4, ::7]).max() > 1e3 and np.abs(x[4, 1::7]).max() < 10
+    assert (x[6, 256:512] == 0).all()  # the forms repeat
+    q8 = npo.quantize_q8_K(x[2:4])
+    assert (np.abs(q8["qs"]) == 127).all()
+    assert (npo.edge_activations(np.random.default_rng(4), 1, K, first=3)[0] == x[3]).all()
+
+
+@pytest.mark.parametrize("type_", TYPES)
+def test_edge_blocks_neon_equals_simd_and_finite(oracle, npo, type_):
+    K = 768
+    rng = np.random.default_rng(40 + type_)
+    w = npo.edge_blocks(rng, type_, 3 * len(npo.EDGE_CATS), K)
+    x = npo.edge_activations(rng, 5, K)
+    a = oracle.mul_mat(type_, w, x, variant="neon")
+    b = oracle.mul_mat(type_, w, x, variant="simd")
+    assert (a.view(np.uint32) == b.view(np.uint32)).all()
+    assert np.isfinite(a).all()
+    ref = npo.mul_mat_q8(w, type_, K, npo.quantize_q8_K(x))
+    assert (a.view(np.uint32) == ref.view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("type_", TYPES)
+@pytest.mark.parametrize("cat", range(8), ids=lambda c: "cat%d" % c)
+def test_edge_mmf_emulation_within_bound_per_category(oracle, npo, type_, cat):
+    """The condition the GPU test of the f16 path relies on, per category of EDGE_CATS_F16 and
+    with only that category's rows in the bound (its second term takes the global max A, so
+    one extreme row would loosen it for all): the emulation is finite and within mmf_bound of
+    the bit-exact reference. maxf16 is outside the f16 path's domain: f16(d sc) overflows."""
+    K = 768
+    cats = npo.EDGE_CATS_F16
+    rng = np.random.default_rng(60 + type_)
+    w = npo.edge_blocks(rng, type_, 4 * len(cats), K, cats)[cat::len(cats)]
+    x = npo.edge_activations(rng, 10, K)
+    ref = oracle.mul_mat(type_, w, x).astype(np.float64)
+    emu = npo.mmf_emulate(w, type_, K, x)
+    bound = npo.mmf_bound(w, type_, K, x)
+    assert np.isfinite(emu).all() and np.isfinite(bound).all(), cats[cat]
+    assert (np.abs(emu - ref) <= bound).all(), (cats[cat], float((np.abs(emu - ref) / bound).max()))
+
+
+def test_edge_mmf_domain_ends_before_maxf16(npo):
+    w = npo.edge_blocks(np.random.default_rng(1), 12, 9, 256)[8:9]
+    assert npo.edge_category(8) == "maxf16"
+    x = npo.edge_activations(np.random.default_rng(2), 1, 256)
+    with np.errstate(all="ignore"):
+        assert not np.isfinite(npo.mmf_emulate(w, 12, 256, x)).all()
+        # the activation side: 16 * max|x| <= 65504 holds for the 1e3-outlier row, not for a 1e5 outlier
+        ok = npo.random_blocks(np.random.default_rng(3), 12, 4, 256)
+        far = x.copy()
+        far[0, 5] = 1e5
+        assert np.isfinite(npo.mmf_emulate(ok, 12, 256, npo.edge_activations(np.random.default_rng(2), 5, 256))).all()
+        assert not np.isfinite(npo.mmf_emulate(ok, 12, 256, far)).all()
+
+
+@pytest.mark.parametrize("type_", TYPES)
+def test_edge_large_rows_reach_past_64(npo, type_):
+    """The `large` rows hold scales with |f16(d sc)| >= 64, where -1024 * f16(d sc) is past 65504 (an f16
+    fma with that addend is non-finite there), and stay inside |d sc| max(q) <= 65504."""
+    cats = npo.EDGE_CATS_F16
+    w = npo.edge_blocks(np.random.default_rng([type_, 768, 80, 20]), type_, 80, 768, cats)[7::len(cats)]
+    q, sc, _, f = npo.weights_int(w, type_, 768)
+    dsc = np.abs((npo.fp16_to_f32(f["d"])[..., None] * sc.astype(np.float32)).astype(np.float16).astype(np.float64))
+    assert dsc.max() >= 64 and dsc.max() * {12: 15, 13: 31, 14: 63}[type_] <= 65504
