@@ -614,6 +614,8 @@ void *reg_proc(ggml_backend_reg_t, const char *name) {
         return (void *)ggml_backend_mi355x_set_multi_seq;
     if (name && std::strcmp(name, "ggml_backend_mi355x_set_long_context") == 0)
         return (void *)ggml_backend_mi355x_set_long_context;
+    if (name && std::strcmp(name, "ggml_backend_mi355x_set_prompt_attn_f16") == 0)
+        return (void *)ggml_backend_mi355x_set_prompt_attn_f16;
     return nullptr;
 }
 
@@ -671,6 +673,10 @@ void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable) {
 }
 
 void ggml_backend_mi355x_set_long_context(bool enable) { mi355x_attn_stream(enable ? 1 : 0); }
+
+void ggml_backend_mi355x_set_prompt_attn_f16(bool enable) {
+    mi355x_attn_prompt_precision(enable ? MI355X_ATTN_PROMPT_F16 : MI355X_ATTN_PROMPT_EXACT);
+}
 
 GGML_BACKEND_DL_IMPL(ggml_backend_mi355x_reg)
 GGML_BACKEND_DL_SCORE_IMPL(mi355x_score)

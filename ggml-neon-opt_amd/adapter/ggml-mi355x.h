@@ -40,6 +40,13 @@ GGML_BACKEND_API void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, 
 // over such caches run on the streamed kernels too. Also returned by the registry's
 // get_proc_address under this name.
 GGML_BACKEND_API void ggml_backend_mi355x_set_long_context(bool enable);
+// Prompt (batched, single-sequence) attention on the f16 matrix cores within the library's stated
+// bound (mi355x_attn_prompt_precision F16) instead of the decode token's bits: off (the default),
+// nothing changes; on, the attention of graphs of two or more tokens runs kq_attn_prompt_f16.
+// Decode graphs, multi-sequence graphs (ATTN_BATCH) and both KV caches keep their bits.
+// Process-wide, like the library's selector. Also returned by the registry's get_proc_address
+// under this name.
+GGML_BACKEND_API void ggml_backend_mi355x_set_prompt_attn_f16(bool enable);
 
 #ifdef __cplusplus
 }

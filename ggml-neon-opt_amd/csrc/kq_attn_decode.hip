@@ -453,6 +453,7 @@ bool attn_cells_applies(const AttnArgs &a) {
 // The workspace of a decode attention that will take the two launches, allocated now (callers
 // that capture graphs call this first; an eager launch allocates on its own)
 int attn_cells_reserve(const AttnArgs &a, hipStream_t stream, int n_tok) {
+    if (n_tok > 1 && attn_prompt_f16()) return MI355X_OK;  // kq_attn_prompt_f16 uses no workspace
     if (n_tok > 1 ? attn_stream_prompt_applies(a) : attn_stream_applies(a))
         return attn_cells_buffer(attn_stream_workspace(a, n_tok), stream, true) ? MI355X_OK : MI355X_E_WORKSPACE;
     if (n_tok > 1 || !attn_cells_applies(a)) return MI355X_OK;

@@ -217,6 +217,11 @@ int attn_args_from(const mi355x_attn_desc *d, AttnArgs &a);  // + check_attn
 // pieces the streamed path shares
 size_t attn_prompt_lds(int hd, int n_ctx);
 int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s);  // kq_kv_store: a prompt's T new cells
+bool attn_prompt_f16();  // mi355x_attn_prompt_precision is MI355X_ATTN_PROMPT_F16
+
+// ---------------------------------------------------------------- kq_attn_mfma.hip
+// Prompt attention on the f16 matrix cores (after kq_kv_store): every descriptor check_attn passes
+int launch_attn_prompt_f16(const AttnArgs &a, int n_tok, hipStream_t s);
 
 // ---------------------------------------------------------------- kq_attn_decode.hip
 // The decode attention block: its kernels, their LDS sizing, the dispatch policy, the launch.

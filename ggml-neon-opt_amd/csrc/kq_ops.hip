@@ -607,6 +607,10 @@ int launch_swiglu(const float *g, const float *u, float *y, int64_t n, hipStream
 // mi355x_attn_prompt_impl: MI355X_ATTN_GROUP (default: one workgroup per kv group and token
 // where the group fits) or MI355X_ATTN_HEAD (one per query head and token)
 std::atomic<int> g_prompt_impl{MI355X_ATTN_GROUP};
+// mi355x_attn_prompt_precision: MI355X_ATTN_PROMPT_EXACT (default: the kernels of this file and the
+// streamed form, the decode token's bits) or MI355X_ATTN_PROMPT_F16 (kq_attn_mfma.hip)
+std::atomic<int> g_prompt_precision{MI355X_ATTN_PROMPT_EXACT};
+bool attn_prompt_f16() { return g_prompt_precision.load() == MI355X_ATTN_PROMPT_F16; }
 
 bool attn_prompt_group_ok(const AttnArgs &a) {
     const int gsz = a.n_head / a.n_head_kv;
@@ -624,7 +628,7 @@ int attn_prompt_tpw(const AttnArgs &a) {
 
 // Q8L rows written by the group kernel: its slice (gsz*head_dim) must be whole superblocks
 bool attn_prompt_q8_ok(const AttnArgs &a) {
-    return !attn_stream_prompt_applies(a) && attn_prompt_group_ok(a) && ((a.n_head / a.n_head_kv) * a.head_dim) % QK == 0 &&
+    return !attn_prompt_f16() && !attn_stream_prompt_applies(a) && attn_prompt_group_ok(a) && ((a.n_head / a.n_head_kv) * a.head_dim) % QK == 0 &&
            a.n_ctx >= a.head_dim;  // staged in the score rows: gsz*head_dim floats
 }
 
@@ -636,6 +640,11 @@ int launch_kv_store(const AttnArgs &a, int n_tok, hipStream_t s) {
 
 int launch_attn_prompt(const AttnArgs &a0, int n_tok, hipStream_t s) {
     if (n_tok <= 0) return MI355X_OK;
+    if (attn_prompt_f16()) {  // the matrix-core kernel: every checked descriptor, no LDS, no workspace
+        if (a0.q8_out) return MI355X_E_INVAL;  // the Q8L-output fusion is the group kernel's (attn_prompt_q8_ok)
+        const int rc = a0.no_store ? 0 : launch_kv_store(a0, n_tok, s);
+        return rc ? rc : launch_attn_prompt_f16(a0, n_tok, s);
+    }
     if (attn_stream_prompt_applies(a0)) return launch_attn_stream_prompt(a0, n_tok, s);
     AttnArgs a = a0;
     a.n_tok = n_tok;
@@ -695,7 +704,7 @@ int check_attn(const AttnArgs &a) {
 
 uint64_t ops_selector_key() {
     return (uint64_t)(uint32_t)attn_impl() | ((uint64_t)(uint32_t)g_prompt_impl.load() << 8) |
-           ((uint64_t)(uint32_t)attn_stream_mode() << 16);
+           ((uint64_t)(uint32_t)attn_stream_mode() << 16) | ((uint64_t)(uint32_t)g_prompt_precision.load() << 24);
 }
 
 }  // namespace kq
@@ -805,7 +814,8 @@ int mi355x_attn_prompt(const mi355x_attn_desc *d, int n_tokens, void *stream) {
     AttnArgs a;
     const int rc = attn_args_from(d, a);
     if (rc) return rc;
-    if (attn_prompt_lds(a.head_dim, a.n_ctx) > 160 * 1024 && !attn_stream_prompt_applies(a)) return MI355X_E_UNSUPPORTED;
+    if (attn_prompt_lds(a.head_dim, a.n_ctx) > 160 * 1024 && !attn_stream_prompt_applies(a) && !attn_prompt_f16())
+        return MI355X_E_UNSUPPORTED;  // (kq_attn_prompt_f16 has no such limit)
     if (n_tokens == 0) return MI355X_OK;
     if (!device_ok()) return MI355X_E_NODEVICE;
     return launch_attn_prompt(a, n_tokens, (hipStream_t)stream);
@@ -814,6 +824,12 @@ int mi355x_attn_prompt(const mi355x_attn_desc *d, int n_tokens, void *stream) {
 int mi355x_attn_prompt_impl(int impl) {
     if (impl != MI355X_ATTN_GROUP && impl != MI355X_ATTN_HEAD) return MI355X_E_INVAL;
     return g_prompt_impl.exchange(impl);
+}
+
+int mi355x_attn_prompt_precision(int p) {
+    if (p == -1) return g_prompt_precision.load();
+    if (p != MI355X_ATTN_PROMPT_EXACT && p != MI355X_ATTN_PROMPT_F16) return MI355X_E_INVAL;
+    return g_prompt_precision.exchange(p);
 }
 
 int mi355x_attn_impl(int impl) {

@@ -55,6 +55,7 @@ ATTN_PATH_HEAD, ATTN_PATH_HEAD_BATCH, ATTN_PATH_SPLIT4, ATTN_PATH_SPLIT8, ATTN_P
 ATTN_PATH_STREAM = 7  # the streamed kernels (attn_stream)
 MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE192 = 0, 1, 2, 3, 4, 6
 PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
+ATTN_PROMPT_EXACT, ATTN_PROMPT_F16 = 0, 1  # attn_prompt_precision
 
 # Every symbol include/ggml_mi355x.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -84,7 +85,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_device_count", "mi355x_device_ordinal", "mi355x_device_memory", "mi355x_backend_memset", "mi355x_backend_set_attn_oproj",
     "mi355x_backend_set_layer_engine", "mi355x_backend_layer_error",
     "mi355x_attn_prompt",
-    "mi355x_attn_prompt_impl", "mi355x_attn_stream",
+    "mi355x_attn_prompt_impl", "mi355x_attn_stream", "mi355x_attn_prompt_precision",
     "mi355x_attn_batch", "mi355x_attn_batch_path",
     "mi355x_rows_prologue_plan", "mi355x_rows_stream_plan", "mi355x_debug_rows_prologue",
     "mi355x_debug_rows_plan",
@@ -329,6 +330,9 @@ def lib():
         L.mi355x_kv_shift.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
+    if hasattr(L, "mi355x_attn_prompt_precision"):  # (an older library under MI355X_LIB, A/B runs: without it)
+        L.mi355x_attn_prompt_precision.argtypes = [i32]
+        L.mi355x_attn_prompt_precision.restype = i32
     L.mi355x_attn_impl.argtypes = [i32]
     L.mi355x_attn_impl.restype = i32
     L.mi355x_attn_stream.argtypes = [i32]
@@ -610,6 +614,14 @@ def attn_prompt_impl(impl):
     """Prompt attention, and attn_batch / OP_ATTN_BATCH: ATTN_GROUP (per kv group and token where it
     fits, default) / ATTN_HEAD (per query head and token); returns the previous."""
     return int(lib().mi355x_attn_prompt_impl(impl))
+
+
+def attn_prompt_precision(p=-1):
+    """Prompt attention precision (mi355x_attn_prompt_precision): ATTN_PROMPT_EXACT (default: the
+    decode token's bits) / ATTN_PROMPT_F16 (kq_attn_prompt_f16 on the f16 matrix cores, within the
+    bound include/ggml_mi355x.h states; attn_prompt and the graph backend's prompt nodes follow it,
+    decode and attn_batch stay exact). -1 queries. Returns the previous value, E_INVAL otherwise."""
+    return int(lib().mi355x_attn_prompt_precision(p))
 
 
 def attn_impl(impl):

@@ -464,6 +464,30 @@ int mi355x_attn_stream(int mode);
  * token). mi355x_attn_batch follows the same selector. Returns the previous value, or
  * MI355X_E_INVAL. */
 int mi355x_attn_prompt_impl(int impl);
+/* Prompt attention precision (process-wide, like mi355x_attn_prompt_impl; set only by this call:
+ * the library reads no environment). MI355X_ATTN_PROMPT_EXACT (0, the default): the kernels above,
+ * the decode token's bits. MI355X_ATTN_PROMPT_F16 (1): mi355x_attn_prompt and the graph backend's
+ * prompt ATTN_DECODE nodes (T >= 2) run kq_kv_store (the same cache bits) and then
+ * kq_attn_prompt_f16 (csrc/kq_attn_mfma.hip), a flash-style kernel on v_mfma_f32_32x32x16_f16
+ * that keeps no score matrix, no LDS and no workspace, for every descriptor mi355x_attn_prompt
+ * accepts under the current mi355x_attn_stream mode and for those refused only because the exact
+ * prompt kernel's LDS does not fit (caches past 8192 cells still need mi355x_attn_stream on).
+ * The rule: with q^ = f16(rope(q)) (the exact path's operand) and the cache bits K, V, in exact
+ * arithmetic s_c = scale * sum_d q^_d K[c][g][d] for c <= p, m = max s_c, w_c = exp(s_c - m),
+ * l = sum w_c, emu_d = sum_c w_c V[g][d][c] / l; the output is within
+ *   B_d = eps * sum_c w_c |V_dc| / l + 2^-24 * sum_{c<=p} |V_dc| / l
+ *         + 2^-24 * (ceil(n/32) + 32) * sum_c w_c |V_dc| / l,      n = p + 1,
+ *   eps = 2^-10 + 4 D,  D = 2^-23 * head_dim * scale * max_c sum_d |q^_d K_cd|
+ * of emu_d (f32 accumulation of the dot, one f16 rounding of each soft_max weight in [0, 1], f32
+ * accumulation of the output; tests/attn_f16_ref.py restates emulation and bound). Cells after
+ * the position contribute nothing; a position outside the cache gives a NaN row and no cell.
+ * Decode (mi355x_attn_decode, T = 1 nodes), mi355x_attn_batch, the attention + o-proj fusion and
+ * the layer engine stay exact. Under F16 the o-proj's Q8L rows are not written by the attention
+ * (a.q8_out is MI355X_E_INVAL; the planner keeps the quantization unfused). The selector is part
+ * of the graph backend's plan key. p = -1 queries. Returns the previous value, or MI355X_E_INVAL. */
+#define MI355X_ATTN_PROMPT_EXACT 0
+#define MI355X_ATTN_PROMPT_F16 1
+int mi355x_attn_prompt_precision(int p);
 /* The same block for a batch whose KV cells and mask are the graph's own inputs (ggml's
  * SET_ROWS + MUL_MAT + SOFT_MAX(mask) + MUL_MAT): several sequences in one unified cache, or
  * one sequence whose cells are not its positions (a removed cell, a context shift, a reused
