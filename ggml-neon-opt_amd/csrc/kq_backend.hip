@@ -405,6 +405,24 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
             kv_shift_desc_of(t, d);
             return kq::launch_kv_shift(&d, st);
         }
+        case MI355X_OP_MOE_ROUTE: {  // the records the MUL_MAT_ID / MOE_COMBINE nodes read on the device
+            const mi355x_tensor *gi = t->src[0], *x = t->src[1];
+            return kq::launch_moe_route((const float *)gi->data, gi->ne[0], (int)gi->ne[1], (const float *)x->data,
+                                        (int64_t)(x->nb[1] / 4), x->ne[1], t->op_params[0], (int32_t *)t->data,
+                                        (int64_t)(t->nb[1] / 4), nullptr, st);
+        }
+        case MI355X_OP_MUL_MAT_ID: {  // the expert ids read on the device at every replay
+            const mi355x_tensor *w = t->src[0], *x = t->src[1], *rt = t->src[2];
+            return kq::launch_mul_mat_id(w->type, w->data, w->ne[0], w->ne[1], w->nb[1], w->nb[2], (int)w->ne[2],
+                                         (const float *)x->data, x->ne[1], (int64_t)(x->nb[1] / 4),
+                                         (const int32_t *)rt->data, (int64_t)(rt->nb[1] / 4), (int)(rt->ne[0] / 2),
+                                         rt->ne[1], (float *)t->data, st);
+        }
+        case MI355X_OP_MOE_COMBINE: {
+            const mi355x_tensor *ex = t->src[0], *rt = t->src[1];
+            return kq::launch_moe_combine((const float *)ex->data, ex->ne[0], (int)(rt->ne[0] / 2), rt->ne[1],
+                                          (const int32_t *)rt->data, (int64_t)(rt->nb[1] / 4), (float *)t->data, st);
+        }
         case MI355X_OP_ATTN_BATCH: {  // store + attention, cells / mask / pos read on the device
             mi355x_attn_batch_desc d;
             attn_batch_desc_of(t, d);

@@ -373,6 +373,18 @@ int launch_penalize_rows(float *x, int64_t n, int64_t rows, int64_t row_stride, 
 // launch of kq_kv_shift in the descriptor's form, or none for an empty range. No workspace.
 int launch_kv_shift(const mi355x_kv_shift_desc *d, hipStream_t stream);
 
+// ---------------------------------------------------------------- kq_moe.hip
+// The mixture-of-experts FFN (include/ggml_mi355x.h, the rule): every check of mi355x_moe_route,
+// mi355x_mul_mat_id and mi355x_moe_combine, then one launch each (none for an empty shape). No
+// workspace: kq_gemv_id quantizes its activation row in the prologue.
+int launch_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const float *x, int64_t x_stride, int64_t T,
+                     int n_used, int32_t *record_out, int64_t record_stride, float *probs_out, hipStream_t stream);
+int launch_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01, size_t nb01, size_t nb02, int n_expert,
+                      const float *x, int64_t ne11, int64_t x_row_stride, const int32_t *ids, int64_t ids_stride,
+                      int n_used, int64_t T, float *y, hipStream_t stream);
+int launch_moe_combine(const float *ex, int64_t n, int n_used, int64_t T, const int32_t *records, int64_t record_stride,
+                       float *y, hipStream_t stream);
+
 // ---------------------------------------------------------------- kq_attn_batch.hip
 // The attention block with cells and mask from the graph. attn_batch_args_from
 // checks every argument (n_pos: rows of the rope table, 0 = n_ctx); attn_batch_form: MI355X_ATTN_GROUP /

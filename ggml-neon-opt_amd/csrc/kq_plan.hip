@@ -196,6 +196,13 @@ bool layer_match(const PlanOpts &po, mi355x_tensor *const *nodes, int n, int i, 
 // supports_op: contiguous f32 with data
 bool contig_f32(const mi355x_tensor *t) { return t && t->type == MI355X_TYPE_F32 && t->nb[0] == 4 && t->data; }
 
+// A MOE_ROUTE node's output: T records of I32 [2 * n_used], 4-byte aligned, nb[1] the record stride
+bool moe_records_ok(const mi355x_tensor *t, int n_used, int64_t T) {
+    return t->type == MI355X_TYPE_I32 && t->data && !((uintptr_t)t->data & 3u) && t->nb[0] == 4 && n_used >= 1 &&
+           t->ne[0] == 2 * (int64_t)n_used && t->ne[1] == T && T >= 1 && nelem(t) == t->ne[0] * T && t->nb[1] % 4 == 0 &&
+           t->nb[1] >= (size_t)t->ne[0] * 4;
+}
+
 // ATTN_DECODE / ATTN_BATCH: the caches (src4, src5) exactly [n_ctx][kvw] and [kvw][n_ctx] f16,
 // 16-B aligned (the kernels' addressing), n_ctx a multiple of 32 up to max_ctx (8192; up to
 // kAttnStreamMaxCtx while mi355x_attn_stream is on); pos (src3) i32
@@ -325,6 +332,11 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
             if (nodes[i] == u) return i;
         return -1;
     };
+    // a graph with MoE nodes joins neither the layer engine nor the attention + o-proj fusion
+    bool moe = false;
+    for (int k = 0; k < n; ++k)
+        moe |= nodes[k]->op == MI355X_OP_MOE_ROUTE || nodes[k]->op == MI355X_OP_MUL_MAT_ID ||
+               nodes[k]->op == MI355X_OP_MOE_COMBINE;
     int i = 0, ly_blocks = 0;
     while (i < n) {
         const mi355x_tensor *t = nodes[i];
@@ -332,7 +344,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
         l.first = i;
         l.count = 1;
         int head = i;  // first MUL_MAT of a run
-        if (fuse && layer_match(po, nodes, n, i, readers, l.la)) {
+        if (fuse && !moe && layer_match(po, nodes, n, i, readers, l.la)) {
             l.kind = LaunchKind::Layer;
             l.count = 15;
             l.ly_block = ly_blocks++;
@@ -340,7 +352,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
             i += 15;
             continue;
         }
-        if (fuse && i + 1 < n && attn_oproj_fusable(po, t, nodes[i + 1], readers[i])) {
+        if (fuse && !moe && i + 1 < n && attn_oproj_fusable(po, t, nodes[i + 1], readers[i])) {
             const mi355x_tensor *mm = nodes[i + 1];
             l.kind = LaunchKind::AttnOproj;
             l.count = 2;
@@ -828,6 +840,60 @@ bool supports_op(const mi355x_tensor *op) {
             if (form != MI355X_KV_SHIFT_DISCARD || !vc || dl) return false;
             const int64_t keep = op->op_params[3], discard = op->op_params[4], n_past = op->op_params[5];
             return keep >= 0 && discard >= 1 && keep + discard <= n_past && n_past <= n_ctx && discard < tab->ne[1];
+        }
+        case MI355X_OP_MOE_ROUTE: {
+            // gate_inp f32 [n_embd, n_expert] packed, x f32 [n_embd, T] -> the records I32 [2 * n_used, T]
+            const mi355x_tensor *gi = op->src[0], *x = op->src[1];
+            const int n_used = op->op_params[0];
+            if (!contig_f32(gi) || !contig_f32(x)) return false;
+            const int64_t E = gi->ne[0], ne = gi->ne[1], T = x->ne[1];
+            if (E < 16 || E % 16 || E > 0x7fffffff || ne < 2 || ne > MI355X_MOE_MAX_EXPERTS || nelem(gi) != E * ne ||
+                gi->nb[1] != (size_t)E * 4)
+                return false;
+            if (n_used < 1 || n_used > ne || n_used > MI355X_MOE_MAX_USED) return false;
+            if (x->ne[0] != E || T < 1 || T > 65535 / n_used || nelem(x) != E * T || x->nb[1] % 4 ||
+                x->nb[1] < (size_t)E * 4)
+                return false;
+            return moe_records_ok(op, n_used, T);
+        }
+        case MI355X_OP_MUL_MAT_ID: {
+            // the expert tensor [K, N, n_expert], the activations f32 [K, ne11, T], the MOE_ROUTE node
+            // -> f32 [N, n_used, T] packed
+            const mi355x_tensor *w = op->src[0], *x = op->src[1], *rt = op->src[2];
+            if (!w || !x || !rt || !w->data || !is_kquant(w->type) || !contig_f32(x) || !contig_f32(op)) return false;
+            if (rt->op != MI355X_OP_MOE_ROUTE || rt->ne[0] < 2 || rt->ne[0] % 2) return false;
+            const int64_t K = w->ne[0], N = w->ne[1], ne = w->ne[2], n_used = rt->ne[0] / 2, T = rt->ne[1];
+            if (!moe_records_ok(rt, (int)n_used, T) || n_used > MI355X_MOE_MAX_USED) return false;
+            if (K < MI355X_QK_K || K % MI355X_QK_K || K > MI355X_MUL_MAT_ID_MAX_K || N < 1 || N > 0x7fffffff || ne < 1 ||
+                ne > MI355X_MOE_MAX_EXPERTS || w->ne[3] != 1 || T * n_used > 65535)
+                return false;
+            if (w->nb[0] != mi355x_row_size(w->type, MI355X_QK_K) || w->nb[1] < (size_t)(K / MI355X_QK_K) * w->nb[0] ||
+                w->nb[2] < (size_t)N * w->nb[1])
+                return false;
+            if (w->type != MI355X_TYPE_Q6_K && (((uintptr_t)w->data & 15u) || (w->nb[1] & 15u) || (w->nb[2] & 15u)))
+                return false;
+            if (w->type == MI355X_TYPE_Q6_K && (((uintptr_t)w->data & 1u) || (w->nb[1] & 1u) || (w->nb[2] & 1u)))
+                return false;  // (a Q6_K block at an even address)
+            const int64_t ne11 = x->ne[1];
+            if (x->ne[0] != K || (ne11 != 1 && ne11 != n_used) || x->ne[2] != T || x->ne[3] != 1 ||
+                ((uintptr_t)x->data & 15u) || x->nb[1] % 16 || x->nb[1] < (size_t)K * 4 ||
+                x->nb[2] != (size_t)ne11 * x->nb[1])
+                return false;
+            return op->ne[0] == N && op->ne[1] == n_used && op->ne[2] == T && op->ne[3] == 1 &&
+                   op->nb[1] == (size_t)N * 4 && op->nb[2] == (size_t)N * 4 * n_used;
+        }
+        case MI355X_OP_MOE_COMBINE: {
+            // the experts' outputs f32 [n, n_used, T] packed, the MOE_ROUTE node -> f32 [n, T] packed
+            const mi355x_tensor *ex = op->src[0], *rt = op->src[1];
+            if (!contig_f32(ex) || !rt || rt->op != MI355X_OP_MOE_ROUTE || rt->ne[0] < 2 || rt->ne[0] % 2 ||
+                !contig_f32(op))
+                return false;
+            const int64_t n = ex->ne[0], n_used = rt->ne[0] / 2, T = rt->ne[1];
+            if (!moe_records_ok(rt, (int)n_used, T) || n_used > MI355X_MOE_MAX_USED || T > 65535) return false;
+            if (n < 1 || n > 0x7fffff00 || ex->ne[1] != n_used || ex->ne[2] != T || ex->ne[3] != 1 ||
+                ex->nb[1] != (size_t)n * 4 || ex->nb[2] != (size_t)n * 4 * n_used)
+                return false;
+            return op->ne[0] == n && op->ne[1] == T && nelem(op) == n * T && op->nb[1] == (size_t)n * 4;
         }
         default:
             return false;

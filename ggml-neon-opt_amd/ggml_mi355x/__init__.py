@@ -44,6 +44,12 @@ PENALTY_MAX_LAST_N, LOGIT_BIAS_MAX = 1024, 256
 # [head_dim, n_pos], src3 I32 deltas [n_cells] (DELTAS); op_params: kv_shift_params(...)
 OP_KV_SHIFT = 18
 KV_SHIFT_DELTAS, KV_SHIFT_DISCARD = 0, 1
+# the MoE FFN: MOE_ROUTE src0 gate_inp f32 [n_embd, n_expert], src1 x [n_embd, T], op_params [n_used] -> the records
+# I32 [2 * n_used, T] (ids, then the weights' bits); MUL_MAT_ID src0 the experts [K, N, n_expert], src1 f32
+# [K, 1 or n_used, T], src2 the MOE_ROUTE node -> f32 [N, n_used, T]; MOE_COMBINE src0 f32 [n, n_used, T], src1 the
+# MOE_ROUTE node -> f32 [n, T]
+OP_MOE_ROUTE, OP_MUL_MAT_ID, OP_MOE_COMBINE = 19, 20, 21
+MOE_MAX_EXPERTS, MOE_MAX_USED, MUL_MAT_ID_MAX_K = 64, 8, 16384
 MAX_SRC = 10
 FLAG_OUTPUT = 1
 E_OK, E_INVAL, E_UNSUPPORTED, E_WORKSPACE, E_NODEVICE, E_COMM, E_LAYER = 0, -1, -2, -3, -4, -6, -7
@@ -95,6 +101,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_logprob_workspace_size", "mi355x_logprob_rows",
     "mi355x_penalize_rows",
     "mi355x_kv_shift",
+    "mi355x_moe_route", "mi355x_mul_mat_id_workspace_size", "mi355x_mul_mat_id", "mi355x_moe_combine",
 )
 
 
@@ -328,6 +335,15 @@ def lib():
     if hasattr(L, "mi355x_kv_shift"):
         L.mi355x_kv_shift.argtypes = [ctypes.POINTER(KvShiftDesc), vp]
         L.mi355x_kv_shift.restype = i32
+    if hasattr(L, "mi355x_mul_mat_id"):
+        L.mi355x_moe_route.argtypes = [vp, i64, i32, vp, i64, i64, i32, vp, i64, vp, vp]
+        L.mi355x_moe_route.restype = i32
+        L.mi355x_mul_mat_id_workspace_size.argtypes = [i32, i64, i32, i64]
+        L.mi355x_mul_mat_id_workspace_size.restype = sz
+        L.mi355x_mul_mat_id.argtypes = [i32, vp, i64, i64, sz, sz, i32, vp, i64, i64, vp, i64, i32, i64, vp, vp, sz, vp]
+        L.mi355x_mul_mat_id.restype = i32
+        L.mi355x_moe_combine.argtypes = [vp, i64, i32, i64, vp, i64, vp, vp]
+        L.mi355x_moe_combine.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     if hasattr(L, "mi355x_attn_prompt_precision"):  # (an older library under MI355X_LIB, A/B runs: without it)
@@ -1154,6 +1170,79 @@ def kv_shift(k_cache, table, n_head_kv, head_dim, v_cache=None, delta=None, n_ce
             raise Mi355xError("kv_shift: the DISCARD form needs v_cache, keep, discard and n_past")
         d.form, d.keep, d.discard, d.n_past = KV_SHIFT_DISCARD, keep, discard, n_past
     _check(_lib_with("mi355x_kv_shift").mi355x_kv_shift(ctypes.byref(d), _stream(stream)), "mi355x_kv_shift")
+
+
+def moe_route(gate_inp, x, n_used, records=None, probs=False, stream=None):
+    """mi355x_moe_route: the router of a MoE layer (the exact rule is in include/ggml_mi355x.h). gate_inp: f32
+    cuda [n_expert, n_embd]; x: f32 cuda [T, n_embd] (rows may be strided) or [n_embd]. Returns the records, an
+    int32 cuda tensor [T, >= 2 * n_used] (row t: the ids, then the bits of the weights; `records` to write
+    into, its row stride the record stride), and with probs=True also the probabilities f32 [T, n_expert]."""
+    torch = _torch()
+    _require_device()
+    if x.dim() == 1:
+        x = x[None]
+    if not (gate_inp.is_cuda and gate_inp.dtype == torch.float32 and gate_inp.dim() == 2 and gate_inp.is_contiguous()):
+        raise Mi355xError("moe_route: gate_inp must be a contiguous float32 cuda tensor [n_expert, n_embd]")
+    n_expert, n_embd = gate_inp.shape
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == n_embd and x.stride(1) == 1):
+        raise Mi355xError(f"moe_route: x must be a float32 cuda tensor [T, {n_embd}] with contiguous rows")
+    T = x.shape[0]
+    if records is None:
+        records = torch.zeros((T, 2 * n_used), dtype=torch.int32, device=x.device)
+    if not (records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[0] == T and
+            records.stride(1) == 1):
+        raise Mi355xError("moe_route: records must be an int32 cuda tensor [T, >= 2 * n_used] with contiguous rows")
+    pr = torch.zeros((T, n_expert), dtype=torch.float32, device=x.device) if probs else None
+    _check(_lib_with("mi355x_mul_mat_id").mi355x_moe_route(
+        gate_inp.data_ptr(), n_embd, n_expert, x.data_ptr(), x.stride(0), T, n_used, records.data_ptr(),
+        records.stride(0), pr.data_ptr() if probs else None, _stream(stream)), "mi355x_moe_route")
+    return (records, pr) if probs else records
+
+
+def mul_mat_id(type_, experts, K, x, records, n_used, out=None, stream=None):
+    """mi355x_mul_mat_id: experts: uint8 cuda [n_expert, N, >= row bytes] (the last dim contiguous; the strides are
+    nb02, nb01); x: f32 cuda [T, ne11, K] with ne11 1 or n_used, packed over the tokens; records: moe_route's (the
+    ids are its first n_used words a row). Returns f32 cuda [T, n_used, N]."""
+    torch = _torch()
+    _require_device()
+    if not (experts.is_cuda and experts.dtype == torch.uint8 and experts.dim() == 3 and experts.stride(2) == 1):
+        raise Mi355xError("mul_mat_id: experts must be a uint8 cuda tensor [n_expert, N, row bytes]")
+    n_expert, N = experts.shape[0], experts.shape[1]
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == K and x.stride(2) == 1 and
+            x.stride(0) == x.shape[1] * x.stride(1)):
+        raise Mi355xError(f"mul_mat_id: x must be a float32 cuda tensor [T, ne11, {K}], its rows evenly strided")
+    T, ne11 = x.shape[0], x.shape[1]
+    if not (records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[0] == T and
+            records.stride(1) == 1):
+        raise Mi355xError("mul_mat_id: records must be an int32 cuda tensor [T, >= n_used]")
+    if out is None:
+        out = torch.empty((T, n_used, N), dtype=torch.float32, device=x.device)
+    L = _lib_with("mi355x_mul_mat_id")
+    ws = int(L.mi355x_mul_mat_id_workspace_size(type_, K, n_used, T))
+    workspace = _workspace(ws, x.device, stream) if ws else None
+    _check(L.mi355x_mul_mat_id(type_, experts.data_ptr(), K, N, experts.stride(1), experts.stride(0), n_expert,
+                               x.data_ptr(), ne11, x.stride(1), records.data_ptr(), records.stride(0), n_used, T,
+                               out.data_ptr(), workspace.data_ptr() if ws else None, ws, _stream(stream)),
+           "mi355x_mul_mat_id")
+    return out
+
+
+def moe_combine(ex, records, n_used, out=None, stream=None):
+    """mi355x_moe_combine: ex f32 cuda [T, n_used, n] packed, records moe_route's -> f32 cuda [T, n]."""
+    torch = _torch()
+    _require_device()
+    if not (ex.is_cuda and ex.dtype == torch.float32 and ex.dim() == 3 and ex.shape[1] == n_used and ex.is_contiguous()):
+        raise Mi355xError("moe_combine: ex must be a contiguous float32 cuda tensor [T, n_used, n]")
+    T, _, n = ex.shape
+    if not (records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[0] == T and
+            records.stride(1) == 1):
+        raise Mi355xError("moe_combine: records must be an int32 cuda tensor [T, >= 2 * n_used]")
+    if out is None:
+        out = torch.empty((T, n), dtype=torch.float32, device=ex.device)
+    _check(_lib_with("mi355x_mul_mat_id").mi355x_moe_combine(ex.data_ptr(), n, n_used, T, records.data_ptr(),
+                                                             records.stride(0), out.data_ptr(), _stream(stream)),
+           "mi355x_moe_combine")
+    return out
 
 
 def block_partials(type_, w, K, q8_row, stream=None):

@@ -113,15 +113,24 @@ class GGUFFile:
             raise RuntimeError(f"gguf upload of {name} failed: {rc}")
 
     def to_device(self, name, device="cuda"):
-        """The tensor's bytes in a new torch uint8 device tensor, rows x row_bytes."""
+        """The tensor's bytes in a new torch uint8 device tensor, rows x row_bytes; a 3-D tensor (the
+        experts of a MoE layer, ne = [K, N, n_expert]) keeps its shape: n_expert x N x row_bytes."""
         import torch
+        info = self.tensors[name]
+        t = torch.empty(info["size"], dtype=torch.uint8, device=device)
+        self.upload(name, t.data_ptr(), info["size"], torch.cuda.current_stream(t.device).cuda_stream)
+        return t.view(*self.shape_bytes(name))
+
+    def shape_bytes(self, name):
+        """The shape to_device gives the tensor's bytes: (rows, row_bytes), or for a 3-D tensor
+        (ne[2], ne[1], row_bytes)."""
         info = self.tensors[name]
         rows = 1
         for d in info["ne"][1:]:
             rows *= d
-        t = torch.empty(info["size"], dtype=torch.uint8, device=device)
-        self.upload(name, t.data_ptr(), info["size"], torch.cuda.current_stream(t.device).cuda_stream)
-        return t.view(rows, info["size"] // rows)
+        if info["n_dims"] == 3:
+            return (info["ne"][2], info["ne"][1], info["size"] // rows)
+        return (rows, info["size"] // rows)
 
     def close(self):
         if self.h:

@@ -14,6 +14,8 @@ Per layer:
   rms_norm(x)*attn_norm -> q, k, v (MUL_MAT) -> attention (rope, f16 KV cache, KQ,
   soft_max, KQV) -> attn_output (MUL_MAT) -> +x -> rms_norm*ffn_norm ->
   gate, up (MUL_MAT) -> swiglu -> down (MUL_MAT) -> +ffn_inp
+  (a MoE model, hp["n_expert"] > 0: after ffn_norm, MOE_ROUTE -> up, gate (MUL_MAT_ID) -> swiglu ->
+  down (MUL_MAT_ID) -> MOE_COMBINE -> +ffn_inp: build_moe_ffn, the experts chosen on the device)
 then rms_norm*output_norm -> output (MUL_MAT) -> logits.
 
 LlamaDecoder's entry points and the graph each runs; all of them are emitted by the one
@@ -41,9 +43,9 @@ import ctypes
 
 from . import (ARGMAX_STEP_INPUTS, BLOCK_BYTES, FLAG_OUTPUT, LOGIT_BIAS_MAX, LOGPROB_MAX_N, OP_ADD, OP_ALL_GATHER,
                OP_ALL_REDUCE, OP_ARGMAX, OP_ARGMAX_BATCH, OP_ATTN_BATCH, OP_ATTN_DECODE, OP_GET_ROWS, OP_KV_SHIFT,
-               OP_LOGPROB_BATCH, OP_MUL, OP_MUL_MAT, OP_PENALIZE, OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU,
-               PENALTY_MAX_LAST_N, QK_K, SAMPLE_MAX_K, SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32, TYPE_I32, Backend,
-               Mi355xError, bias_pairs, f32_bits, kv_shift_params, logprob_dtype, logprob_value, make_tensor,
+               OP_LOGPROB_BATCH, OP_MOE_COMBINE, OP_MOE_ROUTE, OP_MUL, OP_MUL_MAT, OP_MUL_MAT_ID, OP_PENALIZE,
+               OP_RMS_NORM, OP_SAMPLE, OP_SAMPLE_BATCH, OP_SWIGLU, PENALTY_MAX_LAST_N, QK_K, SAMPLE_MAX_K,
+               SAMPLE_STEP_INPUTS, TYPE_F16, TYPE_F32, TYPE_I32, Backend, Mi355xError, bias_pairs, f32_bits, kv_shift_params, logprob_dtype, logprob_value, make_tensor,
                penalize_params, rope_table, sampler_params)
 
 
@@ -53,11 +55,40 @@ def torch_tensor(values):
 
 
 LAYER_MATS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+# a MoE layer (hp["n_expert"] > 0): the attention's matrices, then the router (f32) and the expert tensors
+MOE_LAYER_MATS = LAYER_MATS[:4] + ("ffn_gate_exps", "ffn_up_exps", "ffn_down_exps")
+MOE_ROUTER = "ffn_gate_inp"
 
 
-def hparams(n_embd, n_layer, n_head, n_head_kv, n_ff, n_vocab, eps=1e-5, freq_base=10000.0):
-    return dict(n_embd=n_embd, n_layer=n_layer, n_head=n_head, n_head_kv=n_head_kv, head_dim=n_embd // n_head,
-                n_ff=n_ff, n_vocab=n_vocab, eps=eps, freq_base=freq_base)
+def hparams(n_embd, n_layer, n_head, n_head_kv, n_ff, n_vocab, eps=1e-5, freq_base=10000.0, n_expert=0,
+            n_expert_used=0):
+    """n_expert > 0: every layer's FFN is the MoE arm (llama.expert_count / llama.expert_used_count; n_ff is one
+    expert's width). A dense model's dict has no MoE keys: it is the dict of before."""
+    hp = dict(n_embd=n_embd, n_layer=n_layer, n_head=n_head, n_head_kv=n_head_kv, head_dim=n_embd // n_head,
+              n_ff=n_ff, n_vocab=n_vocab, eps=eps, freq_base=freq_base)
+    if n_expert:
+        if not 1 <= n_expert_used <= n_expert:
+            raise Mi355xError(f"hparams: n_expert_used {n_expert_used} must lie in [1, n_expert {n_expert}]")
+        hp.update(n_expert=int(n_expert), n_expert_used=int(n_expert_used))
+    return hp
+
+
+def layer_mats(hp):
+    """The names of a layer's K-quant tensors: LAYER_MATS, or for a MoE model MOE_LAYER_MATS."""
+    return MOE_LAYER_MATS if hp.get("n_expert", 0) else LAYER_MATS
+
+
+def gguf_hparams(f):
+    """hparams of an open llama-architecture GGUFFile, the MoE keys included; None if it is not one."""
+    arch = f.kv.get("general.architecture", "llama")
+    kv = lambda k, d=None: f.kv.get(f"{arch}.{k}", d)  # noqa: E731
+    E, L, nh = kv("embedding_length"), kv("block_count"), kv("attention.head_count")
+    if arch != "llama" or None in (E, L, nh) or "token_embd.weight" not in f.tensors:
+        return None
+    return hparams(E, L, nh, kv("attention.head_count_kv", nh), kv("feed_forward_length"),
+                   f.tensors["token_embd.weight"]["ne"][1], eps=kv("attention.layer_norm_rms_epsilon", 1e-5),
+                   freq_base=kv("rope.freq_base", 10000.0), n_expert=kv("expert_count", 0),
+                   n_expert_used=kv("expert_used_count", 0))
 
 
 TINYLLAMA = hparams(2048, 22, 32, 4, 5632, 32000)
@@ -188,6 +219,43 @@ class _Graph:
         t, w = self.w[name]
         return self.leaf(w, t, w.shape[1] // BLOCK_BYTES[t] * QK_K, w.shape[0], row_stride=w.stride(0))
 
+    def experts(self, name):
+        """The leaf of an expert tensor (type, uint8 [n_expert, rows, rowbytes]): ne = [K, rows, n_expert]."""
+        t, w = self.w[name]
+        x = self.leaf(w, t, w.shape[2] // BLOCK_BYTES[t] * QK_K, w.shape[1], row_stride=w.stride(1))
+        x.ne[2], x.nb[2], x.nb[3] = w.shape[0], w.stride(0), w.stride(0) * w.shape[0]
+        return x
+
+    def rows3(self, x, ne1, ne2):
+        """x's descriptor reshaped in place to [ne0, ne1, ne2] packed (ne1 * ne2 its rows); returns x."""
+        assert x.ne[1] == ne1 * ne2 and x.ne[2] == 1
+        x.ne[1], x.ne[2], x.nb[2], x.nb[3] = ne1, ne2, x.nb[1] * ne1, x.nb[1] * ne1 * ne2
+        return x
+
+    def moe_ffn(self, p, cur):
+        """build_moe_ffn over cur's T rows in upstream's order [U]: route, up, gate, swiglu, down, combine.
+        Returns the combined output's node (f32 [n_embd, T])."""
+        import torch
+        hp = self.hp
+        E, ne, nu, T = hp["n_embd"], hp["n_expert"], hp["n_expert_used"], cur.ne[1]
+        gi = self.leaf(self.w[p + MOE_ROUTER], TYPE_F32, E, ne)
+        rec = torch.zeros(2 * nu * T, dtype=torch.int32, device=self.dev)  # per row: ids, then the weights' bits
+        self.bufs.append(rec)
+        route = make_tensor(TYPE_I32, 2 * nu, T, rec.data_ptr(), op=OP_MOE_ROUTE, srcs=[gi, cur], op_params=[nu])
+        self.tensors.append(route)
+        self.nodes.append(route)
+        cur3 = self.rows3(make_tensor(TYPE_F32, E, T, cur.data), 1, T)  # one row a token, for every slot
+        self.tensors.append(cur3)
+
+        def mm_id(name, x):
+            wt = self.experts(p + name)
+            return self.rows3(self.node(OP_MUL_MAT_ID, wt.ne[1], [wt, x, route], ne1=nu * T)[0], nu, T)
+
+        up, gate = mm_id("ffn_up_exps", cur3), mm_id("ffn_gate_exps", cur3)
+        par = self.rows3(self.node(OP_SWIGLU, up.ne[0], [gate, up], ne1=nu * T)[0], nu, T)
+        ex = mm_id("ffn_down_exps", par)
+        return self.node(OP_MOE_COMBINE, E, [ex, route], ne1=T)[0]
+
     def mm(self, name, x, flags=0):
         wt = self.mat(name)
         return self.node(OP_MUL_MAT, wt.ne[1], [wt, x], flags=flags, ne1=x.ne[1])
@@ -215,6 +283,11 @@ class LlamaDecoder:
     weights: dict with "token_embd", "output", "output_norm" and per layer i
     "blk.{i}.<name>" for name in LAYER_MATS + ("attn_norm", "ffn_norm"); a K-quant
     matrix is (type, uint8 cuda tensor [rows, rowbytes]), a norm is an f32 cuda tensor.
+    A MoE model (hp["n_expert"] > 0, Mixtral) has per layer, in place of ffn_gate / ffn_up / ffn_down,
+    "blk.{i}.ffn_gate_inp", an f32 cuda tensor [n_expert, n_embd], and "blk.{i}.ffn_gate_exps" /
+    "ffn_up_exps" / "ffn_down_exps", (type, uint8 cuda tensor [n_expert, rows, rowbytes]); its FFN is
+    the MOE_ROUTE / MUL_MAT_ID / MOE_COMBINE nodes, in every graph (they all come from the one layer
+    body). A MoE model takes no row split.
 
     split: a rowsplit.TokenSplit — this process is one rank of a row split; the
     matrices in `weights` are then the rank's row slices (TokenSplit.slice_weights),
@@ -235,6 +308,8 @@ class LlamaDecoder:
         "table": the whole table (what mi355x_lower_ggml_graph passes)."""
         import torch
         self.b, self.hp, self.w, self.n_ctx, self.split = backend, hp, weights, n_ctx, split
+        if split is not None and hp.get("n_expert", 0):
+            raise Mi355xError("a MoE model runs on one GPU (no row split)")
         dev = weights["output_norm"].device
         hd = hp["head_dim"]
         kvw = (split.n_head_kv if split is not None else hp["n_head_kv"]) * hd  # this rank's KV heads
@@ -353,6 +428,9 @@ class LlamaDecoder:
             last_rows = out_ids if i == hp["n_layer"] - 1 and x.ne[1] > 1 else None
             ffn_inp, fb = project(p + "attn_output", att, nh * hd, x, xb, select=last_rows)
             m2 = g.norm(ffn_inp, p + "ffn_norm")
+            if hp.get("n_expert", 0):  # llm_build_llama's MoE arm: build_moe_ffn, then + ffn_inp
+                x, xb = g.node(OP_ADD, E, [g.moe_ffn(p, m2), ffn_inp], ne1=m2.ne[1])
+                continue
             gt, up = g.mm(p + "ffn_gate", m2)[0], g.mm(p + "ffn_up", m2)[0]
             glu, _ = g.node(OP_SWIGLU, gt.ne[0], [gt, up], ne1=gt.ne[1])
             x, xb = project(p + "ffn_down", glu, F // world, ffn_inp, fb)

@@ -744,6 +744,81 @@ typedef struct {
 } mi355x_kv_shift_desc;
 int mi355x_kv_shift(const mi355x_kv_shift_desc *d, void *stream);
 
+/* Mixture of experts on the device: the MoE arm of llm_build_llama (build_moe_ffn [U], taken when
+ * llama.expert_count > 0: Mixtral). Three launches' worth of entry points (csrc/kq_moe.hip): the
+ * router, the expert matmul whose weight base is data (ggml's MUL_MAT_ID) and the weighted sum.
+ * No atomics, no workgroup waits for another. The rule (exact: the same bits as tests/moe_ref.py)
+ * for one row `cur` of n_embd floats, T rows independently:
+ *   logits[e] = vec_dot_f32(gate_inp[e], cur) in ggml_vec_dot_f32's NEON order [U]: 4 accumulators
+ *     of 4 lanes stepping 16 floats, acc[j][l] = fma(g[16 s + 4 j + l], cur[16 s + 4 j + l],
+ *     acc[j][l]); then acc0 += acc2, acc1 += acc3, acc0 += acc1, and (l0 + l1) + (l2 + l3).
+ *     n_embd % 16 == 0: there is no scalar tail.
+ *   probs = soft_max(logits), no mask, scale 1 (ggml_compute_forward_soft_max_f32 [U]): the max,
+ *     e_i = ggml_v_expf(logits_i - max) for i < (n_expert & ~3) with their sums (e0 + e1) + (e2 + e3)
+ *     added to a double in order, e_i = expf(logits_i - max) (libm) for the rest, added one by one;
+ *     probs_i = e_i * (float)(1.0 / sum).
+ *   ids = the first n_used entries of ggml's descending argsort of probs [U], the exchange sort
+ *     `for i: for j > i: if p[idx[i]] < p[idx[j]]: swap(idx[i], idx[j])` from idx = 0 .. n - 1.
+ *     Exact ties follow that sort, which is not "smallest index first".
+ *   w[s] = probs[ids[s]]; w[s] /= (float)(w[0] + w[1] + ... in a double, in slot order) (norm_w; no
+ *     scale_w, no clamp).
+ *   up = mul_mat_id(up_exps, cur, ids); gate = mul_mat_id(gate_exps, cur, ids);
+ *   par = swiglu(gate, up); ex = mul_mat_id(down_exps, par, ids), where for token t and slot s
+ *     dst[:, s, t] = W[ids[s, t]] . q8_K(src1[:, s % ne11, t]): every row by mi355x_mul_mat's rule.
+ *   out = ex[:, 0] * w[0]; out = out + ex[:, s] * w[s] for s = 1 .., each product and sum rounded
+ *     once, in slot order.
+ * NaN router logits are unspecified.
+ *
+ * mi355x_moe_route: gate_inp f32 [n_expert][n_embd] packed; x: T rows of n_embd floats, x_stride
+ * floats apart; record_out: per row one record of int32 ids[n_used] followed by float w[n_used]
+ * (8 * n_used bytes), record_stride 32-bit words apart (>= 2 * n_used; the words between two
+ * records are not written); probs_out: NULL, or f32 [T][n_expert] packed, the probabilities (tests).
+ * One launch, one workgroup a row. 2 <= n_expert <= 64, 1 <= n_used <= min(n_expert, 8),
+ * n_embd % 16 == 0, else MI355X_E_UNSUPPORTED. MI355X_E_INVAL for a null or misaligned (4 bytes)
+ * pointer, n_embd, n_expert or n_used < 1, n_used > n_expert, T < 0, x_stride < n_embd (T > 1) or
+ * record_stride < 2 * n_used; T == 0 returns MI355X_OK with no launch; then MI355X_E_NODEVICE.
+ *
+ * mi355x_mul_mat_id: experts: n_expert matrices of ne01 rows of ne00 K-quant values (Q4_K, Q5_K,
+ * Q6_K), nb01 bytes between rows and nb02 between experts; x: f32 [ne00, ne11, T], rows
+ * x_row_stride floats apart (row t * ne11 + r), 16-byte aligned rows; ne11 == 1 gives every slot
+ * of a token its one row (up, gate), ne11 == n_used one row per slot (down); ids: device int32,
+ * ids[t * ids_stride + s] the expert of token t's slot s (a MOE_ROUTE record: ids_stride its
+ * record_stride), read on the device by every launch; y: f32 [ne01, n_used, T] packed. One launch
+ * of kq_gemv_id, a workgroup per (token, slot) pair and block of rows; only the selected experts'
+ * rows are read. An id outside [0, n_expert) writes NaN to that pair's ne01 outputs and reads
+ * nothing for it: never a silent result. Q4_K / Q5_K: experts, nb01 and nb02 multiples of 16; a
+ * Q6_K tensor may stand at any even address with any even strides (nb02 need not be a multiple of
+ * 16): what ggml's 210-byte block_q6_K of 2-byte members can produce. ne00 <= 16384, n_expert <= 64,
+ * n_used <= 8, T * n_used <= 65535, else MI355X_E_UNSUPPORTED (as an unknown type).
+ * MI355X_E_INVAL for a null pointer, x not 16-byte or ids / y not 4-byte aligned, ne00 < 1 or not
+ * a multiple of 256, ne01 < 0, n_expert, n_used < 1, T < 0, ne11 neither 1 nor n_used,
+ * x_row_stride not a multiple of 4 or < ne00 (more than one row), ids_stride < n_used, nb01 below
+ * a row's bytes, nb02 < ne01 * nb01 (n_expert > 1), a misaligned Q4_K / Q5_K matrix, an odd Q6_K address or stride; then
+ * MI355X_E_UNSUPPORTED; then MI355X_E_WORKSPACE (workspace_size below
+ * mi355x_mul_mat_id_workspace_size, which is 0 today: the activation rows are quantized in the
+ * launch's prologue, and workspace may be NULL); T == 0 or ne01 == 0 returns MI355X_OK with no
+ * launch; then MI355X_E_NODEVICE.
+ *
+ * mi355x_moe_combine: ex f32 [n, n_used, T] packed, records / record_stride as mi355x_moe_route
+ * wrote them (the weights are read at words [n_used, 2 n_used) of a record), y f32 [n, T] packed.
+ * One elementwise launch. MI355X_E_INVAL for a null or misaligned (4 bytes) pointer, n < 0,
+ * n_used < 1, T < 0 or record_stride < 2 * n_used; MI355X_E_UNSUPPORTED for n_used > 8 or
+ * T > 65535; n == 0 or T == 0 returns MI355X_OK with no launch; then MI355X_E_NODEVICE.
+ * All statuses come before any device access. */
+#define MI355X_MOE_MAX_EXPERTS 64
+#define MI355X_MOE_MAX_USED 8
+#define MI355X_MUL_MAT_ID_MAX_K 16384
+int mi355x_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const float *x, int64_t x_stride, int64_t T,
+                     int n_used, int32_t *record_out, int64_t record_stride, float *probs_out /* nullable */,
+                     void *stream);
+size_t mi355x_mul_mat_id_workspace_size(int type, int64_t ne00, int n_used, int64_t T);
+int mi355x_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01, size_t nb01, size_t nb02,
+                      int n_expert, const float *x, int64_t ne11, int64_t x_row_stride, const int32_t *ids,
+                      int64_t ids_stride, int n_used, int64_t T, float *y, void *workspace, size_t workspace_size,
+                      void *stream);
+int mi355x_moe_combine(const float *ex, int64_t n, int n_used, int64_t T, const int32_t *records, int64_t record_stride,
+                       float *y, void *stream);
+
 /* --------------------------------------------- ggml-backend mirror (C++) */
 /* A minimal mirror of ggml-backend's device/buffer/graph interface
  * (ggml-backend-impl.h [U]; CPU sibling ggml-cpu.cpp:186, README.md:162),
@@ -854,7 +929,22 @@ int mi355x_kv_shift(const mi355x_kv_shift_desc *d, void *stream);
  *                discard, n_past} (DISCARD), with mi355x_kv_shift's ranges; any n_ctx >= 1. Launches
  *                of its own in graph order (none for an empty range), never fused, elided or moved
  *                across an attention node on the same caches; captured and replayed like any node
- *                (every replay shifts again): the deltas are read on the device at run time. */
+ *                (every replay shifts again): the deltas are read on the device at run time.
+ *   MOE_ROUTE    mi355x_moe_route: src0 gate_inp f32 [n_embd, n_expert] packed, src1 x f32
+ *                [n_embd, T] (nb[1] the row stride); op_params = {n_used} -> I32 [2 * n_used, T]
+ *                (nb[1] the record stride): row t the record of token t, ids then the weights' bits.
+ *   MUL_MAT_ID   mi355x_mul_mat_id: src0 the expert tensor, K-quant [K, N, n_expert] (ne[2] the
+ *                experts, nb[1], nb[2]), src1 the activations f32 [K, ne11, T] with ne11 1 or n_used
+ *                and packed rows of rows (nb[2] = ne11 * nb[1]), src2 the MOE_ROUTE node (its
+ *                ne[0] / 2 is n_used) -> f32 [N, n_used, T] packed.
+ *   MOE_COMBINE  mi355x_moe_combine: src0 the experts' outputs f32 [n, n_used, T] packed, src1 the
+ *                MOE_ROUTE node -> f32 [n, T] packed.
+ *                The three MoE nodes get launches of their own in graph order and are never fused or
+ *                elided; a graph that holds one of them takes neither the layer engine nor the
+ *                attention + o-proj fusion anywhere (whatever the backend's switches say). They are
+ *                captured and replayed like any node: the ids and weights are read on the device
+ *                at every replay. They count as readers of their sources, so an RMS_NORM -> MUL
+ *                pair they read is materialised. */
 enum mi355x_op {
     MI355X_OP_NONE = 0, MI355X_OP_MUL_MAT = 1, MI355X_OP_GET_ROWS = 2, MI355X_OP_RMS_NORM = 3,
     MI355X_OP_MUL = 4, MI355X_OP_ADD = 5, MI355X_OP_SWIGLU = 6, MI355X_OP_ROPE = 7,
@@ -862,6 +952,7 @@ enum mi355x_op {
     MI355X_OP_ATTN_BATCH = 11, MI355X_OP_ARGMAX = 12, MI355X_OP_ARGMAX_BATCH = 13,
     MI355X_OP_SAMPLE = 14, MI355X_OP_SAMPLE_BATCH = 15, MI355X_OP_LOGPROB_BATCH = 16,
     MI355X_OP_PENALIZE = 17, MI355X_OP_KV_SHIFT = 18,
+    MI355X_OP_MOE_ROUTE = 19, MI355X_OP_MUL_MAT_ID = 20, MI355X_OP_MOE_COMBINE = 21,
 };
 #define MI355X_MAX_SRC 10  /* GGML_MAX_SRC */
 #define MI355X_TENSOR_FLAG_OUTPUT 1  /* read by the caller after graph_compute: never elided by fusion */

@@ -30,7 +30,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import ggml_mi355x as g  # noqa: E402
-from ggml_mi355x.llama import LAYER_MATS, LlamaDecoder, hparams, ppl_of  # noqa: E402
+from ggml_mi355x.llama import MOE_ROUTER, LlamaDecoder, gguf_hparams, layer_mats, ppl_of  # noqa: E402
 
 KQUANTS = (g.TYPE_Q4_K, g.TYPE_Q5_K, g.TYPE_Q6_K)
 
@@ -39,14 +39,10 @@ def load_gguf(path, dev):
     """(hparams, LlamaDecoder's weights dict on the device) of a llama-architecture GGUF file."""
     from ggml_mi355x.gguf import GGUFFile
     with GGUFFile(path) as f:
-        arch = f.kv.get("general.architecture", "llama")
-        kv = lambda k, d=None: f.kv.get(f"{arch}.{k}", d)  # noqa: E731
-        E, L, nh = kv("embedding_length"), kv("block_count"), kv("attention.head_count")
-        if arch != "llama" or None in (E, L, nh):
+        hp = gguf_hparams(f)  # (llama.expert_count > 0: a MoE model, its layers' FFN the expert tensors)
+        if hp is None:
             raise SystemExit(f"{path}: not a llama-architecture model file")
-        V = f.tensors["token_embd.weight"]["ne"][1]
-        hp = hparams(E, L, nh, kv("attention.head_count_kv", nh), kv("feed_forward_length"), V,
-                     eps=kv("attention.layer_norm_rms_epsilon", 1e-5), freq_base=kv("rope.freq_base", 10000.0))
+        L = hp["n_layer"]
 
         def mat(name, table=False):
             t = f.tensors[name]["type"]
@@ -62,8 +58,10 @@ def load_gguf(path, dev):
         w = {"token_embd": mat("token_embd.weight", table=True), "output_norm": vec("output_norm.weight")}
         w["output"] = mat("output.weight" if "output.weight" in f.tensors else "token_embd.weight")  # (tied embeddings)
         for i in range(L):
-            for m in LAYER_MATS:
+            for m in layer_mats(hp):
                 w[f"blk.{i}.{m}"] = mat(f"blk.{i}.{m}.weight")
+            if hp.get("n_expert", 0):  # the router, f32 [n_expert, n_embd]
+                w[f"blk.{i}.{MOE_ROUTER}"] = vec(f"blk.{i}.{MOE_ROUTER}.weight").view(hp["n_expert"], hp["n_embd"])
             for n in ("attn_norm", "ffn_norm"):
                 w[f"blk.{i}.{n}"] = vec(f"blk.{i}.{n}.weight")
         torch.cuda.synchronize()
