@@ -71,7 +71,7 @@ const KnobDef kKnobs[KNOB_COUNT] = {
     {"MMF_ORDER", 0},  {"ATTN_DIAG", 0},     {"LOOPBACK_NOCOPY", 0}, {"ATTN_OPROJ", 1},
     {"AO_NRB", 0},     {"GEMV_DYN", 8},    {"GEMV_DYN_P", 0},      {"GEMV_DYN_STEPS", 16},
     {"GEMV_SHORT", 1}, {"ATTN_STREAM", -1},  {"ATTN_STREAM_TILE", 0},
-    {"ARGMAX_SLICE", 0},
+    {"ARGMAX_SLICE", 0}, {"MMQ_ID_Q6", 0},
 };
 std::atomic<double> g_knob[KNOB_COUNT];
 std::atomic<bool> g_knob_set[KNOB_COUNT];

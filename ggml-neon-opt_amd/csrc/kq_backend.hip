@@ -60,6 +60,8 @@ struct mi355x_backend {
     size_t am_size = 0;      // allocation; every launch leaves them ready for the next
     void *sm = nullptr;      // the SAMPLE / SAMPLE_BATCH nodes' counters and words (kq_sample.hip), as am
     size_t sm_size = 0;
+    void *mg = nullptr;      // the grouped MUL_MAT_ID nodes' group table (kq_moe_group): one, rebuilt per MOE_ROUTE
+    size_t mg_size = 0;      // node; the Q8L rows share the workspace with the other GEMMs
     bool layer_engine = false;  // each decode layer as one persistent launch (kq_layer.hip)
     uint32_t *ly_sync = nullptr;  // the persistent layers' counter blocks (zeroed at allocation), then err
     int ly_blocks = 0;
@@ -255,6 +257,40 @@ int enqueue_batched_mm(mi355x_backend *b, const mi355x_tensor *t, Q8State &q8, f
     return rc;
 }
 
+// the (token, slot) pairs of a MUL_MAT_ID node: T * n_used of its MOE_ROUTE records
+int64_t id_pairs(const mi355x_tensor *t) { return t->src[2]->ne[1] * (t->src[2]->ne[0] / 2); }
+
+// A MUL_MAT_ID node, the expert ids read on the device at every replay. In the grouped form
+// (kq::moe_grouped) the group table in b->mg is built by the first consumer of a MOE_ROUTE node
+// (`table_of`: the node whose table b->mg holds) and read by the others, and up and gate, which
+// share src1, quantize it once (q8).
+int enqueue_mul_mat_id(mi355x_backend *b, const mi355x_tensor *t, Q8State &q8, const mi355x_tensor *&table_of) {
+    const mi355x_tensor *w = t->src[0], *x = t->src[1], *rt = t->src[2];
+    const int64_t K = w->ne[0], rows = x->ne[1] * x->ne[2];
+    kq::MoeGrouped gr = {(int32_t *)b->mg, b->mg_size, (uint8_t *)b->workspace, b->workspace_size, true, true};
+    const bool grouped = kq::moe_grouped(id_pairs(t));
+    if (grouped) {
+        // (ensure_workspace sized both for this node under the mode of this plan key)
+        if (b->mg_size < kq::moe_table_bytes(id_pairs(t)) || b->workspace_size < kq::moe_q8_bytes(K, rows))
+            return MI355X_E_WORKSPACE;
+        gr.build = table_of != rt;
+        gr.quantize = !q8.holds(x, K, rows, false);
+    }
+    if (!grouped || gr.quantize) q8 = Q8State();
+    const int rc = kq::launch_mul_mat_id(w->type, w->data, K, w->ne[1], w->nb[1], w->nb[2], (int)w->ne[2],
+                                         (const float *)x->data, x->ne[1], (int64_t)(x->nb[1] / 4),
+                                         (const int32_t *)rt->data, (int64_t)(rt->nb[1] / 4), (int)(rt->ne[0] / 2),
+                                         rt->ne[1], (float *)t->data, b->stream, &gr);
+    if (rc || !grouped) {
+        q8 = Q8State();
+        return rc;
+    }
+    table_of = rt;
+    q8.set(x, K, rows, false);
+    q8.drop_if_overlaps((const float *)t->data, w->ne[1], id_pairs(t));
+    return 0;
+}
+
 // The matrices of one multi-matrix tile-GEMM launch, in launch order
 struct MatSet {
     const void *w[4];
@@ -411,14 +447,7 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
                                         (int64_t)(x->nb[1] / 4), x->ne[1], t->op_params[0], (int32_t *)t->data,
                                         (int64_t)(t->nb[1] / 4), nullptr, st);
         }
-        case MI355X_OP_MUL_MAT_ID: {  // the expert ids read on the device at every replay
-            const mi355x_tensor *w = t->src[0], *x = t->src[1], *rt = t->src[2];
-            return kq::launch_mul_mat_id(w->type, w->data, w->ne[0], w->ne[1], w->nb[1], w->nb[2], (int)w->ne[2],
-                                         (const float *)x->data, x->ne[1], (int64_t)(x->nb[1] / 4),
-                                         (const int32_t *)rt->data, (int64_t)(rt->nb[1] / 4), (int)(rt->ne[0] / 2),
-                                         rt->ne[1], (float *)t->data, st);
-        }
-        case MI355X_OP_MOE_COMBINE: {
+        case MI355X_OP_MOE_COMBINE: {  // (MUL_MAT_ID: enqueue_mul_mat_id)
             const mi355x_tensor *ex = t->src[0], *rt = t->src[1];
             return kq::launch_moe_combine((const float *)ex->data, ex->ne[0], (int)(rt->ne[0] / 2), rt->ne[1],
                                           (const int32_t *)rt->data, (int64_t)(rt->nb[1] / 4), (float *)t->data, st);
@@ -440,6 +469,7 @@ int enqueue_node(mi355x_backend *b, const Launch &l, const mi355x_tensor *t) {
 int enqueue(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<Launch> &launches) {
     Q8State q8;
     const mi355x_tensor *kv_done = nullptr;  // prompt ATTN whose KV cells a GEMM epilogue stored
+    const mi355x_tensor *table_of = nullptr;  // the MOE_ROUTE node whose group table b->mg holds
     if (!kq::device_ok()) return MI355X_E_NODEVICE;
     const kq::PlanOpts po = plan_opts(b);
     for (size_t li = 0; li < launches.size(); ++li) {
@@ -551,6 +581,11 @@ int enqueue(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<La
             if (rc) return rc;
             continue;
         }
+        if (l.kind == LaunchKind::Node && t->op == MI355X_OP_MUL_MAT_ID) {
+            rc = enqueue_mul_mat_id(b, t, q8, table_of);
+            if (rc) return rc;
+            continue;
+        }
         q8 = Q8State();  // any other launch may overwrite the workspace or the activation
         if (l.kind == LaunchKind::GemvRun) {
             const mi355x_tensor *w = t->src[0];
@@ -600,11 +635,17 @@ int grow_buffer(mi355x_backend *b, void **buf, size_t *size, size_t need, bool z
     return MI355X_OK;
 }
 
-// every node supported; the workspace grown to the largest MUL_MAT's need
+// every node supported; the workspace grown to the largest MUL_MAT's need, or the Q8L rows of the
+// largest MUL_MAT_ID that takes the grouped form, whose group table gets a buffer of its own
 int ensure_workspace(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes) {
-    size_t ws = 0;
+    size_t ws = 0, mg = 0;
     for (int i = 0; i < n_nodes; ++i) {
         if (!mi355x_backend_supports_op(nodes[i])) return MI355X_E_UNSUPPORTED;
+        if (nodes[i]->op == MI355X_OP_MUL_MAT_ID && kq::moe_grouped(id_pairs(nodes[i]))) {
+            const mi355x_tensor *x = nodes[i]->src[1];
+            ws = std::max(ws, kq::moe_q8_bytes(x->ne[0], x->ne[1] * x->ne[2]));
+            mg = std::max(mg, kq::moe_table_bytes(id_pairs(nodes[i])));
+        }
         if (nodes[i]->op == MI355X_OP_MUL_MAT) {
             const mi355x_tensor *w = nodes[i]->src[0];
             size_t need = mi355x_mul_mat_workspace_size(w->type, w->ne[0], w->ne[1], nodes[i]->src[1]->ne[1]);
@@ -615,7 +656,8 @@ int ensure_workspace(mi355x_backend *b, mi355x_tensor *const *nodes, int n_nodes
             ws = need > ws ? need : ws;
         }
     }
-    return grow_buffer(b, &b->workspace, &b->workspace_size, ws, false);
+    const int rc = grow_buffer(b, &b->mg, &b->mg_size, mg, false);
+    return rc ? rc : grow_buffer(b, &b->workspace, &b->workspace_size, ws, false);
 }
 
 // the fused attention + o-proj launches' buffer: sized, and its counters zeroed
@@ -888,6 +930,7 @@ void mi355x_backend_free(mi355x_backend_t b) {
     if (b->fx) hipFree(b->fx);
     if (b->am) hipFree(b->am);
     if (b->sm) hipFree(b->sm);
+    if (b->mg) hipFree(b->mg);
     if (b->ly_sync) hipFree(b->ly_sync);
     for (auto &t : b->ly_tabs)
         if (t.dev) hipFree(t.dev);

@@ -372,6 +372,33 @@ struct MmqArgs {
     int64_t my_col_stride[4];
 };
 
+// ---------------------------------------------------------------- expert-grouped MoE prefill
+// The group table kq_moe_group (kq_moe.hip) builds from a MOE_ROUTE node's ids at every launch and
+// kq_mmq_id (kq_mmq.hip) reads: int32 words. Bucket e < n_expert holds the (token, slot) pairs
+// routed to expert e, bucket n_expert those whose id lies outside the table. Per bucket the pair
+// count, the bucket's first entry in the sorted lists and its first column tile, for tiles of 64
+// and of 128 columns (prefixes of ceil(count / 64) and ceil(count / 128); entry n_expert + 1 is
+// the total). Then the two sorted lists of
+// `pairs` entries each: the pair index p = t * n_used + s (the output row, and the activation
+// row of an ne11 == n_used source) and the token t (the activation row of an ne11 == 1 source),
+// so the GEMM divides nothing. The order of the pairs inside a bucket is unspecified.
+constexpr int MOE_BUCKETS = MI355X_MOE_MAX_EXPERTS + 1;
+constexpr int MOE_TAB_COUNT = 0, MOE_TAB_FIRST = 72, MOE_TAB_TILE0 = 144, MOE_TAB_TILE0W = 216, MOE_TAB_LIST = 288;
+__host__ __device__ constexpr int moe_tab_tile0(int cw) { return cw == 2 ? MOE_TAB_TILE0W : MOE_TAB_TILE0; }  // kq_mmq_id's CW
+static_assert(MOE_TAB_FIRST >= MOE_BUCKETS && MOE_TAB_TILE0 >= MOE_TAB_FIRST + MOE_BUCKETS &&
+                  MOE_TAB_TILE0W >= MOE_TAB_TILE0 + MOE_BUCKETS + 1 && MOE_TAB_LIST >= MOE_TAB_TILE0W + MOE_BUCKETS + 1,
+              "the four per-bucket arrays before the lists");
+__host__ __device__ constexpr int64_t moe_table_words(int64_t pairs) { return MOE_TAB_LIST + 2 * pairs; }
+// kq_mmq_id: what differs from kq_mmq. Of MmqArgs: w the expert tensor's base, m_cols unused
+// (a tile's columns end with its bucket), y_col_stride the rows of an expert (y packed).
+struct MmqIdArgs {
+    const int32_t *tab;   // the group table
+    const int32_t *xrow;  // sorted entry -> Q8L row of the workspace (the token or the pair list)
+    const int32_t *pair;  // sorted entry -> pair index: its outputs at y + pair * y_col_stride
+    int64_t nb02;         // bytes between experts
+    int n_expert;
+};
+
 // ------------------------------------------- batched (prefill) f16 MFMA GEMM, stated tolerance
 // kq_mmf (MI355X_PREFILL_F16): 128 weight rows x 128 activation columns per 4-wave
 // workgroup, K in half-superblock steps. The activation goes through kq_quantize_f16img

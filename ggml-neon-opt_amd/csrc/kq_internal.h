@@ -44,12 +44,13 @@ enum Knob {
     KNOB_ATTN_STREAM,      // 0 / 1 / 2: overrides mi355x_attn_stream's mode (-1: the selector's own value)
     KNOB_ATTN_STREAM_TILE, // streamed prompt attention: tokens per tile (0: by the workspace cap)
     KNOB_ARGMAX_SLICE,     // kq_argmax: entries per workgroup (0: kArgmaxSlice; A/B, and the tests of the longer slices)
+    KNOB_MMQ_ID_Q6,        // kq_mmq_id on Q6_K experts: 0 by shape, 1 the 128 x 128 tile, 2 64 x 128, 3 128 x 64 (A/B: tools/moe_prefill_bench.py)
     KNOB_COUNT
 };
 double knob(Knob k);
 uint32_t knob_generation();
 // Process-wide kernel selectors a captured launch plan depends on (gemv impl / waves,
-// mmq impl; attention decode / prompt impl), packed for the backend's graph key.
+// mmq impl; attention decode / prompt impl, the MoE prefill form), packed for the backend's graph key.
 uint64_t api_selector_key();
 uint64_t ops_selector_key();
 // Launch timing (mi355x_timing_enable): timing_slot returns true (and the events) when this
@@ -375,13 +376,32 @@ int launch_kv_shift(const mi355x_kv_shift_desc *d, hipStream_t stream);
 
 // ---------------------------------------------------------------- kq_moe.hip
 // The mixture-of-experts FFN (include/ggml_mi355x.h, the rule): every check of mi355x_moe_route,
-// mi355x_mul_mat_id and mi355x_moe_combine, then one launch each (none for an empty shape). No
-// workspace: kq_gemv_id quantizes its activation row in the prologue.
+// mi355x_mul_mat_id and mi355x_moe_combine, then one launch each (none for an empty shape):
+// kq_gemv_id quantizes its activation row in the prologue and needs no workspace.
+// The grouped form of launch_mul_mat_id (mi355x_moe_prefill; moe_grouped(pairs) says whether a
+// call of T * n_used pairs takes it): kq_moe_group builds the group table of kq_common.h,
+// kq_quantize_q8L the Q8L/mmq rows of the T * ne11 activation rows, kq_mmq_id (kq_mmq.hip) runs
+// the tiles. `build` / `quantize` false: an earlier launch on the stream left the table of these
+// ids / the rows of this x in the buffers (the backend: one table per MOE_ROUTE node, up and
+// gate on one quantization).
+constexpr int64_t kMoeGroupedMinPairs = 32;  // AUTO: grouped from this many pairs (profiles/moe_prefill.txt)
+static_assert(kMoeGroupedMinPairs >= 16, "decode tokens and the small batches keep kq_gemv_id");
+struct MoeGrouped {
+    int32_t *table;  // moe_table_bytes(pairs), 4-byte aligned
+    size_t table_bytes;
+    uint8_t *xq;  // moe_q8_bytes(K, T * ne11), 16-byte aligned
+    size_t xq_bytes;
+    bool build, quantize;
+};
+int moe_prefill_mode();
+bool moe_grouped(int64_t pairs);
+size_t moe_table_bytes(int64_t pairs);
+size_t moe_q8_bytes(int64_t K, int64_t rows);
 int launch_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const float *x, int64_t x_stride, int64_t T,
                      int n_used, int32_t *record_out, int64_t record_stride, float *probs_out, hipStream_t stream);
 int launch_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01, size_t nb01, size_t nb02, int n_expert,
                       const float *x, int64_t ne11, int64_t x_row_stride, const int32_t *ids, int64_t ids_stride,
-                      int n_used, int64_t T, float *y, hipStream_t stream);
+                      int n_used, int64_t T, float *y, hipStream_t stream, const MoeGrouped *grouped = nullptr);
 int launch_moe_combine(const float *ex, int64_t n, int n_used, int64_t T, const int32_t *records, int64_t record_stride,
                        float *y, hipStream_t stream);
 

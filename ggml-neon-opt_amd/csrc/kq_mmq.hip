@@ -22,6 +22,8 @@
 // The steps, one function each: mmq_tile_of (which tile), mmq_issue (a superblock's DMA),
 // q45_superblock / q6_superblock (a superblock of one wave's 32 x 32 * CW outputs),
 // mmq_store (the outputs, the ADD and the KV-cache epilogue); mmq_tile is the loop.
+// kq_mmq_id is the same loop over the pairs of a MoE prompt grouped by expert (mi355x_mul_mat_id's
+// grouped form): a tile's weight base, activation rows and output rows come from kq_moe_group's table.
 // MFMA operand maps (verified with exact integer data, tools/mfma_layout_check.hip):
 //   i8 32x32x32: lane l (r = l&31, h = l>>5) holds A[r][16h+j], B[16h+j][r], j<16;
 //   f16 32x32x16: A[r][8h+j], B[8h+j][r], j<8; C/D (every dtype): col = r,
@@ -381,28 +383,47 @@ __device__ __forceinline__ int mmq_tile_of(const MmqArgs &a0, MmqArgs &a, int &t
 
 // A superblock's DMA plan: superblock b's A_INSTR activation + NB_I weight instructions of
 // 1 KB into `buf`, NW per wave (the last one repeated where they do not divide).
+__host__ __device__ constexpr int mmq_a_instr(int cw) { return mmq_cols(cw) * Q8L_STRIDE / 1024; }  // 19 per 64 columns (exact)
+__host__ __device__ constexpr int mmq_nw(int type, int rt, int cw) {
+    return (mmq_a_instr(cw) + mmq_b_instr(type, rt) + mmq_waves(rt, cw) - 1) / mmq_waves(rt, cw);
+}
+// instruction s of a wave: t < A_INSTR the activation tile's t-th KB, else the weight tile's
 template <int TYPE, int RT, int CW>
-__device__ __forceinline__ void mmq_issue(const MmqArgs &a, LDS uint8_t *buf, int b, int col0, int row0, int wave, int lane) {
+__device__ __forceinline__ int mmq_instr_of(int wave, int s) {
+    constexpr int TOTAL = mmq_a_instr(CW) + mmq_b_instr(TYPE, RT);
+    const int t = wave + mmq_waves(RT, CW) * s;
+    return t < TOTAL ? t : TOTAL - 1;  // pad: repeat the last one
+}
+// the activation column (of the launch, clamped to the last one) whose granule this lane fetches in
+// activation instruction t, and which of the column's 19 granules
+__device__ __forceinline__ int mmq_a_col(const MmqArgs &a, int col0, int t, int lane, int &piece) {
+    const int g = 64 * t + lane;
+    const int c = g / (Q8L_STRIDE / 16);
+    piece = g - c * (Q8L_STRIDE / 16);
+    return col0 + c < a.m_cols ? col0 + c : a.m_cols - 1;
+}
+// ID (kq_mmq_id): column c of the tile is Q8L row xr[s] of the workspace, read from the group
+// table once per tile (mmq_id_rows), not column c itself.
+template <int TYPE, int RT, int CW, bool ID = false>
+__device__ __forceinline__ void mmq_issue(const MmqArgs &a, LDS uint8_t *buf, int b, int col0, int row0, int wave, int lane,
+                                          const int *xr = nullptr) {
     constexpr int BSZ = block_bytes(TYPE);
-    constexpr int NWV = mmq_waves(RT, CW);
     constexpr int A_BYTES = mmq_cols(CW) * Q8L_STRIDE;
-    constexpr int A_INSTR = A_BYTES / 1024;  // 19 per 64 columns (exact)
-    constexpr int NB_I = mmq_b_instr(TYPE, RT);
-    constexpr int NW = (A_INSTR + NB_I + NWV - 1) / NWV;
+    constexpr int A_INSTR = mmq_a_instr(CW);
+    constexpr int NW = mmq_nw(TYPE, RT, CW);
 #pragma unroll
     for (int s = 0; s < NW; ++s) {
-        int t = wave + NWV * s;
-        if (t >= A_INSTR + NB_I) t = A_INSTR + NB_I - 1;  // pad: repeat the last one
-        const int g = 64 * (t < A_INSTR ? t : t - A_INSTR) + lane;  // granule in its tile
+        const int t = mmq_instr_of<TYPE, RT, CW>(wave, s);
         const uint8_t *src;
         if (t < A_INSTR) {
-            int c = g / (Q8L_STRIDE / 16);
-            const int piece = g - c * (Q8L_STRIDE / 16);
-            c = col0 + c < a.m_cols ? col0 + c : a.m_cols - 1;
+            int piece;
+            int c = mmq_a_col(a, col0, t, lane, piece);
+            if (ID) c = xr[s];
             src = a.xq + (int64_t)c * a.xq_col_stride + (int64_t)b * Q8L_STRIDE + 16 * piece;
             dma16(src, buf + 1024 * t);
         } else {
             constexpr int RG = mmq_row_bytes(TYPE) / 16;
+            const int g = 64 * (t - A_INSTR) + lane;  // granule in the weight tile
             int rw = g / RG;
             int piece = g - rw * RG;
             if (TYPE == Q6_K && piece > 13) piece = 13;  // padding granules: the row's last one again
@@ -413,12 +434,26 @@ __device__ __forceinline__ void mmq_issue(const MmqArgs &a, LDS uint8_t *buf, in
         }
     }
 }
+// kq_mmq_id: xr[s], the Q8L row behind the sorted entry this lane fetches in its activation
+// instruction s (the same for every superblock: read before the loop, so that no DMA of the
+// loop waits for a load of the list).
+template <int TYPE, int RT, int CW>
+__device__ __forceinline__ void mmq_id_rows(const MmqArgs &a, const int32_t *xrow, int col0, int wave, int lane, int *xr) {
+#pragma unroll
+    for (int s = 0; s < mmq_nw(TYPE, RT, CW); ++s) {
+        const int t = mmq_instr_of<TYPE, RT, CW>(wave, s);
+        int piece;
+        xr[s] = t < mmq_a_instr(CW) ? xrow[mmq_a_col(a, col0, t, lane, piece)] : 0;
+    }
+}
 
 // The store of one wave's outputs: the lane's weight row n, 16 activation columns per tile from
 // column cb0 on; y = mul_mat (+ res); for a prompt's k / v matrix also the KV-cache cells, as
-// kq_kv_store computes them (kq_ops.hip).
+// kq_kv_store computes them (kq_ops.hip). pair (kq_mmq_id): sorted entry m's outputs go to column
+// pair[m] of y; no res, no KV cells there.
 template <int CW>
-__device__ __forceinline__ void mmq_store(const MmqArgs &a, const f32x16 *sumf, int n, int cb0, int h) {
+__device__ __forceinline__ void mmq_store(const MmqArgs &a, const f32x16 *sumf, int n, int cb0, int h,
+                                          const int32_t *pair = nullptr) {
 #pragma unroll
     for (int ct = 0; ct < CW; ++ct) {
         const int cb = cb0 + 32 * ct;
@@ -426,7 +461,10 @@ __device__ __forceinline__ void mmq_store(const MmqArgs &a, const f32x16 *sumf, 
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int m = cb + mmq_acc_col(i, h);
-                if (m < a.m_cols)
+                if (m >= a.m_cols) continue;
+                if (pair)
+                    a.y[(int64_t)pair[m] * a.y_col_stride + n] = sumf[ct][i];
+                else
                     a.y[(int64_t)m * a.y_col_stride + n] =
                         a.res ? sumf[ct][i] + a.res[(int64_t)m * a.res_col_stride + n] : sumf[ct][i];
             }
@@ -455,8 +493,10 @@ __device__ __forceinline__ void mmq_store(const MmqArgs &a, const f32x16 *sumf, 
 
 // One (64 * CW)-column x RT-row output tile over the whole K: RT / 16 waves, each 32 weight
 // rows x 32 * CW columns (CW MFMA tiles sharing the wave's weight operands).
-template <int TYPE, int RT, int CW>
-__device__ __forceinline__ void mmq_tile(const MmqArgs &a, int tx, int ty) {
+// id (kq_mmq_id, else null): the tile's columns are the sorted entries [col0, a.m_cols) of the group
+// table: their activation rows and output columns come from its lists.
+template <int TYPE, int RT, int CW, bool ID = false>
+__device__ __forceinline__ void mmq_tile_at(const MmqArgs &a, int col0, int row0, const MmqIdArgs *id = nullptr) {
     constexpr int COLS = mmq_cols(CW);
     constexpr int A_BYTES = COLS * Q8L_STRIDE;
     constexpr int BUF = A_BYTES + RT * mmq_row_bytes(TYPE);
@@ -466,7 +506,6 @@ __device__ __forceinline__ void mmq_tile(const MmqArgs &a, int tx, int ty) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave & 1, wn = wave >> 1;  // the wave's column half and its 32 rows
     const int r = lane & 31, h = lane >> 5;
-    const int col0 = tx * COLS, row0 = ty * RT;
     const int nb = a.nb;
 
     f32x16 sumf[CW];
@@ -475,7 +514,9 @@ __device__ __forceinline__ void mmq_tile(const MmqArgs &a, int tx, int ty) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) sumf[ct][i] = 0.f;
 
-    mmq_issue<TYPE, RT, CW>(a, (LDS uint8_t *)smem, 0, col0, row0, wave, lane);
+    int xr[mmq_nw(TYPE, RT, CW)];
+    if (ID) mmq_id_rows<TYPE, RT, CW>(a, id->xrow, col0, wave, lane, xr);
+    mmq_issue<TYPE, RT, CW, ID>(a, (LDS uint8_t *)smem, 0, col0, row0, wave, lane, xr);
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {
         // One barrier per superblock (profiles/r03_mmq_onebar_tile128.txt): superblock b (the only
@@ -483,13 +524,18 @@ __device__ __forceinline__ void mmq_tile(const MmqArgs &a, int tx, int ty) {
         // has finished reading b - 1's buffer (lgkmcnt(0) before it), so b + 1 goes into that
         // buffer while b is computed
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (b + 1 < nb) mmq_issue<TYPE, RT, CW>(a, (LDS uint8_t *)smem + ((b + 1) & 1) * BUF, b + 1, col0, row0, wave, lane);
+        if (b + 1 < nb)
+            mmq_issue<TYPE, RT, CW, ID>(a, (LDS uint8_t *)smem + ((b + 1) & 1) * BUF, b + 1, col0, row0, wave, lane, xr);
         const uint8_t *buf = smem + (b & 1) * BUF;
         const uint8_t *Bt = buf + A_BYTES + (32 * wn + r) * mmq_row_bytes(TYPE);  // this lane's weight row
         if (TYPE == Q6_K) q6_superblock<CW>(a, buf, 32 * CW * wm, Bt, row0 + 32 * wn + r, b, r, h, sumf);
         else q45_superblock<TYPE, CW>(buf, 32 * CW * wm, Bt, r, h, sumf);
     }
-    mmq_store<CW>(a, sumf, row0 + 32 * wn + r, col0 + 32 * CW * wm, h);
+    mmq_store<CW>(a, sumf, row0 + 32 * wn + r, col0 + 32 * CW * wm, h, ID ? id->pair : nullptr);
+}
+template <int TYPE, int RT, int CW>
+__device__ __forceinline__ void mmq_tile(const MmqArgs &a, int tx, int ty) {
+    mmq_tile_at<TYPE, RT, CW>(a, tx * mmq_cols(CW), ty * RT);
 }
 
 // Two waves per SIMD (profiles/r04_mmq_occupancy_ab.txt); 64 x 128: one 4-wave workgroup per CU by
@@ -521,7 +567,48 @@ __global__ void __launch_bounds__(mmq_waves(RT, CW) * 64) KQ_MMQ_WPE_OF(RT, CW) 
     }
 }
 
-#define KQ_MMQ_INST(RT, CW)                                         \
+// kq_mmq's tile over the pairs of a MoE prompt grouped by expert (kq_moe_group's table): the same
+// superblock bodies and chain per (row, column), so the bits of kq_mmq and of kq_gemv_id. The grid
+// is a function of the shapes alone (row tiles x an upper bound of the column tiles); a workgroup
+// finds its bucket in the table's tile prefix (wave-uniform: at most 65 scalar reads), and with it
+// the expert's weight base, its columns' activation rows and output rows. mmq_tile_of keeps the
+// column tiles of a row tile, every expert's, on one XCD. Bucket n_expert (ids outside the table)
+// reads no weights: NaN to its pairs' rows, as kq_gemv_id stores.
+template <int TYPE, int RT, int CW>
+__global__ void __launch_bounds__(mmq_waves(RT, CW) * 64) KQ_MMQ_WPE_OF(RT, CW) kq_mmq_id(const MmqArgs a0, const MmqIdArgs g) {
+    MmqArgs a = a0;
+    a.res = nullptr;
+    a.kv_cur = 0;
+    int tx, ty;
+    mmq_tile_of(a0, a, tx, ty);
+    const int32_t *tile0 = g.tab + moe_tab_tile0(CW);  // the prefix of this kernel's column tiles
+    const int nbk = g.n_expert + 1;
+    if (tx >= tile0[nbk]) return;  // past the last column tile (before any barrier)
+    int e = 0;
+    for (int k = 1; k < nbk; ++k)
+        if (tile0[k] <= tx) e = k;  // the last bucket starting at or before tx: the non-empty one
+    const int first = g.tab[MOE_TAB_FIRST + e];
+    const int col0 = first + (tx - tile0[e]) * mmq_cols(CW), row0 = ty * RT;
+    a.m_cols = first + g.tab[MOE_TAB_COUNT + e];  // the bucket's end: this tile's columns stop there
+    if (e == g.n_expert) {
+        const int ncol = a.m_cols - col0 < mmq_cols(CW) ? a.m_cols - col0 : mmq_cols(CW);
+        for (int i = (int)threadIdx.x; i < ncol * RT; i += mmq_waves(RT, CW) * 64) {
+            const int n = row0 + i % RT;
+            if (n < a.n_rows) a.y[(int64_t)g.pair[col0 + i / RT] * a.y_col_stride + n] = __uint_as_float(0x7fc00000u);
+        }
+        return;
+    }
+    a.w = a0.w + (int64_t)e * g.nb02;
+    mmq_tile_at<TYPE, RT, CW, true>(a, col0, row0, &g);
+}
+template __global__ void kq_mmq_id<Q4_K, 128, 1>(const MmqArgs a, const MmqIdArgs g);
+template __global__ void kq_mmq_id<Q5_K, 128, 1>(const MmqArgs a, const MmqIdArgs g);
+template __global__ void kq_mmq_id<Q6_K, 128, 1>(const MmqArgs a, const MmqIdArgs g);
+// Q6_K: 128 x 128 where the buckets fill it (launch_mmq_id); 64 x 128 only under the MMQ_ID_Q6 knob (A/B)
+template __global__ void kq_mmq_id<Q6_K, 128, 2>(const MmqArgs a, const MmqIdArgs g);
+template __global__ void kq_mmq_id<Q6_K, 64, 2>(const MmqArgs a, const MmqIdArgs g);
+
+#define KQ_MMQ_INST(RT, CW)                                       \
     template __global__ void kq_mmq<Q4_K, RT, CW>(const MmqArgs a); \
     template __global__ void kq_mmq<Q5_K, RT, CW>(const MmqArgs a); \
     template __global__ void kq_mmq<Q6_K, RT, CW>(const MmqArgs a); \

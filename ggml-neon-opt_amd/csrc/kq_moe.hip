@@ -3,7 +3,7 @@
 // weight base is data (kq_gemv_id, ggml's MUL_MAT_ID) and the weighted sum of the experts' outputs
 // (kq_moe_combine). The rule is stated in include/ggml_mi355x.h (mi355x_moe_route,
 // mi355x_mul_mat_id, mi355x_moe_combine) and restated in tests/moe_ref.py; the device gives the
-// same bits. No atomics, no workgroup waits for another, no workspace.
+// same bits. No global atomics, no workgroup waits for another; no workspace but the grouped form's.
 //
 // kq_moe_route, one workgroup of 4 waves per row of x:
 //   dots     16 lanes per expert, lane c the accumulator lane c of ggml_vec_dot_f32's NEON form
@@ -38,11 +38,22 @@
 //   chain    lane r replays row r's records in superblock order with rows_chain: the reference's
 //            fp32 chain, the bits of kq_rows / kq_gemv and of the CPU oracle.
 //   Only the selected expert's rows are read. T * n_used pairs are independent workgroups: a
-//   prompt is correct but not weight-amortised (grouping tokens by expert onto kq_mmq: DESIGN.md).
+//   prompt is correct but not weight-amortised.
+//
+// The grouped form of mi355x_mul_mat_id (mi355x_moe_prefill: GROUPED, or AUTO from
+// kMoeGroupedMinPairs pairs), the same bits with every expert matrix read once per call:
+//   kq_moe_group     one workgroup sorts the pairs by expert into the group table (kq_common.h),
+//                    at every launch: the ids are data and a captured graph is replayed
+//   kq_quantize_q8L  the T * ne11 activation rows, the Q8L/mmq layout, into the workspace
+//   kq_mmq_id        kq_mmq's tiles with the weight base, the activation rows and the output rows
+//                    of a tile taken from the table (kq_mmq.hip)
 //
 // kq_moe_combine: y[i, t] = ex[i, 0, t] * w[0, t], then + ex[i, s, t] * w[s, t] for s = 1 .. in
 // slot order, each product and sum rounded once (no fused multiply-add), one thread an element.
 #include <string.h>
+
+#include <algorithm>
+#include <atomic>
 
 #include "kq_device.h"
 #include "kq_internal.h"
@@ -266,6 +277,142 @@ __global__ void __launch_bounds__(kMoeThreads) kq_moe_combine(const float *__res
 
 bool moe_type_ok(int type) { return type == Q4_K || type == Q5_K || type == Q6_K; }
 
+// ---------------------------------------------------------------- kq_moe_group
+// The group table of kq_common.h from a MOE_ROUTE node's ids, one workgroup, one launch, LDS
+// atomics only: count the pairs per bucket, one thread forms the three prefixes (at most 65
+// buckets), then every pair takes the next free entry of its bucket. Which entry a pair gets
+// within its bucket depends on the order the atomics retire in, so the sort is not stable and
+// not the same from run to run; no result depends on it, every output element of kq_mmq_id
+// being the chain of its own (row, pair). A stable sort would cost a scan per bucket for nothing.
+constexpr int kGroupThreads = 1024;
+struct GroupArgs {
+    const int32_t *ids;
+    int64_t ids_stride;
+    int32_t *tab;
+    int n_expert, n_used, pairs;
+};
+
+__global__ void __launch_bounds__(kGroupThreads) kq_moe_group(const GroupArgs a) {
+    __shared__ int cnt[MOE_BUCKETS], next[MOE_BUCKETS];
+    const int tid = (int)threadIdx.x, nbk = a.n_expert + 1;
+    if (tid < nbk) cnt[tid] = 0;
+    __syncthreads();
+    for (int p = tid; p < a.pairs; p += kGroupThreads) {
+        const int t = p / a.n_used;
+        const int id = a.ids[(int64_t)t * a.ids_stride + (p - t * a.n_used)];
+        atomicAdd(&cnt[(uint32_t)id < (uint32_t)a.n_expert ? id : a.n_expert], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int first = 0, tile = 0, tilew = 0;
+        for (int k = 0; k < nbk; ++k) {
+            const int c = cnt[k];
+            a.tab[MOE_TAB_COUNT + k] = c;
+            a.tab[MOE_TAB_FIRST + k] = first;
+            a.tab[MOE_TAB_TILE0 + k] = tile;
+            a.tab[MOE_TAB_TILE0W + k] = tilew;
+            next[k] = first;
+            first += c;
+            tile += (c + 63) / 64;
+            tilew += (c + 127) / 128;
+        }
+        a.tab[MOE_TAB_TILE0 + nbk] = tile;
+        a.tab[MOE_TAB_TILE0W + nbk] = tilew;
+    }
+    __syncthreads();
+    int32_t *list_pair = a.tab + MOE_TAB_LIST, *list_tok = list_pair + a.pairs;
+    for (int p = tid; p < a.pairs; p += kGroupThreads) {
+        const int t = p / a.n_used;
+        const int id = a.ids[(int64_t)t * a.ids_stride + (p - t * a.n_used)];
+        const int at = atomicAdd(&next[(uint32_t)id < (uint32_t)a.n_expert ? id : a.n_expert], 1);
+        list_pair[at] = p;
+        list_tok[at] = t;
+    }
+}
+
+std::atomic<int> g_moe_prefill{MI355X_MOE_PREFILL_AUTO};  // mi355x_moe_prefill()
+
+}  // namespace
+
+template <int TYPE, int RT, int CW>
+__global__ void kq_mmq_id(const MmqArgs a, const MmqIdArgs g);
+
+int moe_prefill_mode() { return g_moe_prefill.load(); }
+
+bool moe_grouped(int64_t pairs) {
+    const int mode = moe_prefill_mode();
+    return mode == MI355X_MOE_PREFILL_GROUPED ? pairs >= 1 : mode == MI355X_MOE_PREFILL_AUTO && pairs >= kMoeGroupedMinPairs;
+}
+
+size_t moe_table_bytes(int64_t pairs) { return ((size_t)moe_table_words(pairs) * 4 + 255) & ~(size_t)255; }
+size_t moe_q8_bytes(int64_t K, int64_t rows) { return (size_t)rows * (size_t)(K / QK) * Q8L_STRIDE; }
+
+namespace {
+
+int launch_moe_group(const int32_t *ids, int64_t ids_stride, int n_expert, int n_used, int pairs, int32_t *table,
+                     hipStream_t stream) {
+    GroupArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = ids;
+    a.ids_stride = ids_stride;
+    a.tab = table;
+    a.n_expert = n_expert;
+    a.n_used = n_used;
+    a.pairs = pairs;
+    return timed_launch("kq::kq_moe_group", 4.0 * (2.0 * pairs + (double)moe_table_words(pairs)), kq_moe_group, dim3(1),
+                        dim3(kGroupThreads), 0, stream, a);
+}
+
+// kq_mmq_id on the table and the Q8L rows of `gr`: 128 x 64 tiles (narrow column tiles waste least
+// on ragged experts), row tiles x
+// the most column tiles any routing of `pairs` pairs can need (every non-empty bucket ends with
+// one partial tile, and no tile is empty), so the grid depends on the shapes alone
+int launch_mmq_id(int type, const GemvIdArgs &g, const MoeGrouped &gr, int pairs, hipStream_t stream) {
+    // Q6_K: 128 x 128 once an expert's average bucket fills a 128-column tile (Mixtral's down at 1024 pairs:
+    // 426 against 501 us, 224 against 344 on two experts; at 256 pairs and below 128 x 64 wins, 176 against
+    // 219; 64 x 128 wins nowhere: profiles/moe_prefill.txt). The MMQ_ID_Q6 knob forces a shape (A/B).
+    int q6 = type == Q6_K ? (int)knob(KNOB_MMQ_ID_Q6) : 3;
+    if (q6 < 1 || q6 > 3) q6 = pairs >= 128 * g.n_expert ? 1 : 3;
+    const int RT = q6 == 2 ? 64 : 128, CW = q6 == 3 ? 1 : 2;
+    MmqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w = g.w;
+    a.row_stride = g.nb01;
+    a.n_rows = g.N;
+    a.xq = gr.xq;
+    a.nb = g.nb;
+    a.xq_col_stride = (int64_t)g.nb * Q8L_STRIDE;
+    a.y = g.y;
+    a.y_col_stride = g.N;
+    a.n_mat = 1;
+    MmqIdArgs id;
+    memset(&id, 0, sizeof(id));
+    id.tab = gr.table;
+    id.pair = gr.table + MOE_TAB_LIST;
+    id.xrow = g.ne11 == 1 ? id.pair + pairs : id.pair;  // the token list, or (row t * n_used + s) the pair list
+    id.nb02 = g.nb02;
+    id.n_expert = g.n_expert;
+    const int col_tiles = std::min(pairs / mmq_cols(CW) + g.n_expert + 1, pairs);
+    const dim3 grid((unsigned)col_tiles, (unsigned)((g.N + RT - 1) / RT));
+    const size_t lds = 2 * (size_t)mmq_buf_bytes(type, RT, CW) + 16;  // (+16: the Q6_K realign reads past the last row)
+    const void *fn = type == Q4_K   ? (const void *)kq_mmq_id<Q4_K, 128, 1>
+                     : type == Q5_K ? (const void *)kq_mmq_id<Q5_K, 128, 1>
+                     : q6 == 1      ? (const void *)kq_mmq_id<Q6_K, 128, 2>
+                     : q6 == 2      ? (const void *)kq_mmq_id<Q6_K, 64, 2>
+                                    : (const void *)kq_mmq_id<Q6_K, 128, 1>;
+    allow_lds(fn, lds);
+    void *args[] = {&a, &id};
+    return timed_launch_args(
+        [&] {
+            return LaunchInfo{type == Q4_K   ? "kq::kq_mmq_id<q4_K>"
+                              : type == Q5_K ? "kq::kq_mmq_id<q5_K>"
+                                             : "kq::kq_mmq_id<q6_K>",
+                              (double)g.n_expert * g.N * g.nb * block_bytes(type) +
+                                  (double)pairs * ((double)g.nb * Q8L_STRIDE + 4.0 * g.N)};
+        },
+        fn, grid, dim3((unsigned)(64 * mmq_waves(RT, CW))), lds, stream, args);
+}
+
 }  // namespace
 
 int launch_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const float *x, int64_t x_stride, int64_t T,
@@ -298,7 +445,7 @@ int launch_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const 
 
 int launch_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01, size_t nb01, size_t nb02, int n_expert,
                       const float *x, int64_t ne11, int64_t x_row_stride, const int32_t *ids, int64_t ids_stride,
-                      int n_used, int64_t T, float *y, hipStream_t stream) {
+                      int n_used, int64_t T, float *y, hipStream_t stream, const MoeGrouped *grouped) {
     if (!experts || !x || !ids || !y || ((uintptr_t)x & 15u) || ((uintptr_t)ids & 3u) || ((uintptr_t)y & 3u))
         return MI355X_E_INVAL;
     if (ne00 < 1 || ne00 % QK || ne01 < 0 || n_expert < 1 || n_used < 1 || T < 0) return MI355X_E_INVAL;
@@ -315,6 +462,17 @@ int launch_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01,
     if (n_expert > kMoeMaxExperts || n_used > kMoeMaxUsed || ne00 > MI355X_MUL_MAT_ID_MAX_K || ne01 > 0x7fffffff ||
         T * n_used > 65535)
         return MI355X_E_UNSUPPORTED;
+    const int pairs = (int)(T * n_used);
+    // the grouped form's table and Q8L rows: the caller's, 4- and 16-byte aligned and large enough
+    bool take_grouped = moe_grouped(pairs);
+    if (take_grouped &&
+        (!grouped || !grouped->table || !grouped->xq || ((uintptr_t)grouped->table & 3u) || ((uintptr_t)grouped->xq & 15u) ||
+         grouped->table_bytes < moe_table_bytes(pairs) || grouped->xq_bytes < moe_q8_bytes(ne00, T * ne11))) {
+        // GROUPED asked for the form: an error. AUTO promises the faster form to a caller who brought its
+        // workspace and refuses no call that kq_gemv_id can run
+        if (moe_prefill_mode() == MI355X_MOE_PREFILL_GROUPED) return MI355X_E_WORKSPACE;
+        take_grouped = false;
+    }
     if (T == 0 || ne01 == 0) return MI355X_OK;
     if (!device_ok()) return MI355X_E_NODEVICE;
     GemvIdArgs a;
@@ -332,7 +490,11 @@ int launch_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01,
     a.ne11 = (int)ne11;
     a.nb = (int)(ne00 / QK);
     a.N = (int)ne01;
-    const int pairs = (int)(T * n_used);
+    if (take_grouped) {  // kq_moe_group and kq_quantize_q8L (unless an earlier launch left their outputs), kq_mmq_id
+        int rc = grouped->build ? launch_moe_group(ids, ids_stride, n_expert, n_used, pairs, grouped->table, stream) : 0;
+        if (!rc && grouped->quantize) rc = launch_quantize_q8L(x, x_row_stride, grouped->xq, ne00, T * ne11, stream, true);
+        return rc ? rc : launch_mmq_id(type, a, *grouped, pairs, stream);
+    }
     // 8 rows a wave where that still leaves every CU a few workgroups; else 4
     const int rpw = ((ne01 + 31) / 32) * pairs >= 512 ? 8 : 4;
     const int per_wg = WAVES_PER_WG * rpw;
@@ -378,17 +540,37 @@ int mi355x_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const 
 }
 
 size_t mi355x_mul_mat_id_workspace_size(int type, int64_t ne00, int n_used, int64_t T) {
-    (void)type, (void)ne00, (void)n_used, (void)T;
-    return 0;  // kq_gemv_id quantizes the activation rows in its own prologue
+    (void)type;
+    if (ne00 < 1 || ne00 % kq::QK || n_used < 1 || T < 1 || T * n_used > 65535) return 0;
+    // kq_gemv_id quantizes the activation rows in its own prologue; the grouped form keeps the
+    // group table and the Q8L rows (one per slot at most) there
+    if (!kq::moe_grouped(T * n_used)) return 0;
+    return kq::moe_table_bytes(T * n_used) + kq::moe_q8_bytes(ne00, T * n_used);
+}
+
+int mi355x_moe_prefill(int impl) {
+    if (impl < MI355X_MOE_PREFILL_AUTO || impl > MI355X_MOE_PREFILL_GROUPED) return MI355X_E_INVAL;
+    return kq::g_moe_prefill.exchange(impl);
 }
 
 int mi355x_mul_mat_id(int type, const void *experts, int64_t ne00, int64_t ne01, size_t nb01, size_t nb02, int n_expert,
                       const float *x, int64_t ne11, int64_t x_row_stride, const int32_t *ids, int64_t ids_stride,
                       int n_used, int64_t T, float *y, void *workspace, size_t workspace_size, void *stream) {
-    // (MI355X_E_WORKSPACE would stand between the shape checks and the device check: nothing is needed today)
-    (void)workspace, (void)workspace_size;
+    // the grouped form's buffers in the workspace: the table, then the Q8L rows. launch_mul_mat_id returns
+    // MI355X_E_WORKSPACE between the shape checks and the device check where the form needs more than it got
+    kq::MoeGrouped gr;
+    memset(&gr, 0, sizeof(gr));
+    const size_t need = mi355x_mul_mat_id_workspace_size(type, ne00, n_used, T);
+    if (workspace && need && workspace_size >= need) {
+        const size_t tb = kq::moe_table_bytes(T * n_used);
+        gr.table = (int32_t *)workspace;
+        gr.table_bytes = tb;
+        gr.xq = (uint8_t *)workspace + tb;
+        gr.xq_bytes = workspace_size - tb;
+    }
+    gr.build = gr.quantize = true;
     return kq::launch_mul_mat_id(type, experts, ne00, ne01, nb01, nb02, n_expert, x, ne11, x_row_stride, ids, ids_stride,
-                                 n_used, T, y, (hipStream_t)stream);
+                                 n_used, T, y, (hipStream_t)stream, &gr);
 }
 
 int mi355x_moe_combine(const float *ex, int64_t n, int n_used, int64_t T, const int32_t *records, int64_t record_stride,

@@ -704,7 +704,8 @@ int check_attn(const AttnArgs &a) {
 
 uint64_t ops_selector_key() {
     return (uint64_t)(uint32_t)attn_impl() | ((uint64_t)(uint32_t)g_prompt_impl.load() << 8) |
-           ((uint64_t)(uint32_t)attn_stream_mode() << 16) | ((uint64_t)(uint32_t)g_prompt_precision.load() << 24);
+           ((uint64_t)(uint32_t)attn_stream_mode() << 16) | ((uint64_t)(uint32_t)g_prompt_precision.load() << 24) |
+           ((uint64_t)(uint32_t)moe_prefill_mode() << 32);
 }
 
 }  // namespace kq

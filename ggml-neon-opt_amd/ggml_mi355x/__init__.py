@@ -62,6 +62,7 @@ ATTN_PATH_STREAM = 7  # the streamed kernels (attn_stream)
 MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE192 = 0, 1, 2, 3, 4, 6
 PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
 ATTN_PROMPT_EXACT, ATTN_PROMPT_F16 = 0, 1  # attn_prompt_precision
+MOE_PREFILL_AUTO, MOE_PREFILL_GEMV, MOE_PREFILL_GROUPED = 0, 1, 2  # moe_prefill
 
 # Every symbol include/ggml_mi355x.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -102,6 +103,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_penalize_rows",
     "mi355x_kv_shift",
     "mi355x_moe_route", "mi355x_mul_mat_id_workspace_size", "mi355x_mul_mat_id", "mi355x_moe_combine",
+    "mi355x_moe_prefill",
 )
 
 
@@ -344,6 +346,9 @@ def lib():
         L.mi355x_mul_mat_id.restype = i32
         L.mi355x_moe_combine.argtypes = [vp, i64, i32, i64, vp, i64, vp, vp]
         L.mi355x_moe_combine.restype = i32
+    if hasattr(L, "mi355x_moe_prefill"):
+        L.mi355x_moe_prefill.argtypes = [i32]
+        L.mi355x_moe_prefill.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     if hasattr(L, "mi355x_attn_prompt_precision"):  # (an older library under MI355X_LIB, A/B runs: without it)
@@ -613,7 +618,7 @@ def debug_rows_prologue(x, waves, prologue=PRO_NONE, x2=None, eps=0.0, stream=No
 DEBUG_KNOBS = ("GEMV_DIAG", "GEMV_RING", "GEMV_PRE0", "GEMV_SMALL_MB", "GEMV_WPC",
                "GEMV_SMALL_WG", "GEMV_FQMAX", "MMF_WAVES", "MMF_ORDER", "ATTN_DIAG", "LOOPBACK_NOCOPY",
                "ATTN_OPROJ", "AO_NRB", "GEMV_DYN", "GEMV_DYN_P", "GEMV_DYN_STEPS", "GEMV_SHORT", "ATTN_STREAM",
-               "ATTN_STREAM_TILE", "ARGMAX_SLICE")
+               "ATTN_STREAM_TILE", "ARGMAX_SLICE", "MMQ_ID_Q6")
 
 
 def debug_knob(name, value=float("nan")):
@@ -652,6 +657,14 @@ def attn_stream(mode):
     A/B). attn_path / attn_decode / attn_prompt, attn_batch / attn_batch_path and the graph backend
     (OP_ATTN_BATCH included) follow it. Returns the previous mode, E_INVAL for any other value."""
     return int(lib().mi355x_attn_stream(mode))
+
+
+def moe_prefill(impl):
+    """Which form mul_mat_id and the backend's MUL_MAT_ID nodes take (mi355x_moe_prefill): MOE_PREFILL_AUTO
+    (default: the expert-grouped int8-MFMA tiles, kq_moe_group + kq_mmq_id, from 32 (token, slot) pairs,
+    kq_gemv_id below), MOE_PREFILL_GEMV (always kq_gemv_id) or MOE_PREFILL_GROUPED (grouped for any T >= 1);
+    the same bits either way. Part of the backend's plan key. Returns the previous value, E_INVAL for any other."""
+    return int(_lib_with("mi355x_moe_prefill").mi355x_moe_prefill(impl))
 
 
 def gemv_fused_ext(mats, x, prologue=PRO_NONE, x2=None, eps=0.0, residual=None, epi_y=None, stream=None):

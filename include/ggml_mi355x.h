@@ -794,10 +794,32 @@ int mi355x_kv_shift(const mi355x_kv_shift_desc *d, void *stream);
  * a multiple of 256, ne01 < 0, n_expert, n_used < 1, T < 0, ne11 neither 1 nor n_used,
  * x_row_stride not a multiple of 4 or < ne00 (more than one row), ids_stride < n_used, nb01 below
  * a row's bytes, nb02 < ne01 * nb01 (n_expert > 1), a misaligned Q4_K / Q5_K matrix, an odd Q6_K address or stride; then
- * MI355X_E_UNSUPPORTED; then MI355X_E_WORKSPACE (workspace_size below
- * mi355x_mul_mat_id_workspace_size, which is 0 today: the activation rows are quantized in the
- * launch's prologue, and workspace may be NULL); T == 0 or ne01 == 0 returns MI355X_OK with no
- * launch; then MI355X_E_NODEVICE.
+ * MI355X_E_UNSUPPORTED; then MI355X_E_WORKSPACE (under MI355X_MOE_PREFILL_GROUPED, below: a
+ * workspace that is NULL, not 16-byte aligned or below mi355x_mul_mat_id_workspace_size; the
+ * kq_gemv_id form needs none: its activation rows are quantized in the launch's prologue, the
+ * size is 0 and workspace may be NULL); T == 0 or ne01 == 0 returns MI355X_OK with no launch;
+ * then MI355X_E_NODEVICE.
+ *
+ * mi355x_moe_prefill: which form mi355x_mul_mat_id and the graph backend's MUL_MAT_ID nodes take
+ * (process-wide, like mi355x_mmq_impl; reads no environment; part of the backend's plan key).
+ * kq_gemv_id streams an expert matrix once per (token, slot) pair; the grouped form streams every
+ * expert matrix once per call, whatever T is, and gives the same bits:
+ *   kq_moe_group      sorts the T * n_used pairs by expert on the device, at every launch (the ids
+ *                     are data, a captured graph is replayed): one workgroup, no global atomics;
+ *   kq_quantize_q8L   the T * ne11 activation rows as Q8L blocks in the workspace;
+ *   kq_mmq_id         mi355x_mul_mat's int8-MFMA tiles (128 rows x 64 pairs of one expert): the
+ *                     weight base, the activation rows and the output rows of a tile come from the
+ *                     sorted list. The grid depends on the shapes alone.
+ * An id outside [0, n_expert) gives NaN rows in either form. The order of the pairs inside an
+ * expert's group is unspecified and enters no result. Same limits as above (T * n_used <= 65535).
+ *   MI355X_MOE_PREFILL_AUTO (0, default)  grouped from T * n_used >= 32 pairs, kq_gemv_id below. A
+ *                                         call that brings no (or too small a) workspace runs kq_gemv_id:
+ *                                         AUTO refuses nothing that form can run;
+ *   MI355X_MOE_PREFILL_GEMV (1)           always kq_gemv_id;
+ *   MI355X_MOE_PREFILL_GROUPED (2)        grouped for any T >= 1; MI355X_E_WORKSPACE without its workspace.
+ * Returns the previous value, or MI355X_E_INVAL. mi355x_mul_mat_id_workspace_size: the bytes a
+ * call of that shape needs under the current mode: 0 where it takes kq_gemv_id, else the group
+ * table (1152 + 8 bytes a pair) and T * n_used Q8L rows of ne00 / 256 * 304 bytes.
  *
  * mi355x_moe_combine: ex f32 [n, n_used, T] packed, records / record_stride as mi355x_moe_route
  * wrote them (the weights are read at words [n_used, 2 n_used) of a record), y f32 [n, T] packed.
@@ -808,6 +830,10 @@ int mi355x_kv_shift(const mi355x_kv_shift_desc *d, void *stream);
 #define MI355X_MOE_MAX_EXPERTS 64
 #define MI355X_MOE_MAX_USED 8
 #define MI355X_MUL_MAT_ID_MAX_K 16384
+#define MI355X_MOE_PREFILL_AUTO 0
+#define MI355X_MOE_PREFILL_GEMV 1
+#define MI355X_MOE_PREFILL_GROUPED 2
+int mi355x_moe_prefill(int impl);
 int mi355x_moe_route(const float *gate_inp, int64_t n_embd, int n_expert, const float *x, int64_t x_stride, int64_t T,
                      int n_used, int32_t *record_out, int64_t record_stride, float *probs_out /* nullable */,
                      void *stream);
@@ -936,7 +962,11 @@ int mi355x_moe_combine(const float *ex, int64_t n, int n_used, int64_t T, const 
  *   MUL_MAT_ID   mi355x_mul_mat_id: src0 the expert tensor, K-quant [K, N, n_expert] (ne[2] the
  *                experts, nb[1], nb[2]), src1 the activations f32 [K, ne11, T] with ne11 1 or n_used
  *                and packed rows of rows (nb[2] = ne11 * nb[1]), src2 the MOE_ROUTE node (its
- *                ne[0] / 2 is n_used) -> f32 [N, n_used, T] packed.
+ *                ne[0] / 2 is n_used) -> f32 [N, n_used, T] packed. In the grouped form
+ *                (mi355x_moe_prefill) the group table, in a buffer of the backend's own, is built
+ *                once per MOE_ROUTE node and read by its three consumers, and up and gate, which
+ *                share src1, quantize it once: per MoE layer one kq_moe_group, two
+ *                kq_quantize_q8L and three kq_mmq_id.
  *   MOE_COMBINE  mi355x_moe_combine: src0 the experts' outputs f32 [n, n_used, T] packed, src1 the
  *                MOE_ROUTE node -> f32 [n, T] packed.
  *                The three MoE nodes get launches of their own in graph order and are never fused or
