@@ -612,6 +612,8 @@ ggml_backend_dev_t reg_device(ggml_backend_reg_t reg, size_t i) {
 void *reg_proc(ggml_backend_reg_t, const char *name) {
     if (name && std::strcmp(name, "ggml_backend_mi355x_set_multi_seq") == 0)
         return (void *)ggml_backend_mi355x_set_multi_seq;
+    if (name && std::strcmp(name, "ggml_backend_mi355x_set_small_batch") == 0)
+        return (void *)ggml_backend_mi355x_set_small_batch;
     if (name && std::strcmp(name, "ggml_backend_mi355x_set_long_context") == 0)
         return (void *)ggml_backend_mi355x_set_long_context;
     if (name && std::strcmp(name, "ggml_backend_mi355x_set_prompt_attn_f16") == 0)
@@ -670,6 +672,11 @@ int ggml_backend_mi355x_get_device_count(void) { return (int)registry()->devices
 
 void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable) {
     if (ggml_backend_is_mi355x(backend)) ((Backend *)backend->context)->multi_seq = enable;
+}
+
+// (the selector is process-wide, like the library's other kernel selectors; `backend` names the caller)
+void ggml_backend_mi355x_set_small_batch(ggml_backend_t backend, bool enable) {
+    if (ggml_backend_is_mi355x(backend)) mi355x_small_batch(enable ? MI355X_SMALL_BATCH_FUSED : MI355X_SMALL_BATCH_NODES);
 }
 
 void ggml_backend_mi355x_set_long_context(bool enable) { mi355x_attn_stream(enable ? 1 : 0); }

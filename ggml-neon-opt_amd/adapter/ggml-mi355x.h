@@ -32,6 +32,9 @@ GGML_BACKEND_API int ggml_backend_mi355x_get_device_count(void);
 // keep the single-sequence path either way. Also returned by the registry's get_proc_address
 // under this name.
 GGML_BACKEND_API void ggml_backend_mi355x_set_multi_seq(ggml_backend_t backend, bool enable);
+// Graphs of 2 to 15 tokens (several sequences, short prompts) on the fused small-batch kernels
+// (mi355x_small_batch FUSED: kq_rows_cols; the same bits). Off by default; process-wide.
+GGML_BACKEND_API void ggml_backend_mi355x_set_small_batch(ggml_backend_t backend, bool enable);
 // KV caches of more than 7040-7616 cells (the per-head attention kernels' limit), up to 131072:
 // off (the default), a graph over such a cache is refused (GGML_STATUS_FAILED); on, its
 // attention runs on the library's streamed kernels (mi355x_attn_stream mode 1, same bits).

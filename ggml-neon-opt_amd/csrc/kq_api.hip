@@ -181,7 +181,7 @@ void allow_lds(const void *fn, size_t lds) {
 uint64_t api_selector_key() {
     return (uint64_t)(uint32_t)(gemv_impl_select(-1) + 1) | ((uint64_t)(uint32_t)rows_waves_select(-1) << 8) |
            ((uint64_t)(uint32_t)(mmq_impl() + 1) << 16) | ((uint64_t)(uint32_t)(prefill_precision() + 1) << 24) |
-           ((uint64_t)knob_generation() << 32);
+           ((uint64_t)(knob_generation() & 0x7fffffffu) << 32) | ((uint64_t)(uint32_t)small_batch_select(-1) << 63);
 }
 
 }  // namespace kq
@@ -348,6 +348,20 @@ int mi355x_mul_mat(int src0_type, const void *src0, int64_t ne00, int64_t ne01, 
     }
     size_t need = mi355x_mul_mat_workspace_size(src0_type, ne00, ne01, ne11);
     if (!workspace || workspace_size < need) return MI355X_E_WORKSPACE;
+    if (ne11 < kMmqMinCols && small_batch_fused() && ((uintptr_t)workspace & 15u) == 0) {
+        // MI355X_SMALL_BATCH_FUSED: one quantization into plain Q8L blocks, then kq_rows_cols
+        mi355x_gemv_desc d = {src0_type, src0, ne01, nb01, dst};
+        RowsColsPlan cp;
+        int rc = plan_rows_cols(&d, 1, ne00, ne11, cp);
+        if (rc == MI355X_OK) {
+            if (!device_ok()) return MI355X_E_NODEVICE;
+            rc = launch_quantize_q8L(src1, (int64_t)(nb11 / 4), workspace, ne00, ne11, (hipStream_t)stream, false);
+            if (rc) return rc;
+            const int64_t y_cs = (int64_t)(nb1 / 4);
+            return launch_rows_cols(cp, (const uint8_t *)workspace, &y_cs, nullptr, nullptr, (hipStream_t)stream);
+        }
+        if (rc != MI355X_E_UNSUPPORTED) return rc;
+    }
     if (mmf_applies(src0_type, src0, ne01, nb01, ne11, ne00) && ((uintptr_t)workspace & 15u) == 0) {
         if (!device_ok()) return MI355X_E_NODEVICE;
         int rc = launch_f16img(src1, (int64_t)(nb11 / 4), (uint8_t *)workspace, ne00, ne11, (hipStream_t)stream);
@@ -544,6 +558,28 @@ int mi355x_prefill_precision(int precision) {
     const int prev = prefill_precision();
     prefill_precision_set(precision);
     return prev;
+}
+
+int mi355x_small_batch(int impl) {
+    if (impl == -1) return small_batch_select(-1);  // query
+    if (impl < MI355X_SMALL_BATCH_NODES || impl > MI355X_SMALL_BATCH_FUSED) return MI355X_E_INVAL;
+    return small_batch_select(impl);
+}
+
+int mi355x_rows_cols_plan(int type, int64_t k, int64_t n_rows, int64_t m, int *ncol, int *groups, int64_t *lds,
+                          int *batch_rows, int *rows_per_wave) {
+    mi355x_gemv_desc d[1];
+    int rc = placeholder_descs(&type, &n_rows, 1, k, d);
+    if (rc) return rc;
+    RowsColsPlan cp;
+    rc = plan_rows_cols(d, 1, k, m, cp);
+    if (rc) return rc;
+    if (ncol) *ncol = cp.ncol;
+    if (groups) *groups = (int)cp.grid.y;
+    if (lds) *lds = (int64_t)cp.lds;
+    if (batch_rows) *batch_rows = cp.a.bR;
+    if (rows_per_wave) *rows_per_wave = cp.a.rpw;
+    return MI355X_OK;
 }
 
 int mi355x_gemv_waves(int waves) {

@@ -197,7 +197,9 @@ int find_ly_block(const mi355x_backend *b, const std::vector<uint32_t> &k) {
 }
 
 kq::PlanOpts plan_opts(const mi355x_backend *b) {
-    return {b->fuse, b->attn_oproj, b->layer_engine, b->workspace, b->workspace_size};
+    // (under a communicator, real or emulated, the small-batch mode plans what NODES plans)
+    return {b->fuse, b->attn_oproj, b->layer_engine, b->workspace, b->workspace_size,
+            kq::small_batch_fused() && !b->comm && b->loop_world == 0};
 }
 
 // What the workspace holds of an activation: the Q8L blocks (int8-MFMA GEMMs, kq_mmq) or
@@ -228,8 +230,43 @@ int ensure_activation(mi355x_backend *b, const mi355x_tensor *x, int64_t K, int6
     const float *xd = (const float *)x->data;
     const int64_t xs = (int64_t)(x->nb[1] / 4);
     const int rc = f16 ? kq::launch_f16img(xd, xs, (uint8_t *)b->workspace, K, M, b->stream)
-                       : kq::launch_quantize_q8L(xd, xs, b->workspace, K, M, b->stream, true);
+                       : kq::launch_quantize_q8L(xd, xs, b->workspace, K, M, b->stream, M >= kq::kMmqMinCols);
     if (!rc) q8.set(x, K, M, f16);
+    return rc;
+}
+
+// MUL_MATs of 2 .. 15 columns on one activation (kq::cols_mm each): its plain Q8L blocks in the
+// workspace, then one kq_rows_cols launch over all of them, or one per matrix where the joint
+// layout does not fit. res: the ADD epilogue of a single matrix.
+int enqueue_cols_mm(mi355x_backend *b, mi355x_tensor *const *mm, int n, Q8State &q8, float *y0 = nullptr,
+                    int64_t y0_stride = 0, const float *res = nullptr, int64_t res_stride = 0) {
+    const mi355x_tensor *x = mm[0]->src[1];
+    const int64_t K = mm[0]->src[0]->ne[0], M = x->ne[1];
+    int rc = ensure_activation(b, x, K, M, false, q8);
+    if (rc) return rc;
+    mi355x_gemv_desc d[MI355X_MAX_FUSED];
+    int64_t y_cs[MI355X_MAX_FUSED], res_cs[MI355X_MAX_FUSED] = {res_stride};
+    const float *rs[MI355X_MAX_FUSED] = {res};
+    for (int k = 0; k < n; ++k) {
+        const mi355x_tensor *w = mm[k]->src[0];
+        d[k] = {w->type, w->data, w->ne[1], w->nb[1], y0 ? y0 : (float *)mm[k]->data};
+        y_cs[k] = y0 ? y0_stride : (int64_t)(mm[k]->nb[1] / 4);
+    }
+    kq::RowsColsPlan cp;
+    rc = kq::plan_rows_cols(d, n, K, M, cp);
+    if (rc == MI355X_OK) {
+        rc = kq::launch_rows_cols(cp, (const uint8_t *)b->workspace, y_cs, rs, res_cs, b->stream);
+    } else if (rc == MI355X_E_UNSUPPORTED && n > 1) {
+        rc = MI355X_OK;
+        for (int k = 0; k < n && !rc; ++k) {
+            rc = kq::plan_rows_cols(d + k, 1, K, M, cp);
+            if (!rc) rc = kq::launch_rows_cols(cp, (const uint8_t *)b->workspace, y_cs + k, nullptr, nullptr, b->stream);
+        }
+    }
+    if (rc)
+        q8 = Q8State();
+    else
+        for (int k = 0; k < n; ++k) q8.drop_if_overlaps(d[k].y, y_cs[k], M);
     return rc;
 }
 
@@ -243,6 +280,10 @@ int enqueue_batched_mm(mi355x_backend *b, const mi355x_tensor *t, Q8State &q8, f
         y_stride = (int64_t)(t->nb[1] / 4);
     }
     const int64_t K = w->ne[0], M = x->ne[1];
+    if (M < kq::kMmqMinCols) {
+        mi355x_tensor *const one[1] = {const_cast<mi355x_tensor *>(t)};
+        return enqueue_cols_mm(b, one, 1, q8, y, y_stride, res, res_stride);
+    }
     const bool f16 = kq::mmf_applies(w->type, w->data, w->ne[1], w->nb[1], M, K);
     int rc = ensure_activation(b, x, K, M, f16, q8);
     if (rc) return rc;
@@ -500,9 +541,10 @@ int enqueue(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<La
         if (l.kind == LaunchKind::PrefillPrologue) {  // the activation's Q8L blocks for the MUL_MATs after it
             const mi355x_tensor *m = l.q8_of;
             const int64_t K = m->ne[0], M = m->ne[1];
+            const bool mmq = M >= kq::kMmqMinCols;  // fewer columns: the plain blocks kq_rows_cols reads
             rc = l.pro == MI355X_PRO_RMS_NORM
-                     ? kq::launch_rms_norm_q8L(l.x, l.x2, b->workspace, K, M, l.eps, b->stream)
-                     : kq::launch_swiglu_q8L(l.x, l.x2, b->workspace, K, M, b->stream);
+                     ? kq::launch_rms_norm_q8L(l.x, l.x2, b->workspace, K, M, l.eps, b->stream, mmq)
+                     : kq::launch_swiglu_q8L(l.x, l.x2, b->workspace, K, M, b->stream, mmq);
             if (rc) return rc;
             q8.set(m, K, M, false);  // int8 Q8L blocks now, whatever a preceding f16 GEMM left
             continue;
@@ -535,6 +577,11 @@ int enqueue(mi355x_backend *b, mi355x_tensor *const *nodes, const std::vector<La
                                        b->fx_size, b->stream);
             if (rc) return rc;
             q8 = Q8State();
+            continue;
+        }
+        if (l.kind == LaunchKind::MmMulti && t->src[1]->ne[1] < kq::kMmqMinCols) {  // ... of 2 .. 15 columns: kq_rows_cols
+            rc = enqueue_cols_mm(b, nodes + l.first, l.count, q8);
+            if (rc) return rc;
             continue;
         }
         if (l.kind == LaunchKind::MmMulti) {  // several batched MUL_MATs on one activation: one tile-GEMM launch

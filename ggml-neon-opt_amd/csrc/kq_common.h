@@ -258,6 +258,54 @@ __host__ __device__ inline RowsDynLayout rows_dyn_layout(int nb, int tmask, int 
     return L;
 }
 
+// ---------------------------------------------------------------- small-batch GEMV (2-15 columns)
+// kq_rows_cols (kq_rows_cols.hip): kq_rows' row streams against a group of NCOL = 2 / 4 / 8
+// activation columns. Workgroups of ROWS_COLS_WAVES waves, two of them resident on a CU;
+// grid.y = the column groups (M = 9 .. 15: two groups of 8). Global wave gw = wave * grid.x +
+// blockIdx.x owns rows as in kq_rows (wave_prefix / rbase / rrem).
+constexpr int ROWS_COLS_WAVES = 4;
+constexpr int ROWS_COLS_RECS = 256;  // chain records per wave and record buffer (4 KB)
+struct RowsColsArgs {
+    int n_desc, nb, m_total, waves_total;
+    int bR;    // rows per chain batch; nbuf == 2: bR * nb >= 16, a step touches two batches at most
+    int nbuf;  // record buffers per wave: 1 where one batch covers a wave's rows (bR >= rpw), else 2
+    int rpw;   // the most rows of any wave (staged outputs)
+    int tmask;
+    int wave_prefix[MI355X_MAX_FUSED + 1];
+    int rbase[MI355X_MAX_FUSED], rrem[MI355X_MAX_FUSED], type[MI355X_MAX_FUSED];
+    const uint8_t *w[MI355X_MAX_FUSED];
+    const float *res[MI355X_MAX_FUSED];  // y[c] = mul_mat + res[c] (the ADD after the MUL_MAT), or null
+    int64_t res_col_stride[MI355X_MAX_FUSED];  // floats
+    float *y[MI355X_MAX_FUSED];
+    int64_t y_col_stride[MI355X_MAX_FUSED];  // floats
+    const uint8_t *xq;  // plain Q8L blocks (kq_quantize_q8L<false>'s): column j's block b at (j * nb + b) * 304
+};
+//   act:  the column group's Q8L blocks, column-major (ncol * nb * 304 B)
+//   ring: per wave, the ring of its type (rows_ring)
+//   recs: per wave nbuf buffers of bR x nb x ncol records (16 B), [row][block][column]
+//   outs: per wave rpw x ncol staged results
+struct RowsColsLayout {
+    int act, ring, ring_stride, recs, recs_stride, outs, outs_stride, total;
+};
+__host__ __device__ inline RowsColsLayout rows_cols_layout(int ncol, int nb, int tmask, int bR, int nbuf, int rpw) {
+    RowsColsLayout L;
+    L.act = 0;
+    L.ring = ncol * nb * Q8L_STRIDE;
+    L.ring_stride = rows_ring(tmask);
+    L.recs = L.ring + ROWS_COLS_WAVES * L.ring_stride;
+    L.recs_stride = nbuf * bR * nb * ncol * 16;
+    L.outs = L.recs + ROWS_COLS_WAVES * L.recs_stride;
+    L.outs_stride = (rpw * ncol * 4 + 15) & ~15;
+    L.total = L.outs + ROWS_COLS_WAVES * L.outs_stride;
+    return L;
+}
+// rows per chain batch at ncol columns: bR * ncol pairs fill the wave (<= 64) within
+// ROWS_COLS_RECS records per buffer, never fewer rows than one 16-superblock step holds
+__host__ __device__ constexpr int rows_cols_batch(int ncol, int nb) {
+    const int fill = WAVE / ncol, cap = ROWS_COLS_RECS / (nb * ncol), step = (ROWS_SB + nb - 1) / nb;
+    return cmax(cmax(fill < cap ? fill : cap, step), 1);
+}
+
 // Decode attention block (kq_attn_decode.hip): one workgroup per query head.
 struct AttnArgs {
     const float *q, *k, *v;       // projections of this token (before rope)

@@ -21,8 +21,12 @@ __global__ void kq_rows_dyn(KQ_ROWS_PARAMS);
 template <bool AM>
 __global__ void kq_quantize_q8L(const float *x, int64_t x_stride, uint8_t *y, int nb, int64_t nblocks);
 
+template <int NCOL>
+__global__ void kq_rows_cols(const RowsColsArgs a);
+
 namespace {
 
+std::atomic<int> g_small_batch{MI355X_SMALL_BATCH_NODES};  // mi355x_small_batch()
 std::atomic<int> g_impl{MI355X_GEMV_AUTO};  // mi355x_gemv_impl()
 std::atomic<int> g_rows_waves{0};           // mi355x_gemv_waves: 0 = by size, else fixed
 
@@ -509,6 +513,93 @@ int launch_rows(const RowsPlan &pl, hipStream_t stream) {
     return timed_launch_lazy([&] { return LaunchInfo{rows_name(pl), rows_bytes(a, pl.fusedq)}; }, pl.fn, pl.grid,
                              dim3(pl.nwv * 64), pl.lds, stream, x, a.x2, a.w[0], a.res[0], a.nb, a.waves_total, grid,
                              cfg, a.rbase[0], a.rrem[0], a);
+}
+
+// ------------------------------------------------------------ small-batch GEMV (kq_rows_cols)
+int small_batch_select(int impl) { return impl < 0 ? g_small_batch.load() : g_small_batch.exchange(impl); }
+bool small_batch_fused() { return g_small_batch.load() == MI355X_SMALL_BATCH_FUSED && rows_enabled(); }
+
+// The plan of one kq_rows_cols launch over M = 2 .. 15 columns: kq_rows' descriptor conditions
+// (contiguous rows; Q4_K / Q5_K streams 16-byte aligned, Q6_K at any even address), the waves
+// and their rows by kq_rows' split over two workgroups of ROWS_COLS_WAVES waves per CU, the
+// chain batch, and the widest NCOL whose layout leaves both workgroups resident
+// (kTargetLds). MI355X_E_UNSUPPORTED: the caller keeps the kq_quantize + kq_gemv path.
+int plan_rows_cols(const mi355x_gemv_desc *d, int n_desc, int64_t K, int64_t M, RowsColsPlan &pl) {
+    if (n_desc < 1 || n_desc > MI355X_MAX_FUSED || K <= 0 || K % QK) return MI355X_E_INVAL;
+    if (M < 2 || M >= kMmqMinCols) return MI355X_E_UNSUPPORTED;
+    const int64_t nb = K / QK;
+    if (nb > 4096) return MI355X_E_UNSUPPORTED;
+    RowsColsArgs &a = pl.a;
+    memset(&a, 0, sizeof(a));
+    double bytes_total = 0;
+    for (int i = 0; i < n_desc; ++i) {
+        const int bb = block_bytes(d[i].type);
+        if (!bb) return MI355X_E_UNSUPPORTED;
+        if (d[i].n_rows < 0 || d[i].n_rows > 0x7fffffff) return MI355X_E_INVAL;
+        if (d[i].n_rows > 0) {
+            if (!d[i].w || !d[i].y) return MI355X_E_INVAL;
+            if (d[i].row_stride != (size_t)(nb * bb)) return MI355X_E_UNSUPPORTED;
+            if ((uintptr_t)d[i].w & (d[i].type == Q6_K ? 1u : 15u)) return MI355X_E_UNSUPPORTED;
+        }
+        bytes_total += (double)d[i].n_rows * bb;
+        a.tmask |= type_bit(d[i].type);
+        a.type[i] = d[i].type;
+        a.w[i] = (const uint8_t *)d[i].w;
+        a.y[i] = d[i].y;
+    }
+    a.n_desc = n_desc;
+    a.nb = (int)nb;
+    a.m_total = (int)M;
+    pl.bytes = bytes_total * nb + (double)M * nb * Q8L_STRIDE;
+    for (int i = 0; i < n_desc; ++i) pl.bytes += (double)d[i].n_rows * 4.0 * M;
+    if (bytes_total == 0) return MI355X_OK;  // (waves_total 0: nothing to launch)
+    const int64_t n_wg = 2 * (int64_t)num_cus();
+    int64_t wv[MI355X_MAX_FUSED], longest[MI355X_MAX_FUSED];
+    RowsArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    rows_split_waves(d, n_desc, nb, bytes_total, n_wg * ROWS_COLS_WAVES, wv);
+    const int64_t rpw = rows_split_rows(d, n_desc, nb, wv, ra, longest);
+    if (rpw > 0x7fffffff / 64) return MI355X_E_UNSUPPORTED;
+    a.rpw = (int)(rpw > 0 ? rpw : 1);
+    a.waves_total = ra.waves_total;
+    for (int i = 0; i <= MI355X_MAX_FUSED; ++i) a.wave_prefix[i] = ra.wave_prefix[i];
+    for (int i = 0; i < MI355X_MAX_FUSED; ++i) a.rbase[i] = ra.rbase[i], a.rrem[i] = ra.rrem[i];
+    // NCOL: the narrowest group that covers M, then down while the layout does not fit
+    pl.ncol = 0;
+    for (int nc = M > 4 ? 8 : M > 2 ? 4 : 2; nc >= 2; nc >>= 1) {
+        int bR = rows_cols_batch(nc, (int)nb), nbuf = 2;
+        if (bR >= a.rpw) bR = a.rpw, nbuf = 1;
+        const RowsColsLayout L = rows_cols_layout(nc, (int)nb, a.tmask, bR, nbuf, a.rpw);
+        if ((size_t)L.total > kTargetLds) continue;
+        pl.ncol = nc, pl.lds = (size_t)L.total;
+        a.bR = bR, a.nbuf = nbuf;
+        break;
+    }
+    if (!pl.ncol) return MI355X_E_UNSUPPORTED;
+    const int64_t grid = a.waves_total < n_wg ? a.waves_total : n_wg;
+    pl.grid = dim3((unsigned)(grid > 0 ? grid : 1), (unsigned)((M + pl.ncol - 1) / pl.ncol), 1);
+    return MI355X_OK;
+}
+
+// xq: M columns of plain Q8L blocks, column j at xq + j * nb * 304. y_cs / res / res_cs per matrix
+// (floats between columns; res null or res[i] null: no residual).
+int launch_rows_cols(RowsColsPlan &pl, const uint8_t *xq, const int64_t *y_cs, const float *const *res,
+                     const int64_t *res_cs, hipStream_t stream) {
+    RowsColsArgs &a = pl.a;
+    if (a.waves_total == 0) return MI355X_OK;
+    if (!xq || ((uintptr_t)xq & 15u)) return MI355X_E_WORKSPACE;
+    a.xq = xq;
+    for (int i = 0; i < a.n_desc; ++i) {
+        a.y_col_stride[i] = y_cs[i];
+        a.res[i] = res ? res[i] : nullptr;
+        a.res_col_stride[i] = res && res[i] ? res_cs[i] : 0;
+    }
+    if (!device_ok()) return MI355X_E_NODEVICE;
+    const auto fn = pl.ncol == 8 ? kq_rows_cols<8> : pl.ncol == 4 ? kq_rows_cols<4> : kq_rows_cols<2>;
+    allow_lds((const void *)fn, pl.lds);
+    return timed_launch_lazy(
+        [&] { return LaunchInfo{"kq::kq_rows_cols<" + std::to_string(pl.ncol) + ">", pl.bytes}; }, fn, pl.grid,
+        dim3(ROWS_COLS_WAVES * 64), pl.lds, stream, a);
 }
 
 int launch_quantize_q8L(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,

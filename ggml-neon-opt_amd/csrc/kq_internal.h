@@ -152,6 +152,22 @@ int rows_pro_kind(int prologue);  // MI355X_PRO_* -> ROWS_PRO_*
 bool rows_enabled();
 int gemv_impl_select(int impl);  // mi355x_gemv_impl / mi355x_gemv_waves: set, return the previous; < 0: query
 int rows_waves_select(int waves);
+// Small-batch GEMV (kq_rows_cols.hip; mi355x_small_batch): 2 <= M < kMmqMinCols columns of plain
+// Q8L blocks against up to MI355X_MAX_FUSED matrices in one launch. plan_rows_cols returns
+// MI355X_E_UNSUPPORTED where the rows are not contiguous / aligned for it or no NCOL's layout fits
+// (the caller keeps its other path); launch_rows_cols sets the operands and launches.
+struct RowsColsPlan {
+    RowsColsArgs a;
+    dim3 grid;
+    size_t lds;
+    int ncol;
+    double bytes;  // weights + Q8L blocks read + f32 outputs (gemv_bytes' convention)
+};
+int small_batch_select(int impl);  // mi355x_small_batch: set, return the previous; < 0: query
+bool small_batch_fused();          // MI355X_SMALL_BATCH_FUSED (and the row-stream kernels enabled)
+int plan_rows_cols(const mi355x_gemv_desc *d, int n_desc, int64_t K, int64_t M, RowsColsPlan &pl);
+int launch_rows_cols(RowsColsPlan &pl, const uint8_t *xq, const int64_t *y_cs, const float *const *res,
+                     const int64_t *res_cs, hipStream_t stream);
 int launch_quantize(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
                     hipStream_t stream);
 int launch_quantize_q8L(const float *x, int64_t x_stride_floats, void *y, int64_t k, int64_t nrows,
@@ -204,8 +220,10 @@ int launch_mmq_multi(const int *types, int n_mat, const void *const *w, const in
 int launch_rows_prologue_dbg(int pro, const float *x, const float *x2, float eps, int nb, int waves, uint8_t *out,
                              hipStream_t s);
 // prefill prologues: rms_norm(x) * w -> Q8L, swiglu(g, u) -> Q8L (nrows rows of n)
-int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s);
-int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s);
+// mmq: the prefill GEMMs' Q8L/mmq layout; false: the plain layout kq_rows_cols reads
+int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s,
+                        bool mmq = true);
+int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s, bool mmq = true);
 
 // ---------------------------------------------------------------- kq_ops.hip
 int launch_rms_norm(const float *x, const float *w, float *y, int64_t n, int64_t nrows, float eps, hipStream_t s);

@@ -42,6 +42,7 @@ struct PlanOpts {
     bool fuse, attn_oproj, layer_engine;  // mi355x_backend_set_fusion / _attn_oproj / _layer_engine
     const void *workspace;                // the shared-activation GEMMs need it aligned and large enough
     size_t workspace_size;
+    bool small_batch = false;  // mi355x_small_batch FUSED (no communicator): the batched patterns from 2 columns on
 };
 
 inline int64_t nelem(const mi355x_tensor *t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
@@ -56,8 +57,10 @@ inline const mi355x_tensor *other_operand(const mi355x_tensor *add, const mi355x
 }
 
 std::vector<Launch> plan_launches(const PlanOpts &o, mi355x_tensor *const *nodes, int n);
-// A batched MUL_MAT (ne11 >= 16) on the tile GEMMs, its activation shared through the workspace
+// A batched MUL_MAT (ne11 >= 16) on the tile GEMMs, its activation shared through the workspace;
+// under o.small_batch also one of 2 .. 15 columns that kq_rows_cols takes (cols_mm)
 bool batched_mm_shares(const PlanOpts &o, const mi355x_tensor *t);
+bool cols_mm(const PlanOpts &o, const mi355x_tensor *t);
 bool attn_feeds_batched_mm(const PlanOpts &o, const mi355x_tensor *t, const Launch &next, mi355x_tensor *const *nodes);
 bool kv_epilogue(mi355x_tensor *const *nodes, const Launch &l, const Launch &next, MmqKv &kv);
 void attn_desc_of(const mi355x_tensor *t, mi355x_attn_desc &a);  // rope_row left to the caller

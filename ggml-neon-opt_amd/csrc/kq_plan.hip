@@ -313,9 +313,22 @@ void attn_batch_desc_of(const mi355x_tensor *t, mi355x_attn_batch_desc &d) {
     d.n_tokens = (int)t->src[0]->ne[1];
 }
 
+// A MUL_MAT of 2 .. 15 columns that kq_rows_cols takes (mi355x_small_batch FUSED): the layout fits
+bool cols_mm(const PlanOpts &o, const mi355x_tensor *t) {
+    if (!o.small_batch || t->op != MI355X_OP_MUL_MAT) return false;
+    const mi355x_tensor *w = t->src[0], *x = t->src[1];
+    if (x->ne[1] < 2 || x->ne[1] >= kMmqMinCols || !is_kquant(w->type)) return false;
+    const mi355x_gemv_desc d = {w->type, w->data, w->ne[1], w->nb[1], (float *)t->data};
+    RowsColsPlan cp;
+    return plan_rows_cols(&d, 1, w->ne[0], x->ne[1], cp) == MI355X_OK;
+}
+
 bool batched_mm_shares(const PlanOpts &o, const mi355x_tensor *t) {
     if (t->op != MI355X_OP_MUL_MAT) return false;
     const mi355x_tensor *w = t->src[0], *x = t->src[1];
+    if (x->ne[1] < kMmqMinCols)
+        return cols_mm(o, t) && !(x->nb[1] & 3u) && !(t->nb[1] & 3u) && !((uintptr_t)o.workspace & 15u) &&
+               o.workspace_size >= mi355x_mul_mat_workspace_size(w->type, w->ne[0], w->ne[1], x->ne[1]);
     if (x->ne[1] < 16 || (x->nb[1] & 3u) || (t->nb[1] & 3u) || ((uintptr_t)o.workspace & 15u)) return false;
     if (!mmf_applies(w->type, w->data, w->ne[1], w->nb[1], x->ne[1], w->ne[0]) &&
         !mmq_applies(w->type, w->data, w->ne[1], w->nb[1], x->ne[1]))
@@ -325,6 +338,7 @@ bool batched_mm_shares(const PlanOpts &o, const mi355x_tensor *t) {
 
 std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *nodes, int n) {
     const bool fuse = po.fuse;
+    const int64_t min_cols = po.small_batch ? 2 : kMmqMinCols;  // the batched patterns' column threshold
     std::vector<Launch> out;
     const std::vector<int> readers = fuse ? count_readers(nodes, n) : std::vector<int>(n, 0);
     auto index_of = [&](const mi355x_tensor *u, int lo, int hi) {
@@ -457,7 +471,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                 return cnt > 0;
             };
             int cnt = 0;
-            if (nm && t->ne[1] >= 16 && i + 2 < n && nm->ne[0] == t->ne[0] && nm->ne[1] == t->ne[1] &&
+            if (nm && t->ne[1] >= min_cols && i + 2 < n && nm->ne[0] == t->ne[0] && nm->ne[1] == t->ne[1] &&
                 nm->src[1]->ne[0] == t->ne[0] && nelem(nm->src[1]) == t->ne[0] && t->nb[1] == (size_t)t->ne[0] * 4 &&
                 t->src[0]->nb[1] == (size_t)t->ne[0] * 4 && ((uintptr_t)t->src[0]->data & 15u) == 0 &&
                 !(nm->flags & MI355X_TENSOR_FLAG_OUTPUT) && shares_run(i + 2, nm, cnt) && readers[i + 1] == cnt) {
@@ -472,7 +486,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                 i += 2;
                 continue;
             }
-            if (t->op == MI355X_OP_SWIGLU && t->ne[1] >= 16 && t->ne[0] % MI355X_QK_K == 0 &&
+            if (t->op == MI355X_OP_SWIGLU && t->ne[1] >= min_cols && t->ne[0] % MI355X_QK_K == 0 &&
                 t->nb[1] == (size_t)t->ne[0] * 4 && t->src[0]->nb[1] == t->nb[1] && t->src[1]->nb[1] == t->nb[1] &&
                 nelem(t->src[0]) == nelem(t) && nelem(t->src[1]) == nelem(t) && !(t->flags & MI355X_TENSOR_FLAG_OUTPUT) &&
                 shares_run(i + 1, t, cnt) && readers[i] == cnt) {
@@ -485,7 +499,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                 i += 1;
                 continue;
             }
-            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= 16 && batched_mm_shares(po, t)) {
+            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= min_cols && batched_mm_shares(po, t)) {
                 // (the f16 GEMM: one weight type per launch)
                 int run = 1;
                 while (i + run < n && run < 4) {
@@ -505,7 +519,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
                     continue;
                 }
             }
-            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= 16 && i + 1 < n && nodes[i + 1]->op == MI355X_OP_ADD &&
+            if (t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] >= min_cols && i + 1 < n && nodes[i + 1]->op == MI355X_OP_ADD &&
                 elidable(t, readers[i]) && batched_mm_shares(po, t)) {
                 const mi355x_tensor *ad = nodes[i + 1], *other = other_operand(ad, t);
                 if (other && ad->ne[0] == t->ne[0] && ad->ne[1] == t->ne[1] && other->ne[0] == t->ne[0] &&

@@ -108,6 +108,8 @@ template __global__ void kq_quantize_q8L<true>(const float *, int64_t, uint8_t *
 // exactness guard, (x*scale)*w; silu(g)*u on the NEON path), quantized straight into the
 // GEMMs' Q8L blocks (row r's superblock b at (r*nb + b)*304); the f32 intermediate is
 // never written.
+// AM: the prefill GEMMs' layout; false (a batch under 16 columns, kq_rows_cols): the plain one.
+template <bool AM>
 __global__ void __launch_bounds__(256) kq_rms_norm_q8L(const float *__restrict__ x, const float *__restrict__ w,
                                                        uint8_t *__restrict__ yq, int64_t n, float eps) {
     extern __shared__ __attribute__((aligned(16))) double sb_sum[];
@@ -158,10 +160,11 @@ __global__ void __launch_bounds__(256) kq_rms_norm_q8L(const float *__restrict__
             v[k].z = __float_as_uint((t.z * scale) * m.z);
             v[k].w = __float_as_uint((t.w * scale) * m.w);
         }
-        quant16_store<true>(v, l, yq + (row * nb + b) * Q8L_STRIDE);  // (prefill only: Q8L/mmq)
+        quant16_store<AM>(v, l, yq + (row * nb + b) * Q8L_STRIDE);
     }
 }
 
+template <bool AM>
 __global__ void __launch_bounds__(256) kq_swiglu_q8L(const float *__restrict__ g, const float *__restrict__ u,
                                                      uint8_t *__restrict__ yq, int nb, int64_t nblocks) {
     const int64_t bi = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);  // superblock (row * nb + b)
@@ -178,22 +181,25 @@ __global__ void __launch_bounds__(256) kq_swiglu_q8L(const float *__restrict__ g
         v[k].w = __float_as_uint(v_silu(gv.w) * uv.w);
     }
     (void)nb;
-    quant16_store<true>(v, l, yq + bi * Q8L_STRIDE);  // (prefill only: Q8L/mmq)
+    quant16_store<AM>(v, l, yq + bi * Q8L_STRIDE);
 }
 
-int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s) {
+int launch_rms_norm_q8L(const float *x, const float *w, void *yq, int64_t n, int64_t nrows, float eps, hipStream_t s,
+                        bool mmq) {
     if (nrows == 0) return MI355X_OK;
     const size_t lds = (size_t)(n / QK) * 8 + 8;
     return timed_launch("kq::kq_rms_norm_q8L", (double)nrows * (n * 4.0 + (n / QK) * (double)Q8L_STRIDE) + n * 4.0,
-                        kq_rms_norm_q8L, dim3((unsigned)nrows), dim3(256), lds, s, x, w, (uint8_t *)yq, n, eps);
+                        mmq ? kq_rms_norm_q8L<true> : kq_rms_norm_q8L<false>, dim3((unsigned)nrows), dim3(256), lds, s, x, w,
+                        (uint8_t *)yq, n, eps);
 }
 
-int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s) {
+int launch_swiglu_q8L(const float *g, const float *u, void *yq, int64_t n, int64_t nrows, hipStream_t s, bool mmq) {
     const int64_t nb = n / QK, nblocks = nb * nrows;
     if (nblocks == 0) return MI355X_OK;
     const int64_t wgs = (nblocks + 15) / 16;
-    return timed_launch("kq::kq_swiglu_q8L", (double)nblocks * (QK * 8.0 + Q8L_STRIDE), kq_swiglu_q8L, dim3((unsigned)wgs),
-                        dim3(256), 0, s, g, u, (uint8_t *)yq, (int)nb, nblocks);
+    return timed_launch("kq::kq_swiglu_q8L", (double)nblocks * (QK * 8.0 + Q8L_STRIDE),
+                        mmq ? kq_swiglu_q8L<true> : kq_swiglu_q8L<false>, dim3((unsigned)wgs), dim3(256), 0, s, g, u,
+                        (uint8_t *)yq, (int)nb, nblocks);
 }
 
 // ---------------------------------------------------------------- kernel entry

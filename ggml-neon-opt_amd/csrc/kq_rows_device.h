@@ -355,6 +355,87 @@ __device__ __forceinline__ QuadOut quad_q6K(const uint8_t *blk, const uint8_t *a
     return r;
 }
 
+// ---- the same partials in two halves (kq_rows_cols: one weight block against several columns)
+// quad_unpack: lane s's 64 quants of the superblock at `blk` as four registers of 16 values, the
+// scale of each and what the mins' term multiplies; quad_dot: those against one activation block.
+// q[k] meets the activation's 16 values at aq + aoff(k), aq = ab + 16 + ae:
+//   Q4_K / Q5_K: ae = 64 s, aoff = {0, 16, 32, 48}; sc = {sc_lo, sc_lo, sc_hi, sc_hi},
+//                mn = {mn(2s), mn(2s), mn(2s+1), mn(2s+1)} against bsums[4s .. 4s+3];
+//   Q6_K:        ae = 128 n + 32 part2, aoff = {0, 64, 16, 80}; sc = the four scale bytes of those
+//                16-value groups, mn = scale bytes 4s .. 4s+3 against bsums[4s .. 4s+3].
+// Every sum is the exact int32 of quad_q4K / quad_q5K / quad_q6K (integer additions re-associated).
+struct QuadW {
+    u32x4 q[4];
+    int sc[4], mn[4];
+    int ae;
+    uint32_t dh;
+};
+
+template <int TYPE>
+__device__ __forceinline__ QuadW quad_unpack(const uint8_t *blk, int s) {
+    QuadW w;
+    if (TYPE == Q6_K) {
+        const uint32_t s4 = (uint32_t)((uintptr_t)blk & 3u);
+        const uint8_t *b = blk - s4;
+        const int n = s >> 1, part2 = s & 1;
+        const u32x4 L0 = realign(*(const u32x4a *)(b + 32 * s), *(const uint32_t *)(b + 32 * s + 16), s4);
+        const u32x4 L1 = realign(*(const u32x4a *)(b + 32 * s + 16), *(const uint32_t *)(b + 32 * s + 32), s4);
+        const u32x4 H0 = realign(*(const u32x4a *)(b + 128 + 32 * n), *(const uint32_t *)(b + 144 + 32 * n), s4);
+        const u32x4 H1 = realign(*(const u32x4a *)(b + 144 + 32 * n), *(const uint32_t *)(b + 160 + 32 * n), s4);
+        const uint32_t w208 = *(const uint32_t *)(b + 208);
+        const u32x4 SC = realign(*(const u32x4a *)(b + 192), w208, s4);
+        const uint32_t shl = (uint32_t)part2 * 2u;
+        w.q[0] = (L0 & 0x0f0f0f0fu) | (((H0 >> shl) & 0x03030303u) << 4);
+        w.q[1] = ((L0 >> 4) & 0x0f0f0f0fu) | (((H0 >> (shl + 4u)) & 0x03030303u) << 4);
+        w.q[2] = (L1 & 0x0f0f0f0fu) | (((H1 >> shl) & 0x03030303u) << 4);
+        w.q[3] = ((L1 >> 4) & 0x0f0f0f0fu) | (((H1 >> (shl + 4u)) & 0x03030303u) << 4);
+        w.ae = 128 * n + 32 * part2;
+        const int sb = w.ae >> 4;
+        w.sc[0] = sbyte(SC, sb), w.sc[1] = sbyte(SC, sb + 4), w.sc[2] = sbyte(SC, sb + 1), w.sc[3] = sbyte(SC, sb + 5);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w.mn[k] = sbyte(SC, 4 * s + k);
+        w.dh = (w208 >> (8u * s4)) & 0xffffu;
+    } else {
+        const u32x4 hdr = *(const u32x4 *)blk;
+        const int qo = TYPE == Q5_K ? 48 : 16;
+        const u32x4 q0 = *(const u32x4 *)(blk + qo + 32 * s);
+        const u32x4 q1 = *(const u32x4 *)(blk + qo + 16 + 32 * s);
+        w.q[0] = q0 & 0x0f0f0f0fu, w.q[1] = q1 & 0x0f0f0f0fu;
+        w.q[2] = (q0 >> 4) & 0x0f0f0f0fu, w.q[3] = (q1 >> 4) & 0x0f0f0f0fu;
+        if (TYPE == Q5_K) {
+            const u32x4 h0 = *(const u32x4 *)(blk + 16), h1 = *(const u32x4 *)(blk + 32);
+            const uint32_t sl = (uint32_t)(2 * s), shh = (uint32_t)(2 * s + 1);
+            w.q[0] |= ((h0 >> sl) & 0x01010101u) << 4, w.q[1] |= ((h1 >> sl) & 0x01010101u) << 4;
+            w.q[2] |= ((h0 >> shh) & 0x01010101u) << 4, w.q[3] |= ((h1 >> shh) & 0x01010101u) << 4;
+        }
+        const ScMn s0 = scales_k4(hdr, 2 * s), s1 = scales_k4(hdr, 2 * s + 1);
+        w.sc[0] = w.sc[1] = s0.sc_lo, w.sc[2] = w.sc[3] = s0.sc_hi;
+        w.mn[0] = w.mn[1] = s0.mn, w.mn[2] = w.mn[3] = s1.mn;
+        w.ae = 64 * s;
+        w.dh = hdr.x;
+    }
+    return w;
+}
+
+template <int TYPE>
+__device__ __forceinline__ QuadOut quad_dot(const QuadW &w, const uint8_t *ab, int s) {
+    const uint8_t *aq = ab + 16 + w.ae;
+    constexpr int o1 = TYPE == Q6_K ? 64 : 16, o2 = TYPE == Q6_K ? 16 : 32, o3 = TYPE == Q6_K ? 80 : 48;
+    const int d0 = dotacc(w.q[0], *(const u32x4 *)(aq), 0);
+    const int d1 = dotacc(w.q[1], *(const u32x4 *)(aq + o1), 0);
+    const int d2 = dotacc(w.q[2], *(const u32x4 *)(aq + o2), 0);
+    const int d3 = dotacc(w.q[3], *(const u32x4 *)(aq + o3), 0);
+    const uint2 bs = *(const uint2 *)(ab + 272 + 8 * s);
+    QuadOut r;
+    // |dot| < 2^17 (Q4_K / Q5_K: the two halves of a sub-block summed first, < 2^18): full-rate i24
+    if (TYPE == Q6_K) r.isum = __mul24(d0, w.sc[0]) + __mul24(d1, w.sc[1]) + __mul24(d2, w.sc[2]) + __mul24(d3, w.sc[3]);
+    else r.isum = __mul24(d0 + d1, w.sc[0]) + __mul24(d2 + d3, w.sc[2]);
+    r.imin = (int)(int16_t)(bs.x & 0xffffu) * w.mn[0] + (int)(int16_t)(bs.x >> 16) * w.mn[1] +
+             (int)(int16_t)(bs.y & 0xffffu) * w.mn[2] + (int)(int16_t)(bs.y >> 16) * w.mn[3];
+    r.dh = w.dh;
+    return r;
+}
+
 __device__ __forceinline__ int quad_sum(int v) {
     v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
     v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);  // quad_perm [2,3,0,1]

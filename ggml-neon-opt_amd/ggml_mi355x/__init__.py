@@ -63,6 +63,7 @@ MMQ_AUTO, MMQ_TILE64, MMQ_TILE128, MMQ_TILE128W, MMQ_TILE64W, MMQ_TILE192 = 0, 1
 PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
 ATTN_PROMPT_EXACT, ATTN_PROMPT_F16 = 0, 1  # attn_prompt_precision
 MOE_PREFILL_AUTO, MOE_PREFILL_GEMV, MOE_PREFILL_GROUPED = 0, 1, 2  # moe_prefill
+SMALL_BATCH_NODES, SMALL_BATCH_FUSED = 0, 1  # small_batch
 
 # Every symbol include/ggml_mi355x.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -104,6 +105,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_kv_shift",
     "mi355x_moe_route", "mi355x_mul_mat_id_workspace_size", "mi355x_mul_mat_id", "mi355x_moe_combine",
     "mi355x_moe_prefill",
+    "mi355x_small_batch", "mi355x_rows_cols_plan",
 )
 
 
@@ -349,6 +351,11 @@ def lib():
     if hasattr(L, "mi355x_moe_prefill"):
         L.mi355x_moe_prefill.argtypes = [i32]
         L.mi355x_moe_prefill.restype = i32
+    if hasattr(L, "mi355x_small_batch"):
+        L.mi355x_small_batch.argtypes = [i32]
+        L.mi355x_small_batch.restype = i32
+        L.mi355x_rows_cols_plan.argtypes = [i32, i64, i64, i64, vp, vp, vp, vp, vp]
+        L.mi355x_rows_cols_plan.restype = i32
     L.mi355x_attn_prompt_impl.argtypes = [i32]
     L.mi355x_attn_prompt_impl.restype = i32
     if hasattr(L, "mi355x_attn_prompt_precision"):  # (an older library under MI355X_LIB, A/B runs: without it)
@@ -665,6 +672,28 @@ def moe_prefill(impl):
     kq_gemv_id below), MOE_PREFILL_GEMV (always kq_gemv_id) or MOE_PREFILL_GROUPED (grouped for any T >= 1);
     the same bits either way. Part of the backend's plan key. Returns the previous value, E_INVAL for any other."""
     return int(_lib_with("mi355x_moe_prefill").mi355x_moe_prefill(impl))
+
+
+def small_batch(impl=-1):
+    """How 2 to 15 activation columns run (mi355x_small_batch): SMALL_BATCH_NODES (default: one launch per
+    graph node, a MUL_MAT as kq_quantize + kq_gemv) or SMALL_BATCH_FUSED (mul_mat and the backend's batched
+    patterns on kq_rows_cols, the multi-column row-stream GEMV; the same bits). step_batch, generate_batch,
+    prompts of 2 to 15 tokens and logprobs follow it. Part of the backend's plan key. -1 queries. Returns
+    the previous value, E_INVAL for any other."""
+    return int(_lib_with("mi355x_small_batch").mi355x_small_batch(impl))
+
+
+def rows_cols_plan(k, m, type=TYPE_Q4_K, n_rows=4096):
+    """The kq_rows_cols launch of one matrix of n_rows rows of k at m = 2 .. 15 columns
+    (mi355x_rows_cols_plan): {"ncol", "groups", "lds", "batch_rows", "rows_per_wave"}, or None where no layout fits and
+    the call keeps the per-node path."""
+    out = [ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)]
+    rc = _lib_with("mi355x_rows_cols_plan").mi355x_rows_cols_plan(type, k, n_rows, m, *[ctypes.byref(o) for o in out])
+    if rc == E_UNSUPPORTED:
+        return None
+    if rc:
+        raise Mi355xError("mi355x_rows_cols_plan failed: %d" % rc)
+    return dict(zip(("ncol", "groups", "lds", "batch_rows", "rows_per_wave"), (int(o.value) for o in out)))
 
 
 def gemv_fused_ext(mats, x, prologue=PRO_NONE, x2=None, eps=0.0, residual=None, epi_y=None, stream=None):

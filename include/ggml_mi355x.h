@@ -335,6 +335,29 @@ int mi355x_prefill_precision(int precision);
  * quantization covers 12 superblocks per wave). Returns the previous value, or
  * MI355X_E_INVAL. */
 int mi355x_gemv_waves(int waves);
+/* Small batches (2 <= ne11 < 16 activation columns: step_batch, generate_batch, short prompts).
+ *   MI355X_SMALL_BATCH_NODES (0, default)  one launch per graph node; a MUL_MAT is kq_quantize,
+ *                                          then kq_gemv<NCOL>.
+ *   MI355X_SMALL_BATCH_FUSED (1)           mi355x_mul_mat runs one kq_quantize_q8L launch, then
+ *       kq_rows_cols (csrc/kq_rows_cols.hip): the row-stream GEMV over groups of 2 / 4 / 8 columns,
+ *       bit-identical to NODES. The graph backend fuses its batched patterns from 2 columns on
+ *       (norm -> Q8L, SWIGLU -> Q8L, MUL_MATs on one activation in one launch, MUL_MAT + ADD).
+ *       A group is 8 columns up to K = 3840, 4 up to K = 7936, 2 up to K = 15872 (the LDS layout
+ *       that leaves two workgroups on a CU; more columns run as more groups of one launch). K above
+ *       that and rows that are not contiguous keep the NODES path. ne11 == 1 and ne11 >= 16 are the same in both
+ *       modes, and so is mi355x_mul_mat_workspace_size. MUL_MAT_ID and a backend with a communicator
+ *       plan as under NODES.
+ * Process-wide and part of the graph backend's plan key. -1 queries. Returns the previous value,
+ * or MI355X_E_INVAL. Replaces no reference interface. */
+#define MI355X_SMALL_BATCH_NODES 0
+#define MI355X_SMALL_BATCH_FUSED 1
+int mi355x_small_batch(int impl);
+/* The kq_rows_cols launch of one `type` matrix of n_rows rows of k at m = 2 .. 15 columns, without
+ * launching: *ncol = columns per workgroup (8, 4 or 2: the widest whose LDS layout leaves two
+ * workgroups on a CU), *groups = column groups (grid.y), *lds = bytes of LDS per workgroup,
+ * *batch_rows = rows per chain batch, *rows_per_wave = the most rows of one wave (any may be NULL). MI355X_E_UNSUPPORTED where no layout fits. */
+int mi355x_rows_cols_plan(int type, int64_t k, int64_t n_rows, int64_t m, int *ncol, int *groups, int64_t *lds,
+                          int *batch_rows, int *rows_per_wave);
 /* Experiment / diagnostic knobs of A/B runs and timing tools (replaces no reference
  * interface). The library reads no environment variable; every knob holds its product
  * default until set here, process-wide: "GEMV_DIAG", "GEMV_RING", "GEMV_PRE0",

@@ -5,7 +5,7 @@ synthetic Q4_K_M weights, hipGraph replay — and the kq_attn_batch launch besid
 kq_attn_prompt_group on a causal single-sequence batch of the same T and n_kv.
 
     python tools/batch_decode.py [--cells 512,2048] [--seqs 1,2,4,8] [--steps 64] [--warmup 16] [--reps 3]
-                                 [--form auto|head] [--attn-stream]
+                                 [--form auto|head] [--attn-stream] [--small-batch]
 
 The caches are pre-filled with random finite f16 values up to `cells` cells per sequence; in the
 batch decoder the sequences are interleaved (sequence s holds the cells c with c % n_seq == s).
@@ -148,6 +148,8 @@ def main():
                     help="head: one attention workgroup per query head and token at every size (attn_prompt_impl)")
     ap.add_argument("--attn-stream", action="store_true",
                     help="mi355x_attn_stream mode 1: caches past the attention kernels' sizes run on the streamed kernels")
+    ap.add_argument("--small-batch", action="store_true",
+                    help="mi355x_small_batch FUSED: the 2 to 15 column launches on kq_rows_cols")
     args = ap.parse_args()
     if not g.device_available():
         raise SystemExit("batch_decode: no gfx950 device (the measurement does not fall back)")
@@ -158,6 +160,8 @@ def main():
         g.attn_stream(1)
     if args.form == "head":
         g.attn_prompt_impl(g.ATTN_HEAD)
+    if args.small_batch:
+        g.small_batch(g.SMALL_BATCH_FUSED)
     be = g.Backend()
     gen = torch.Generator(device=dev)
     gen.manual_seed(7)
