@@ -195,7 +195,7 @@ size_t mi355x_row_size(int type, int64_t k) {
     const int64_t nb = k / QK;
     if (type == MI355X_TYPE_Q8_K) return (size_t)(nb * 292);
     if (type == MI355X_TYPE_F32) return (size_t)(k * 4);
-    return (size_t)(nb * block_bytes(type));
+    return (size_t)(nb * type_block_bytes(type));
 }
 
 const char *mi355x_version(void) { return "ggml-mi355x 0.1.0 (gfx950, wave64, K-quant GEMV)"; }
@@ -295,6 +295,7 @@ void mi355x_quantize_row_q8_K(const float *x, void *y, int64_t k) {
 }
 
 size_t mi355x_mul_mat_workspace_size(int src0_type, int64_t ne00, int64_t ne01, int64_t ne11) {
+    if (src0_type == Q3_K) return ne00 <= 0 || ne00 % QK || ne11 < 0 ? 0 : q3k_workspace(ne00, ne11);
     if (!block_bytes(src0_type) || ne00 <= 0 || ne00 % QK || ne11 < 0) return 0;
     if (ne11 == 0 || (ne11 == 1 && ne00 / QK <= kFusedQMaxNb)) return 0;
     size_t bytes = (size_t)ne11 * (size_t)(ne00 / QK) * Q8L_STRIDE;  // >= raw 292-B blocks
@@ -321,6 +322,8 @@ int mi355x_mul_mat_q8(int src0_type, const void *src0, int64_t ne00, int64_t ne0
     if (ne00 <= 0 || ne00 % QK) return MI355X_E_INVAL;
     if (ne11 > 1 && (nb11 < (size_t)(ne00 / QK) * 292 || nb1 < (size_t)ne01 * 4)) return MI355X_E_INVAL;
     if (ne11 > 0x7fffffff) return MI355X_E_INVAL;
+    if (src0_type == Q3_K)  // kernels of its own (kq_q3k.hip)
+        return q3k_mul_mat_q8(src0, ne00, ne01, nb01, src1_q8, ne11, nb11, dst, nb1, (hipStream_t)stream);
     mi355x_gemv_desc d = {src0_type, src0, ne01, nb01, dst};
     const int ncol = choose_ncol(ne11, (int)(ne00 / QK));
     GemvPlan pl;
@@ -337,11 +340,15 @@ int mi355x_mul_mat(int src0_type, const void *src0, int64_t ne00, int64_t ne01, 
                    int64_t ne11, size_t nb11, float *dst, size_t nb1, void *workspace, size_t workspace_size,
                    void *stream) {
     if (ne11 < 0 || ne01 < 0 || ne00 <= 0 || ne00 % QK) return MI355X_E_INVAL;
-    if (!block_bytes(src0_type)) return MI355X_E_UNSUPPORTED;
+    if (!type_block_bytes(src0_type)) return MI355X_E_UNSUPPORTED;
     if (ne11 == 0 || ne01 == 0) return MI355X_OK;
     if (!src1 || ((uintptr_t)src1 & 3u) || (nb11 & 3u) || !dst || ((uintptr_t)dst & 3u) || (nb1 & 3u))
         return MI355X_E_INVAL;
     if (ne11 > 1 && (nb11 < (size_t)ne00 * 4 || nb1 < (size_t)ne01 * 4)) return MI355X_E_INVAL;
+    if (src0_type == Q3_K)  // kernels of its own (kq_q3k.hip); the precision selector does not apply
+        return ne11 > 0x7fffffff ? MI355X_E_INVAL
+                                 : q3k_mul_mat(src0, ne00, ne01, nb01, src1, ne11, nb11, dst, nb1, workspace,
+                                               workspace_size, (hipStream_t)stream);
     if (ne11 == 1) {
         mi355x_gemv_desc d = {src0_type, src0, ne01, nb01, dst};
         return gemv_m1(&d, 1, src1, ne00, workspace, workspace_size, (hipStream_t)stream);
@@ -582,6 +589,22 @@ int mi355x_rows_cols_plan(int type, int64_t k, int64_t n_rows, int64_t m, int *n
     return MI355X_OK;
 }
 
+int mi355x_q3k_plan(int64_t k, int64_t n_rows, int64_t m, int fusedq, int *ncol, int *groups, int *waves,
+                    int *rows_per_wave, int *flush_rows, int64_t *lds) {
+    alignas(16) static const uint8_t dummy_w[16] = {0};  // the plan reads no weights
+    if (k <= 0 || k % QK) return MI355X_E_INVAL;
+    Q3kPlan pl;
+    const int rc = plan_q3k(dummy_w, k, n_rows, (size_t)(k / QK) * Q3K_BLOCK, m, fusedq != 0, pl);
+    if (rc) return rc;
+    if (ncol) *ncol = pl.ncol;
+    if (groups) *groups = (int)pl.grid.y;
+    if (waves) *waves = pl.a.waves_total;
+    if (rows_per_wave) *rows_per_wave = pl.a.rbase + (pl.a.rrem ? 1 : 0);
+    if (flush_rows) *flush_rows = Q3K_OUTS / pl.ncol;
+    if (lds) *lds = (int64_t)pl.lds;
+    return MI355X_OK;
+}
+
 int mi355x_gemv_waves(int waves) {
     if (waves < 0 || waves > ROWS_WAVES) return MI355X_E_INVAL;
     return rows_waves_select(waves);
@@ -652,6 +675,11 @@ static void vec_dot_dev(int type, const char *fn, int n, float *s, const void *v
     if (hipStreamSynchronize(c->st) != hipSuccess) die(fn, "hipStreamSynchronize failed");
 }
 
+void mi355x_vec_dot_q3_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t bx, const void *vy, size_t by,
+                              int nrc) {
+    (void)bs; (void)bx; (void)by;
+    vec_dot_dev(MI355X_TYPE_Q3_K, __func__, n, s, vx, vy, nrc);
+}
 void mi355x_vec_dot_q4_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t bx, const void *vy, size_t by,
                               int nrc) {
     (void)bs; (void)bx; (void)by;

@@ -21,9 +21,17 @@ constexpr int Q4_K = MI355X_TYPE_Q4_K;
 constexpr int Q5_K = MI355X_TYPE_Q5_K;
 constexpr int Q6_K = MI355X_TYPE_Q6_K;
 
+constexpr int Q3_K = MI355X_TYPE_Q3_K;
+
+// The types of the shared kernels (kq_rows, kq_gemv, kq_mmq, kq_mmf, kq_layer, ...): 0 for any
+// other type, Q3_K included, which is how their planners refuse it. Q3_K has kernels of its
+// own (kq_q3k.hip) and its size in type_block_bytes().
 __host__ __device__ constexpr int block_bytes(int type) {
     return type == Q4_K ? 144 : type == Q5_K ? 176 : type == Q6_K ? 210 : 0;
 }
+constexpr int Q3K_BLOCK = 110;  // block_q3_K: hmask[32] qs[64] scales[12] d
+// Every weight type the library stores: block_bytes' three and Q3_K (mi355x_row_size, get_rows).
+__host__ __device__ constexpr int type_block_bytes(int type) { return type == Q3_K ? Q3K_BLOCK : block_bytes(type); }
 
 // Argument block of the GEMV / small-M kernel (passed by value).
 struct GemvArgs {
@@ -305,6 +313,26 @@ __host__ __device__ constexpr int rows_cols_batch(int ncol, int nb) {
     const int fill = WAVE / ncol, cap = ROWS_COLS_RECS / (nb * ncol), step = (ROWS_SB + nb - 1) / nb;
     return cmax(cmax(fill < cap ? fill : cap, step), 1);
 }
+
+// ---------------------------------------------------------------- Q3_K GEMV (kq_q3k.hip)
+// kq_gemv_q3k: one workgroup per CU of Q3K_WAVES waves, each with a ring of Q3K_DEPTH steps of 8
+// superblocks (5.4 KB in flight per wave, 64 KB per CU); grid.y = the groups of NCOL columns.
+constexpr int Q3K_WAVES = 12;
+constexpr int Q3K_DEPTH = 6;
+constexpr int Q3K_FUSED_MAX_NB = 64;  // M = 1: x quantized inside the kernel up to K = 16384
+constexpr int Q3K_MAX_NB = 256;       // K <= 65536: one column's Q8L blocks beside the rings
+constexpr int Q3K_OUTS = 256;         // staged results per wave (floats): stored every 256 / NCOL rows
+struct Q3kArgs {
+    const uint8_t *w;        // n_rows packed rows of nb blocks, at any even address
+    float *y;                // dst column j at y + j * y_col_stride
+    int64_t y_col_stride;    // floats
+    const float *x;          // FUSEDQ: the f32 activation row
+    const uint8_t *xq;       // !FUSEDQ: Q8_K rows (292-B blocks), column j at xq + j * xq_col_stride
+    int64_t xq_col_stride;   // bytes
+    int n_rows, nb, m_total;
+    int waves_total, rbase, rrem;  // wave gw owns rbase rows, one more for gw < rrem
+    int nwv;                 // waves per workgroup
+};
 
 // Decode attention block (kq_attn_decode.hip): one workgroup per query head.
 struct AttnArgs {

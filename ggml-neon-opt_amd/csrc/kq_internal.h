@@ -176,6 +176,27 @@ size_t ext_x_bytes(int64_t k);  // the staged prologue's f32 row at the workspac
 int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *ws, size_t ws_size,
             hipStream_t stream, const mi355x_gemv_ext *ext = nullptr);
 
+// ---------------------------------------------------------------- kq_q3k.hip
+// Q3_K weights: one kernel, kq_gemv_q3k, for every batch size (M columns in groups of up to 8).
+// plan_q3k checks the matrix (MI355X_E_INVAL: an odd address or stride; MI355X_E_UNSUPPORTED:
+// rows not packed, K > 65536) and splits the rows; q3k_mul_mat / q3k_mul_mat_q8 are the arms of
+// mi355x_mul_mat / mi355x_mul_mat_q8, which have checked the other operands.
+struct Q3kPlan {
+    Q3kArgs a;
+    dim3 grid;
+    size_t lds;
+    int ncol;
+    bool fusedq;
+    double bytes;  // weights (once per column group) + activations read + f32 outputs
+};
+int plan_q3k(const void *w, int64_t K, int64_t N, size_t row_stride, int64_t M, bool fusedq, Q3kPlan &pl);
+int launch_q3k(const Q3kPlan &pl, hipStream_t stream);
+size_t q3k_workspace(int64_t K, int64_t M);  // mi355x_mul_mat_workspace_size's Q3_K arm
+int q3k_mul_mat(const void *w, int64_t K, int64_t N, size_t nb01, const float *x, int64_t M, size_t nb11, float *dst,
+                size_t nb1, void *ws, size_t ws_size, hipStream_t stream);
+int q3k_mul_mat_q8(const void *w, int64_t K, int64_t N, size_t nb01, const void *q8, int64_t M, size_t nb11, float *dst,
+                   size_t nb1, hipStream_t stream);
+
 // ---------------------------------------------------------------- kq_prefill_host.hip
 // prefill (ne11 >= kMmqMinCols) pieces, for the backend's shared-activation runs
 constexpr int64_t kMmqMinCols = 16;  // below this the NCOL GEMV streams the weights fewer times

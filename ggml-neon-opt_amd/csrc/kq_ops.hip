@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) kq_get_rows(int type, const uint8_t *__re
         return;
     }
     // the workgroup's superblocks [b0, b0 + nblk) of the row -> LDS (uniform over the workgroup)
-    const int bsz = block_bytes(type);
+    const int bsz = type_block_bytes(type);
     const int64_t b0 = (int64_t)blockIdx.x * 8;
     const int64_t left = k / QK - b0;
     const int nblk = (int)(left < 8 ? left : 8);
@@ -104,6 +104,20 @@ __global__ void __launch_bounds__(256) kq_get_rows(int type, const uint8_t *__re
         for (int i = 0; i < 8; ++i) {
             const int hb = q5 ? ((qh[i] >> (2 * j + h)) & 1) << 4 : 0;
             y[i] = __builtin_fmaf(d1, (float)(((q[i] >> (4 * h)) & 0xF) + hb), -m1);
+        }
+    } else if (type == MI355X_TYPE_Q3_K) {  // y = (d * sc) * q, two f32 multiplies, no fma
+        const uint8_t *blk = row + b * Q3K_BLOCK;
+        const float d = h2f((uint16_t)(blk[108] | (blk[109] << 8)));
+        const int n = e / 128, j = (e / 32) & 3, l0 = e % 32, is = e / 16;
+        const uint8_t *sc = blk + 96;
+        const int lo4 = is < 8 ? sc[is] & 15 : sc[is - 8] >> 4;
+        const int hi2 = (sc[8 + (is & 3)] >> (2 * (is >> 2))) & 3;
+        const float dl = d * (float)((lo4 | (hi2 << 4)) - 32);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int l = l0 + i;
+            const int q = ((blk[32 + 32 * n + l] >> (2 * j)) & 3) - (((blk[l] >> (4 * n + j)) & 1) ? 0 : 4);
+            y[i] = dl * (float)q;
         }
     } else {  // Q6_K
         const uint8_t *blk = row + b * 210;
@@ -717,8 +731,7 @@ extern "C" {
 int mi355x_get_rows(int type, const void *table, int64_t ne0, size_t row_stride, int64_t n_rows, const int32_t *ids,
                     int64_t n_ids, float *dst, void *stream) {
     if (!table || !ids || !dst || ne0 <= 0 || n_ids < 0 || n_rows < 0) return MI355X_E_INVAL;
-    if (type != MI355X_TYPE_F32 && type != MI355X_TYPE_Q4_K && type != MI355X_TYPE_Q5_K && type != MI355X_TYPE_Q6_K)
-        return MI355X_E_UNSUPPORTED;
+    if (type != MI355X_TYPE_F32 && !type_block_bytes(type)) return MI355X_E_UNSUPPORTED;
     if (ne0 % (type == MI355X_TYPE_F32 ? 8 : QK)) return MI355X_E_INVAL;
     if (row_stride < mi355x_row_size(type, ne0) && type != MI355X_TYPE_F32) return MI355X_E_INVAL;
     if (n_ids == 0) return MI355X_OK;

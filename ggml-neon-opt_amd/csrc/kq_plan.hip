@@ -9,6 +9,11 @@ namespace kq {
 namespace {
 
 bool is_kquant(int t) { return t == MI355X_TYPE_Q4_K || t == MI355X_TYPE_Q5_K || t == MI355X_TYPE_Q6_K; }
+// Q3_K (kq_q3k.hip) is a weight type of MUL_MAT and GET_ROWS nodes, and of no fusion: every
+// pattern below asks is_kquant, so a Q3_K matrix runs as a single node and breaks the pattern
+// around it into single nodes too.
+bool is_q3k_mm(const mi355x_tensor *t) { return t->op == MI355X_OP_MUL_MAT && t->src[0]->type == MI355X_TYPE_Q3_K; }
+bool is_wtype(int t) { return is_kquant(t) || t == MI355X_TYPE_Q3_K; }
 
 // Byte range [lo, hi) a tensor's data spans (ggml_nbytes: the last element of every
 // dim; K-quant rows are whole blocks).
@@ -18,7 +23,7 @@ struct Span {
 Span span_of(const mi355x_tensor *t) {
     Span s;
     if (!t || !t->data) return s;
-    const int64_t blck = is_kquant(t->type) ? MI355X_QK_K : 1;
+    const int64_t blck = is_wtype(t->type) ? MI355X_QK_K : 1;
     uint64_t bytes = (uint64_t)(t->ne[0] / blck) * t->nb[0];
     for (int d = 1; d < 4; ++d)
         if (t->ne[d] > 1) bytes += (uint64_t)(t->ne[d] - 1) * t->nb[d];
@@ -62,7 +67,9 @@ bool elidable(const mi355x_tensor *t, int readers) {
     return readers == 1 && !(t->flags & MI355X_TENSOR_FLAG_OUTPUT);
 }
 
-bool is_gemv_node(const mi355x_tensor *t) { return t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] == 1; }
+bool is_gemv_node(const mi355x_tensor *t) {
+    return t->op == MI355X_OP_MUL_MAT && t->src[1]->ne[1] == 1 && !is_q3k_mm(t);
+}
 
 // nodes[i] is an RMS_NORM and nodes[i + 1] the MUL of it (src[0]) by a weight: that MUL,
 // else null. Shapes and readers are the caller's conditions.
@@ -412,7 +419,7 @@ std::vector<Launch> plan_launches(const PlanOpts &po, mi355x_tensor *const *node
             head = i + 1;
         }
         const mi355x_tensor *h = nodes[head];
-        if (h->op == MI355X_OP_MUL_MAT && h->src[1]->ne[1] == 1 && (l.pro != MI355X_PRO_NONE || head == i)) {
+        if (is_gemv_node(h) && (l.pro != MI355X_PRO_NONE || head == i)) {
             int cnt = 1;
             while (head + cnt < n && cnt < MI355X_MAX_FUSED) {
                 const mi355x_tensor *u = nodes[head + cnt];
@@ -633,8 +640,13 @@ bool supports_op(const mi355x_tensor *op) {
         case MI355X_OP_MUL_MAT: {
             const mi355x_tensor *w = op->src[0], *x = op->src[1];
             if (!w || !x) return false;
-            if (!is_kquant(w->type) || x->type != MI355X_TYPE_F32 || op->type != MI355X_TYPE_F32) return false;
+            if (!is_wtype(w->type) || x->type != MI355X_TYPE_F32 || op->type != MI355X_TYPE_F32) return false;
             if (w->ne[0] % MI355X_QK_K || w->ne[0] != x->ne[0]) return false;
+            // Q3_K: kq_gemv_q3k's matrix (packed rows at an even address, K <= 65536)
+            if (w->type == MI355X_TYPE_Q3_K &&
+                (!w->data || ((uintptr_t)w->data & 1u) || w->ne[0] / MI355X_QK_K > Q3K_MAX_NB ||
+                 (w->ne[1] > 1 && w->nb[1] != (size_t)(w->ne[0] / MI355X_QK_K) * Q3K_BLOCK)))
+                return false;
             if (w->ne[2] != 1 || w->ne[3] != 1 || x->ne[2] != 1 || x->ne[3] != 1) return false;
             if (op->ne[0] != w->ne[1] || op->ne[1] != x->ne[1]) return false;
             if (x->nb[0] != 4 || op->nb[0] != 4) return false;  // contiguous rows
@@ -644,7 +656,7 @@ bool supports_op(const mi355x_tensor *op) {
             const mi355x_tensor *w = op->src[0], *ids = op->src[1];
             if (!w || !ids || ids->type != MI355X_TYPE_I32 || !ids->data || ids->nb[0] != 4 || !contig_f32(op))
                 return false;
-            if (w->type != MI355X_TYPE_F32 && !is_kquant(w->type)) return false;
+            if (w->type != MI355X_TYPE_F32 && !is_wtype(w->type)) return false;
             if (op->ne[1] > 1 && op->nb[1] != (size_t)op->ne[0] * 4) return false;  // dst rows packed (kernel: out + r*k)
             return op->ne[0] == w->ne[0] && op->ne[1] == ids->ne[0] && w->ne[0] % MI355X_QK_K == 0;
         }

@@ -19,9 +19,10 @@ LIB_PATH = os.environ.get("MI355X_LIB") or os.path.join(PKG_ROOT, "lib", "libggm
 
 TYPE_F32, TYPE_F16, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K, TYPE_Q8_K, TYPE_I32 = 0, 1, 12, 13, 14, 15, 26
 TYPE_I64 = 27  # cell indices of attn_batch / OP_ATTN_BATCH
+TYPE_Q3_K = 11  # mul_mat, mul_mat_q8, get_rows, vec_dot_q3_K_q8_K and the backend's MUL_MAT / GET_ROWS (kq_gemv_q3k)
 QK_K = 256
-BLOCK_BYTES = {TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210, TYPE_Q8_K: 292}
-TYPE_NAMES = {TYPE_Q4_K: "q4_K", TYPE_Q5_K: "q5_K", TYPE_Q6_K: "q6_K", TYPE_Q8_K: "q8_K", TYPE_F32: "f32"}
+BLOCK_BYTES = {TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210, TYPE_Q8_K: 292}
+TYPE_NAMES = {TYPE_Q3_K: "q3_K", TYPE_Q4_K: "q4_K", TYPE_Q5_K: "q5_K", TYPE_Q6_K: "q6_K", TYPE_Q8_K: "q8_K", TYPE_F32: "f32"}
 MAX_FUSED = 4
 OP_NONE, OP_MUL_MAT, OP_GET_ROWS, OP_RMS_NORM, OP_MUL, OP_ADD, OP_SWIGLU, OP_ROPE, OP_ATTN_DECODE, OP_ALL_GATHER, \
     OP_ALL_REDUCE = range(11)
@@ -106,6 +107,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_moe_route", "mi355x_mul_mat_id_workspace_size", "mi355x_mul_mat_id", "mi355x_moe_combine",
     "mi355x_moe_prefill",
     "mi355x_small_batch", "mi355x_rows_cols_plan",
+    "mi355x_vec_dot_q3_K_q8_K", "mi355x_q3k_plan",
 )
 
 
@@ -222,7 +224,7 @@ def lib():
     L.mi355x_backend_layer_error.argtypes = [ctypes.c_void_p]
     L.mi355x_backend_layer_error.restype = i32
     L.mi355x_quantize_row_q8_K.argtypes = [vp, vp, i64]
-    for n in ("q4_K", "q5_K", "q6_K"):
+    for n in ("q3_K", "q4_K", "q5_K", "q6_K"):
         getattr(L, f"mi355x_vec_dot_{n}_q8_K").argtypes = [i32, vp, sz, vp, sz, vp, sz, i32]
     L.mi355x_quantize_q8_K.argtypes = [vp, sz, vp, i64, i64, vp]
     L.mi355x_quantize_q8_K.restype = i32
@@ -694,6 +696,16 @@ def rows_cols_plan(k, m, type=TYPE_Q4_K, n_rows=4096):
     if rc:
         raise Mi355xError("mi355x_rows_cols_plan failed: %d" % rc)
     return dict(zip(("ncol", "groups", "lds", "batch_rows", "rows_per_wave"), (int(o.value) for o in out)))
+
+
+def q3k_plan(k, n_rows, m=1, fusedq=None):
+    """mi355x_q3k_plan: dict(ncol, groups, waves, rows_per_wave, flush_rows, lds) of the kq_gemv_q3k launch of a
+    packed Q3_K matrix; fusedq None: as mul_mat chooses (m == 1 and k <= 16384)."""
+    v = [ctypes.c_int() for _ in range(5)] + [ctypes.c_int64()]
+    fq = (m == 1 and k <= 16384) if fusedq is None else fusedq
+    _check(lib().mi355x_q3k_plan(ctypes.c_int64(k), ctypes.c_int64(n_rows), ctypes.c_int64(m), int(fq),
+                                 *[ctypes.byref(x) for x in v]), "mi355x_q3k_plan")
+    return dict(zip(("ncol", "groups", "waves", "rows_per_wave", "flush_rows", "lds"), (x.value for x in v)))
 
 
 def gemv_fused_ext(mats, x, prologue=PRO_NONE, x2=None, eps=0.0, residual=None, epi_y=None, stream=None):
@@ -1299,6 +1311,10 @@ def block_partials(type_, w, K, q8_row, stream=None):
 
 
 # ------------------------------------------- raw ggml surface (device pointers)
+def vec_dot_q3_K_q8_K(n, s, bs, vx, bx, vy, by, nrc):
+    lib().mi355x_vec_dot_q3_K_q8_K(n, s, bs, vx, bx, vy, by, nrc)
+
+
 def vec_dot_q4_K_q8_K(n, s, bs, vx, bx, vy, by, nrc):
     lib().mi355x_vec_dot_q4_K_q8_K(n, s, bs, vx, bx, vy, by, nrc)
 

@@ -102,11 +102,13 @@ class TokenSplit:
         matrices sliced by rows (and, in reduce mode, attn_output / ffn_down by superblock
         columns: the GGUF bytes of those superblocks, unchanged), everything else
         (token_embd, norms) replicated."""
-        from . import BLOCK_BYTES
+        from . import BLOCK_BYTES, TYPE_Q3_K, Mi355xError
         out = {}
         for k, v in weights.items():
             base = k.split(".")[-1]
             if isinstance(v, tuple) and base in self.rows:
+                if v[0] == TYPE_Q3_K:
+                    raise Mi355xError(f"row split: {k} is Q3_K, which the split token does not serve")
                 r0, r1 = self.rows[base]
                 w = v[1][r0:r1]
                 if base in self.cols:

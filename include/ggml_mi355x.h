@@ -68,6 +68,13 @@ typedef struct {
 } mi355x_block_q6_K;                     /* 210 bytes, 6.5625 bpw */
 
 typedef struct {
+    uint8_t hmask[MI355X_QK_K / 8];      /* third bit of the quants: bit 4n + j of hmask[l] */
+    uint8_t qs[MI355X_QK_K / 4];         /* low 2 bits                                      */
+    uint8_t scales[12];                  /* 16 sub-block scales, 6 bits each                */
+    mi355x_half d;                       /* super-block scale                               */
+} mi355x_block_q3_K;                     /* 110 bytes, 3.4375 bpw */
+
+typedef struct {
     float d;                             /* delta (negative when the block max is positive) */
     int8_t qs[MI355X_QK_K];              /* quants                                          */
     int16_t bsums[MI355X_QK_K / 16];     /* sums of 16 consecutive quants                    */
@@ -77,6 +84,7 @@ typedef struct {
 enum mi355x_type {
     MI355X_TYPE_F32  = 0,
     MI355X_TYPE_F16  = 1,
+    MI355X_TYPE_Q3_K = 11,   /* mul_mat, mul_mat_q8, get_rows and the graph backend's MUL_MAT / GET_ROWS */
     MI355X_TYPE_Q4_K = 12,
     MI355X_TYPE_Q5_K = 13,
     MI355X_TYPE_Q6_K = 14,
@@ -131,6 +139,14 @@ void mi355x_vec_dot_q5_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t
                               const void *vy, size_t by, int nrc);
 void mi355x_vec_dot_q6_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t bx,
                               const void *vy, size_t by, int nrc);
+/* Q3_K x Q8_K (block_q3_K: hmask[32], qs[64], scales[12], d; 110 bytes). The rule, restated from
+ * ggml's NEON kernel: element e = 128n + 32j + l is q = ((qs[32n + l] >> 2j) & 3) - (hmask[l] >>
+ * (4n + j) & 1 ? 0 : 4); the 16-element group is = e / 16 has the 6-bit scale sc = (lo4 | hi2 << 4)
+ * - 32, lo4 = is < 8 ? scales[is] & 15 : scales[is - 8] >> 4, hi2 = (scales[8 + (is & 3)] >>
+ * 2 * (is >> 2)) & 3; per superblock isum = sum sc * sum q * y8 (exact), and sumf = fmaf(y.d *
+ * fp16(x.d), (float)isum, sumf) over the superblocks in order. No bsums are read. */
+void mi355x_vec_dot_q3_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t bx,
+                              const void *vy, size_t by, int nrc);
 
 /* ----------------------------------------------------- stream-level API */
 /* Quantize `nrows` f32 rows of k elements (row stride x_stride bytes) into
@@ -138,15 +154,27 @@ void mi355x_vec_dot_q6_K_q8_K(int n, float *s, size_t bs, const void *vx, size_t
 int mi355x_quantize_q8_K(const float *x, size_t x_stride, void *y, int64_t k, int64_t nrows,
                          void *stream);
 
-/* MUL_MAT for src0 in {Q4_K, Q5_K, Q6_K}: dst[N x M] = src0[N x K] . src1[K x M]
+/* MUL_MAT for src0 in {Q3_K, Q4_K, Q5_K, Q6_K}: dst[N x M] = src0[N x K] . src1[K x M]
  * with ggml conventions: src0 row i at src0 + i*nb01 (ne00 = K, ne01 = N);
  * src1 column j (ggml row j of src1) at src1 + j*nb11, K floats; dst column j at
  * dst + j*nb1, N floats. Semantics = ggml_compute_forward_mul_mat: src1 is first
  * quantized to Q8_K (bit-exact), then every dst element is vec_dot(row, col).
  * M == 1 with K <= 8192 quantizes inside the GEMV kernel (no workspace); other
  * shapes need a workspace of mi355x_mul_mat_workspace_size() bytes (the Q8_K
- * copy of src1). Async on `stream`. */
+ * copy of src1). Async on `stream`.
+ * Q3_K (kq_gemv_q3k, every M in groups of up to 8 columns): rows contiguous (nb01 == K / 256 * 110,
+ * else MI355X_E_UNSUPPORTED) at an even address (else MI355X_E_INVAL), K <= 65536; M == 1 with
+ * K <= 16384 quantizes inside the kernel. mi355x_prefill_precision does not apply to it. The fused
+ * entries below (mi355x_gemv_fused*, mi355x_mul_mat_id, the layer engine) refuse the type. */
 size_t mi355x_mul_mat_workspace_size(int src0_type, int64_t ne00, int64_t ne01, int64_t ne11);
+/* The plan of the kq_gemv_q3k launch mi355x_mul_mat would issue for a packed Q3_K matrix of n_rows
+ * rows of k elements against m columns (no launch, no device access): *ncol = columns per group
+ * (1 / 2 / 4 / 8), *groups = column groups (each streams the weights once), *waves = waves that own
+ * rows, *rows_per_wave = the most rows of one wave, *flush_rows = rows a wave stages before it stores
+ * them, *lds = LDS bytes per workgroup (any may be NULL). fusedq: M == 1 with x quantized inside the
+ * kernel (k <= 16384). Returns MI355X_OK or plan errors as mi355x_mul_mat would. */
+int mi355x_q3k_plan(int64_t k, int64_t n_rows, int64_t m, int fusedq, int *ncol, int *groups, int *waves,
+                    int *rows_per_wave, int *flush_rows, int64_t *lds);
 int mi355x_mul_mat(int src0_type, const void *src0, int64_t ne00, int64_t ne01, size_t nb01,
                    const float *src1, int64_t ne11, size_t nb11,
                    float *dst, size_t nb1,
