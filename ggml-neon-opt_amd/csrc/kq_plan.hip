@@ -203,6 +203,9 @@ bool layer_match(const PlanOpts &po, mi355x_tensor *const *nodes, int n, int i, 
 // supports_op: contiguous f32 with data
 bool contig_f32(const mi355x_tensor *t) { return t && t->type == MI355X_TYPE_F32 && t->nb[0] == 4 && t->data; }
 
+// f32 rows that follow each other (one row: whatever nb[1] says)
+bool packed_rows(const mi355x_tensor *t) { return t->ne[1] == 1 || t->nb[1] == (size_t)t->ne[0] * 4; }
+
 // A MOE_ROUTE node's output: T records of I32 [2 * n_used], 4-byte aligned, nb[1] the record stride
 bool moe_records_ok(const mi355x_tensor *t, int n_used, int64_t T) {
     return t->type == MI355X_TYPE_I32 && t->data && !((uintptr_t)t->data & 3u) && t->nb[0] == 4 && n_used >= 1 &&
@@ -667,12 +670,19 @@ bool supports_op(const mi355x_tensor *op) {
                    nelem(op->src[0]) == nelem(op) && ((uintptr_t)op->src[0]->data & 15u) == 0;
         case MI355X_OP_MUL:
         case MI355X_OP_ADD:
-            // src1 the same shape, or one row repeated over the rows (ggml_mul by the norm weight)
-            return contig_f32(op) && contig_f32(op->src[0]) && contig_f32(op->src[1]) && nelem(op->src[0]) == nelem(op) &&
+            // src1 the same shape, or one row repeated over the rows (ggml_mul by the norm weight).
+            // kq_mul walks nelem packed floats, so rows a stride apart are refused. An ADD with such
+            // rows is taken: MmAdd folds it into the GEMM with its strides (run as a node of its own
+            // it is still walked as packed).
+            if (!contig_f32(op) || !contig_f32(op->src[0]) || !contig_f32(op->src[1])) return false;
+            if (op->op == MI355X_OP_MUL && !(packed_rows(op) && packed_rows(op->src[0]) && packed_rows(op->src[1])))
+                return false;
+            return nelem(op->src[0]) == nelem(op) &&
                    (nelem(op->src[1]) == nelem(op) || (nelem(op->src[1]) == op->ne[0] && op->nb[1] == (size_t)op->ne[0] * 4));
-        case MI355X_OP_SWIGLU:
+        case MI355X_OP_SWIGLU:  // kq_swiglu walks nelem packed floats
             return contig_f32(op) && contig_f32(op->src[0]) && contig_f32(op->src[1]) &&
-                   nelem(op->src[0]) == nelem(op) && nelem(op->src[1]) == nelem(op);
+                   nelem(op->src[0]) == nelem(op) && nelem(op->src[1]) == nelem(op) && packed_rows(op) &&
+                   packed_rows(op->src[0]) && packed_rows(op->src[1]);
         case MI355X_OP_ROPE:
             return contig_f32(op) && contig_f32(op->src[0]) && op->src[1] && op->src[1]->type == MI355X_TYPE_I32 &&
                    contig_f32(op->src[2]) && op->op_params[0] > 0 && op->op_params[0] <= op->ne[0] &&
