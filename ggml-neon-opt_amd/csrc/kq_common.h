@@ -25,7 +25,8 @@ constexpr int Q3_K = MI355X_TYPE_Q3_K;
 
 // The types of the shared kernels (kq_rows, kq_gemv, kq_mmq, kq_mmf, kq_layer, ...): 0 for any
 // other type, Q3_K included, which is how their planners refuse it. Q3_K has kernels of its
-// own (kq_q3k.hip) and its size in type_block_bytes().
+// own (kq_q3k.hip; a body in kq_mmq's tile loop that only q3k_mul_mat reaches) and its size in
+// type_block_bytes().
 __host__ __device__ constexpr int block_bytes(int type) {
     return type == Q4_K ? 144 : type == Q5_K ? 176 : type == Q6_K ? 210 : 0;
 }
@@ -202,8 +203,18 @@ __host__ __device__ constexpr int mmq_waves(int rt, int cw) { return rt / 16; }
 // conflicted for 71 % of the LDS's active cycles at 224 (profiles/r06_prefill_stall.md).
 constexpr int MMQ_Q6_STRIDE = 240;
 static_assert(MMQ_Q6_STRIDE % 16 == 0 && MMQ_Q6_STRIDE >= 224, "whole granules");
+// Q3_K rows (110 B at any even address) staged the same way: the 7 or 8 granules from the 16-B
+// boundary below the block (offset + 110 <= 124), at MMQ_Q3_STRIDE = 144 bytes. 128 would hold
+// them, but consecutive rows would then start 32 dwords apart: two bank offsets for a wave's 32
+// rows on the 64 banks. At 36 dwords they take 16 (gcd(36, 64) = 4), as Q4_K's 144-B rows do,
+// and the tile has Q4_K's buffer size and DMA instruction count (9 per 64 rows).
+constexpr int MMQ_Q3_STRIDE = 144;
+static_assert(MMQ_Q3_STRIDE % 16 == 0 && MMQ_Q3_STRIDE >= 128, "whole granules");
+__host__ __device__ constexpr int mmq_row_bytes(int type) {
+    return type == Q6_K ? MMQ_Q6_STRIDE : type == Q3_K ? MMQ_Q3_STRIDE : block_bytes(type);
+}
 __host__ __device__ constexpr int mmq_buf_bytes(int type, int rt, int cw) {
-    return mmq_cols(cw) * Q8L_STRIDE + rt * (type == Q6_K ? MMQ_Q6_STRIDE : block_bytes(type));
+    return mmq_cols(cw) * Q8L_STRIDE + rt * mmq_row_bytes(type);
 }
 constexpr int ROWS_RECS = 64;   // chain records per wave per batch (soft cap)
 __host__ __device__ constexpr int rows_gran(int type) { return block_bytes(type) + 1; }

@@ -177,10 +177,13 @@ int gemv_m1(const mi355x_gemv_desc *d, int n, const float *x, int64_t k, void *w
             hipStream_t stream, const mi355x_gemv_ext *ext = nullptr);
 
 // ---------------------------------------------------------------- kq_q3k.hip
-// Q3_K weights: one kernel, kq_gemv_q3k, for every batch size (M columns in groups of up to 8).
+// Q3_K weights: kq_gemv_q3k for every batch size (M columns in groups of up to 8), and from
+// mi355x_q3k_prefill's columns on kq_mmq's Q3_K body through launch_mmq (q3k_mul_mat alone).
 // plan_q3k checks the matrix (MI355X_E_INVAL: an odd address or stride; MI355X_E_UNSUPPORTED:
 // rows not packed, K > 65536) and splits the rows; q3k_mul_mat / q3k_mul_mat_q8 are the arms of
 // mi355x_mul_mat / mi355x_mul_mat_q8, which have checked the other operands.
+int q3k_prefill_mode();  // mi355x_q3k_prefill (part of ops_selector_key)
+int q3k_prefill_set(int impl);
 struct Q3kPlan {
     Q3kArgs a;
     dim3 grid;

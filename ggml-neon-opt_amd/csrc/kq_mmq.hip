@@ -17,10 +17,10 @@
 //    the result equals the oracle's mul_mat (and ggml's vec_dot loop) bit for bit.
 // Tiles: a workgroup of RT / 16 waves owns 64 * CW activation columns x RT weight rows (2 x
 // RT / 32 waves of 32 rows x 32 * CW columns); each superblock's Q8L activation blocks (304 B
-// per column) and weight blocks (144 / 176 / 240 B per row) are double-buffered in LDS by
+// per column) and weight blocks (144 / 176 / 240 B per row, Q3_K 144) are double-buffered in LDS by
 // LDS-DMA, a fixed number of DMA instructions per wave and superblock.
 // The steps, one function each: mmq_tile_of (which tile), mmq_issue (a superblock's DMA),
-// q45_superblock / q6_superblock (a superblock of one wave's 32 x 32 * CW outputs),
+// q45_superblock / q6_superblock / q3_superblock (a superblock of one wave's 32 x 32 * CW outputs),
 // mmq_store (the outputs, the ADD and the KV-cache epilogue); mmq_tile is the loop.
 // kq_mmq_id is the same loop over the pairs of a MoE prompt grouped by expert (mi355x_mul_mat_id's
 // grouped form): a tile's weight base, activation rows and output rows come from kq_moe_group's table.
@@ -30,6 +30,7 @@
 //   row = (reg&3) + 8(reg>>2) + 4h (mmq_acc_col: the activation column, A being the activation).
 #include "kq_device.h"
 #include "kq_ops_device.h"
+#include "kq_q3k_device.h"
 
 // Timing-only ablations of kq_mmq<Q4_K>, compile time so the product kernel carries none of
 // them (as run-time branches they cost 40 VGPRs and a wave per SIMD): 1 no chain epilogue,
@@ -63,10 +64,9 @@ __device__ __forceinline__ uint32_t as_u32(u16x2 v) {
 // the activation tile is fetched once per RT rows, so RT = 128 halves its LDS-DMA traffic.
 // Weight bytes per row in the LDS tile: the superblock itself (Q4_K 144, Q5_K 176,
 // 16-B aligned rows), or for Q6_K (210 B, any alignment) the 14 granules from the
-// 16-B boundary below it.
-__host__ __device__ constexpr int mmq_row_bytes(int type) { return type == Q6_K ? MMQ_Q6_STRIDE : block_bytes(type); }
-__host__ __device__ constexpr int mmq_b_instr(int type, int rt) { return rt * mmq_row_bytes(type) / 1024; }  // 9 / 11 / 15 per 64 rows
-static_assert(64 * MMQ_Q6_STRIDE % 1024 == 0, "whole DMA instructions per 64 rows");
+// 16-B boundary below it, for Q3_K (110 B, any even address) the 7 or 8 (mmq_row_bytes, kq_common.h).
+__host__ __device__ constexpr int mmq_b_instr(int type, int rt) { return rt * mmq_row_bytes(type) / 1024; }  // 9 / 11 / 15, Q3_K 9 per 64 rows
+static_assert(64 * MMQ_Q6_STRIDE % 1024 == 0 && 64 * MMQ_Q3_STRIDE % 1024 == 0, "whole DMA instructions per 64 rows");
 
 // Accumulator element i (of 16) of a lane in half h of a 32 x 32 MFMA result -> its activation
 // column within the 32-column tile (the lane's weight row is lane & 31).
@@ -204,6 +204,66 @@ __device__ __forceinline__ void q6_superblock(const MmqArgs &a, const uint8_t *A
 #pragma unroll
         for (int i = 0; i < 16; ++i)  // sum += d_all*y.d*(isum - 32*isum_mins)
             sumf[ct][i] = fmaf(xd * yd[16 * ct + i], (float)(256 * shi[ct][i] + slo[ct][i]), sumf[ct][i]);
+}
+
+// Q3_K superblock of one wave's 32 rows x 32 * CW columns (the rule: kq_q3k_device.h). Chunk
+// c = 4n + j is elements 128n + 32j + l, l < 32; a lane's half h of it, l in [16h, 16h + 16), is
+// the one scale group is = 2c + h. So a lane reads hmask[16h ..] once (bit c of it serves chunk
+// c), qs[32n + 16h ..] once per n (bits 2j of it serve chunk 4n + j), the 12 scale bytes and d.
+// The scaled weight W = sc * q, sc in [-32, 31], q in [-4, 3], lies in [-124, 128]: +128 is no
+// int8, but -W in [-128, 124] is, so the operand carries -W. u = q + 4 in 0 .. 7 per byte, spread
+// to 16-bit lanes; one packed 16-bit multiply-add T = u * (-sc) + 4 * sc = -W mod 2^16, whose low
+// byte is the operand. One MFMA per chunk and column tile into ONE accumulator over the whole
+// superblock, |S| <= 256 * 128 * 128 = 2^22, and isum = -S: no mins, no bsums, no hi / lo split.
+// Then kq_gemv_q3k's one fmaf(y.d * f32(x.d), (float)isum, sumf) per superblock, in order.
+// The row lies at its byte offset `mis` in the 16-B granules the DMA staged (mmq_issue): aligned
+// dwords + realign, all inside [Bbase, Bbase + 126). Arguments as q6_superblock's.
+template <int CW>
+__device__ __forceinline__ void q3_superblock(const MmqArgs &a, const uint8_t *A, int c0, const uint8_t *Bbase, int n, int b,
+                                              int r, int h, f32x16 *sumf) {
+    const int nrow = n < a.n_rows ? n : a.n_rows - 1;  // the DMA clamped the same way
+    const uint32_t mis = (uint32_t)((uintptr_t)(a.w + (int64_t)nrow * a.row_stride + (int64_t)b * Q3K_BLOCK) & 15u);
+    const uint8_t *region = Bbase + mis;
+    const uint32_t s4 = (uint32_t)((uintptr_t)region & 3u);  // 0 or 2
+    const uint8_t *bb = region - s4;
+    const u32x4 HM = realign(*(const u32x4a *)(bb + 16 * h), *(const uint32_t *)(bb + 16 * h + 16), s4);
+    const u32x4 SW = *(const u32x4a *)(bb + 96);  // scales[12], then d
+    const uint32_t S[3] = {__builtin_amdgcn_alignbyte(SW.y, SW.x, s4), __builtin_amdgcn_alignbyte(SW.z, SW.y, s4),
+                           __builtin_amdgcn_alignbyte(SW.w, SW.z, s4)};
+    const uint32_t dh = (SW.w >> (8u * s4)) & 0xffffu;
+    i32x16 acc[CW];
+#pragma unroll
+    for (int ct = 0; ct < CW; ++ct) acc[ct] = i32x16{};
+#pragma unroll
+    for (int nh = 0; nh < 2; ++nh) {
+        const u32x4 QS = realign(*(const u32x4a *)(bb + 32 + 32 * nh + 16 * h), *(const uint32_t *)(bb + 48 + 32 * nh + 16 * h), s4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = 4 * nh + j;  // chunk: elements 32c .. 32c+31
+            const int sc = q3k_scale(S, 2 * c + h);
+            const uint32_t nsw = (uint32_t)(-sc) & 0xffffu, cw = (uint32_t)(4 * sc) & 0xffffu;
+            const u16x2 nscp = {(uint16_t)nsw, (uint16_t)nsw}, cp = {(uint16_t)cw, (uint16_t)cw};
+            u32x4 bw;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t u = ((QS[k] >> (2u * j)) & 0x03030303u) | (((HM[k] >> (uint32_t)c) & 0x01010101u) << 2);  // q + 4
+                const uint32_t t0 = as_u32(as_u16x2(__builtin_amdgcn_perm(0u, u, 0x0c010c00u)) * nscp + cp);  // values 0, 1
+                const uint32_t t1 = as_u32(as_u16x2(__builtin_amdgcn_perm(0u, u, 0x0c030c02u)) * nscp + cp);  // values 2, 3
+                bw[k] = __builtin_amdgcn_perm(t1, t0, 0x06040200u);
+            }
+#pragma unroll
+            for (int ct = 0; ct < CW; ++ct) {
+                const u32x4 act = *(const u32x4 *)(A + (c0 + 32 * ct + r) * Q8L_STRIDE + 16 + 32 * c + 16 * h);
+                acc[ct] = mfma_i8(act, bw, acc[ct]);
+            }
+        }
+    }
+    const float xd = h2f(dh);
+#pragma unroll
+    for (int ct = 0; ct < CW; ++ct)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            sumf[ct][i] = fmaf(mmq_yd(A, c0 + 32 * ct, i, h) * xd, (float)(-acc[ct][i]), sumf[ct][i]);
 }
 
 // Q4_K / Q5_K superblock of one wave's 32 rows x 32 * CW columns: sumi = 8 * S8 + S1 over the 8
@@ -407,7 +467,7 @@ __device__ __forceinline__ int mmq_a_col(const MmqArgs &a, int col0, int t, int 
 template <int TYPE, int RT, int CW, bool ID = false>
 __device__ __forceinline__ void mmq_issue(const MmqArgs &a, LDS uint8_t *buf, int b, int col0, int row0, int wave, int lane,
                                           const int *xr = nullptr) {
-    constexpr int BSZ = block_bytes(TYPE);
+    constexpr int BSZ = type_block_bytes(TYPE);
     constexpr int A_BYTES = mmq_cols(CW) * Q8L_STRIDE;
     constexpr int A_INSTR = mmq_a_instr(CW);
     constexpr int NW = mmq_nw(TYPE, RT, CW);
@@ -429,6 +489,10 @@ __device__ __forceinline__ void mmq_issue(const MmqArgs &a, LDS uint8_t *buf, in
             if (TYPE == Q6_K && piece > 13) piece = 13;  // padding granules: the row's last one again
             rw = row0 + rw < a.n_rows ? row0 + rw : a.n_rows - 1;
             const uintptr_t blk = (uintptr_t)(a.w + (int64_t)rw * a.row_stride + (int64_t)b * BSZ);
+            if (TYPE == Q3_K) {  // the 7 or 8 granules that hold a byte of the block; the others repeat its last one
+                const int last = (int)(((blk & 15u) + BSZ - 1) >> 4);
+                piece = piece < last ? piece : last;
+            }
             src = (const uint8_t *)(blk & ~(uintptr_t)15) + 16 * piece;
             dma16(src, buf + A_BYTES + 1024 * (t - A_INSTR));
         }
@@ -529,6 +593,7 @@ __device__ __forceinline__ void mmq_tile_at(const MmqArgs &a, int col0, int row0
         const uint8_t *buf = smem + (b & 1) * BUF;
         const uint8_t *Bt = buf + A_BYTES + (32 * wn + r) * mmq_row_bytes(TYPE);  // this lane's weight row
         if (TYPE == Q6_K) q6_superblock<CW>(a, buf, 32 * CW * wm, Bt, row0 + 32 * wn + r, b, r, h, sumf);
+        else if (TYPE == Q3_K) q3_superblock<CW>(a, buf, 32 * CW * wm, Bt, row0 + 32 * wn + r, b, r, h, sumf);
         else q45_superblock<TYPE, CW>(buf, 32 * CW * wm, Bt, r, h, sumf);
     }
     mmq_store<CW>(a, sumf, row0 + 32 * wn + r, col0 + 32 * CW * wm, h, ID ? id->pair : nullptr);
@@ -620,5 +685,9 @@ KQ_MMQ_INST(64, 2)
 // the selector-only 12-wave tile (MI355X_MMQ_TILE192): Q4_K / Q5_K
 template __global__ void kq_mmq<Q4_K, 192, 1>(const MmqArgs a);
 template __global__ void kq_mmq<Q5_K, 192, 1>(const MmqArgs a);
+// Q3_K: the shapes mmq_shape's Q4_K choices reach (launch_mmq_tiles maps a forced 64 x 128 or 192 x 64 to one of them)
+template __global__ void kq_mmq<Q3_K, 64, 1>(const MmqArgs a);
+template __global__ void kq_mmq<Q3_K, 128, 1>(const MmqArgs a);
+template __global__ void kq_mmq<Q3_K, 128, 2>(const MmqArgs a);
 
 }  // namespace kq

@@ -76,6 +76,10 @@ const void *mmq_fn(int type, bool mixed, MmqShape sh) {
          : type == Q5_K ? (const void *)kq_mmq<Q5_K, RT, CW>                   \
          : type == Q6_K ? (const void *)kq_mmq<Q6_K, RT, CW>                   \
                         : (const void *)kq_mmq<Q4_K, RT, CW>;
+    if (type == Q3_K && !mixed)  // (launch_mmq_tiles keeps sh among these three)
+        return sh.rt == 64    ? (const void *)kq_mmq<Q3_K, 64, 1>
+               : sh.cw == 2 ? (const void *)kq_mmq<Q3_K, 128, 2>
+                            : (const void *)kq_mmq<Q3_K, 128, 1>;
     if (sh.rt == 192 && !mixed && type != Q6_K)
         return type == Q5_K ? (const void *)kq_mmq<Q5_K, 192, 1> : (const void *)kq_mmq<Q4_K, 192, 1>;
     if (sh.rt == 128 && sh.cw == 2) KQ_MMQ_PICK(128, 2)
@@ -85,7 +89,7 @@ const void *mmq_fn(int type, bool mixed, MmqShape sh) {
 #undef KQ_MMQ_PICK
 }
 // two superblock buffers: mmq_cols(cw) Q8L columns + rt weight rows (Q6_K: MMQ_Q6_STRIDE, the 224-B
-// granule span + padding), +16 B for the Q6_K realign reads past the last row
+// granule span + padding; Q3_K: MMQ_Q3_STRIDE), +16 B for the Q6_K realign reads past the last row
 size_t mmq_lds(int type, MmqShape sh) { return 2 * (size_t)mmq_buf_bytes(type, sh.rt, sh.cw) + 16; }
 
 // ------------------------------------------- prefill on the f16 matrix core (stated tolerance)
@@ -275,6 +279,11 @@ int launch_mmq_tiles(const int *types, int n_mat, const void *const *w, const in
     for (int d = 0; d < n_mat; ++d) has_q5 |= types[d] == Q5_K;
     if (mixed && has_q5 && sh.rt == 128 && sh.cw == 2) sh = {128, 1};  // kq_mmq_mixed<128, 2> has no Q5_K body
     if (sh.rt == 192 && (mixed || type == Q6_K)) sh = {128, 1};  // the 12-wave 192-row tile: Q4_K / Q5_K only
+    if (type == Q3_K) {  // one matrix, no epilogue; 64 x 64, 128 x 64 and 128 x 128 (mmq_shape's Q4_K choices)
+        if (n_mat > 1 || res || kv) return MI355X_E_UNSUPPORTED;
+        if (sh.rt == 192) sh = {128, 1};
+        if (sh.rt == 64 && sh.cw == 2) sh = {64, 1};
+    }
     const int rt = sh.rt;
     MmqArgs a;
     memset(&a, 0, sizeof(a));
@@ -296,7 +305,7 @@ int launch_mmq_tiles(const int *types, int n_mat, const void *const *w, const in
         a.my_col_stride[d] = y_col_stride[d];
         a.mtype[d] = types[d];
         tiles += (int)((N[d] + rt - 1) / rt);
-        wbytes += (double)N[d] * a.nb * block_bytes(types[d]);
+        wbytes += (double)N[d] * a.nb * type_block_bytes(types[d]);
         ybytes += (double)M * N[d] * 4.0;
     }
     a.tile0[n_mat] = tiles;

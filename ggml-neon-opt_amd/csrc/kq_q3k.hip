@@ -18,6 +18,7 @@
 // Activation: M = 1 and K <= 16384 with an f32 x: the workgroup quantizes x to Q8_K in LDS
 // itself (quant_block_wave, kq_quantize_q8K's bits); otherwise the caller's Q8_K rows (292-B
 // blocks) are copied into the same Q8L layout (d @0, qs @16, 304 B: 8-byte aligned pieces).
+#include <atomic>
 #include <string>
 
 #include "kq_common.h"
@@ -286,8 +287,25 @@ size_t q3k_workspace(int64_t K, int64_t M) {
     return ((size_t)M * (size_t)(K / QK) * Q8L_STRIDE + 255) & ~(size_t)255;  // >= the raw 292-B blocks
 }
 
-// mi355x_mul_mat's Q3_K arm: the decode token quantizes in the kernel, every other shape goes
-// through kq_quantize_q8K into the workspace first
+// mi355x_q3k_prefill: from how many columns on q3k_mul_mat takes kq_mmq's Q3_K body (the int8
+// matrix cores, the weights streamed once) instead of kq_gemv_q3k over groups of 8 columns. AUTO's
+// 64 is one whole column tile, a condition and no measurement (tools/q3k_bench.py sweeps the
+// crossover); MMQ takes it from the prefill GEMMs' floor on.
+namespace {
+std::atomic<int> g_q3k_prefill{MI355X_Q3K_PREFILL_AUTO};
+constexpr int64_t kQ3kMmqAutoCols = 64;
+}  // namespace
+int q3k_prefill_mode() { return g_q3k_prefill.load(); }
+int q3k_prefill_set(int impl) { return g_q3k_prefill.exchange(impl); }
+static bool q3k_takes_mmq(int64_t M) {
+    const int mode = q3k_prefill_mode();
+    return mode == MI355X_Q3K_PREFILL_MMQ ? M >= kMmqMinCols : mode == MI355X_Q3K_PREFILL_AUTO && M >= kQ3kMmqAutoCols;
+}
+
+// mi355x_mul_mat's Q3_K arm: the decode token quantizes in the kernel; from q3k_takes_mmq's
+// columns on kq_quantize_q8L and kq_mmq<Q3_K> (a workspace that is not 16-byte aligned or holds
+// only the raw 292-B blocks keeps the GEMV); every other shape goes through kq_quantize_q8K into
+// the workspace first. plan_q3k's refusals come first whichever kernel runs.
 int q3k_mul_mat(const void *w, int64_t K, int64_t N, size_t nb01, const float *x, int64_t M, size_t nb11, float *dst,
                 size_t nb1, void *ws, size_t ws_size, hipStream_t stream) {
     const int64_t nb = K / QK;
@@ -307,9 +325,19 @@ int q3k_mul_mat(const void *w, int64_t K, int64_t N, size_t nb01, const float *x
     const size_t q8_row = (size_t)nb * 292;
     if (!ws || ws_size < q8_row * (size_t)M || ((uintptr_t)ws & 3u)) return MI355X_E_WORKSPACE;
     if (!device_ok()) return MI355X_E_NODEVICE;
+    if (q3k_takes_mmq(M) && ((uintptr_t)ws & 15u) == 0 && ws_size >= (size_t)M * (size_t)nb * Q8L_STRIDE) {
+        rc = launch_quantize_q8L(x, (int64_t)(nb11 / 4), ws, K, M, stream, true);
+        if (rc) return rc;
+        return launch_mmq(Q3_K, w, K, N, nb01, (const uint8_t *)ws, M, dst, (int64_t)(nb1 / 4), stream);
+    }
     rc = launch_quantize(x, (int64_t)(nb11 / 4), ws, K, M, stream);
     if (rc) return rc;
     return q3k_mul_mat_q8(w, K, N, nb01, ws, M, q8_row, dst, nb1, stream);
 }
 
 }  // namespace kq
+
+extern "C" int mi355x_q3k_prefill(int impl) {
+    if (impl < MI355X_Q3K_PREFILL_AUTO || impl > MI355X_Q3K_PREFILL_MMQ) return MI355X_E_INVAL;
+    return kq::q3k_prefill_set(impl);
+}

@@ -65,6 +65,7 @@ PREFILL_EXACT, PREFILL_F16, PREFILL_F16_ALL = 0, 1, 2
 ATTN_PROMPT_EXACT, ATTN_PROMPT_F16 = 0, 1  # attn_prompt_precision
 MOE_PREFILL_AUTO, MOE_PREFILL_GEMV, MOE_PREFILL_GROUPED = 0, 1, 2  # moe_prefill
 SMALL_BATCH_NODES, SMALL_BATCH_FUSED = 0, 1  # small_batch
+Q3K_PREFILL_AUTO, Q3K_PREFILL_GEMV, Q3K_PREFILL_MMQ = 0, 1, 2  # q3k_prefill
 
 # Every symbol include/ggml_mi355x.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -107,7 +108,7 @@ EXPORTED_SYMBOLS = (
     "mi355x_moe_route", "mi355x_mul_mat_id_workspace_size", "mi355x_mul_mat_id", "mi355x_moe_combine",
     "mi355x_moe_prefill",
     "mi355x_small_batch", "mi355x_rows_cols_plan",
-    "mi355x_vec_dot_q3_K_q8_K", "mi355x_q3k_plan",
+    "mi355x_vec_dot_q3_K_q8_K", "mi355x_q3k_plan", "mi355x_q3k_prefill",
 )
 
 
@@ -353,6 +354,9 @@ def lib():
     if hasattr(L, "mi355x_moe_prefill"):
         L.mi355x_moe_prefill.argtypes = [i32]
         L.mi355x_moe_prefill.restype = i32
+    if hasattr(L, "mi355x_q3k_prefill"):
+        L.mi355x_q3k_prefill.argtypes = [i32]
+        L.mi355x_q3k_prefill.restype = i32
     if hasattr(L, "mi355x_small_batch"):
         L.mi355x_small_batch.argtypes = [i32]
         L.mi355x_small_batch.restype = i32
@@ -706,6 +710,15 @@ def q3k_plan(k, n_rows, m=1, fusedq=None):
     _check(lib().mi355x_q3k_plan(ctypes.c_int64(k), ctypes.c_int64(n_rows), ctypes.c_int64(m), int(fq),
                                  *[ctypes.byref(x) for x in v]), "mi355x_q3k_plan")
     return dict(zip(("ncol", "groups", "waves", "rows_per_wave", "flush_rows", "lds"), (x.value for x in v)))
+
+
+def q3k_prefill(impl):
+    """Which kernel mul_mat and the backend's MUL_MAT node run a Q3_K matrix of 16 or more columns on
+    (mi355x_q3k_prefill): Q3K_PREFILL_AUTO (default: kq_mmq's Q3_K body on the int8 matrix cores from 64
+    columns, kq_gemv_q3k over groups of 8 below), Q3K_PREFILL_GEMV (always kq_gemv_q3k) or Q3K_PREFILL_MMQ
+    (kq_mmq from 16 columns); the same bits either way. prompt, logprobs, perplexity and step_batch follow it.
+    Part of the backend's plan key. Returns the previous value, E_INVAL for any other."""
+    return int(_lib_with("mi355x_q3k_prefill").mi355x_q3k_prefill(impl))
 
 
 def gemv_fused_ext(mats, x, prologue=PRO_NONE, x2=None, eps=0.0, residual=None, epi_y=None, stream=None):

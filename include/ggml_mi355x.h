@@ -162,10 +162,30 @@ int mi355x_quantize_q8_K(const float *x, size_t x_stride, void *y, int64_t k, in
  * M == 1 with K <= 8192 quantizes inside the GEMV kernel (no workspace); other
  * shapes need a workspace of mi355x_mul_mat_workspace_size() bytes (the Q8_K
  * copy of src1). Async on `stream`.
- * Q3_K (kq_gemv_q3k, every M in groups of up to 8 columns): rows contiguous (nb01 == K / 256 * 110,
- * else MI355X_E_UNSUPPORTED) at an even address (else MI355X_E_INVAL), K <= 65536; M == 1 with
- * K <= 16384 quantizes inside the kernel. mi355x_prefill_precision does not apply to it. The fused
- * entries below (mi355x_gemv_fused*, mi355x_mul_mat_id, the layer engine) refuse the type. */
+ * Q3_K (kq_gemv_q3k, M in groups of up to 8 columns; prompts on kq_mmq, below): rows contiguous
+ * (nb01 == K / 256 * 110, else MI355X_E_UNSUPPORTED) at an even address (else MI355X_E_INVAL),
+ * K <= 65536; M == 1 with K <= 16384 quantizes inside the kernel. mi355x_prefill_precision does not
+ * apply to it. The fused entries below (mi355x_gemv_fused*, mi355x_mul_mat_id, the layer engine)
+ * refuse the type.
+ *
+ * mi355x_q3k_prefill: which kernel mi355x_mul_mat (and with it the graph backend's MUL_MAT node)
+ * runs a Q3_K matrix of 16 or more columns on (process-wide, like mi355x_moe_prefill; reads no
+ * environment; part of the backend's plan key). kq_gemv_q3k streams the weights once per group of
+ * 8 columns; kq_mmq's Q3_K body streams them once per call on the int8 matrix cores (the operand
+ * carries -sc * q, which is an int8 where sc * q = +128 is not; one int32 accumulator per
+ * superblock) and gives the same bits:
+ *   MI355X_Q3K_PREFILL_AUTO (0, default)  kq_mmq from 64 columns (one whole column tile) on,
+ *                                         kq_gemv_q3k below;
+ *   MI355X_Q3K_PREFILL_GEMV (1)           always kq_gemv_q3k;
+ *   MI355X_Q3K_PREFILL_MMQ (2)            kq_mmq from 16 columns on.
+ * The checks and refusals of a call, and mi355x_mul_mat_workspace_size, are the same under all
+ * three: a workspace that is not 16-byte aligned, or holds the raw Q8_K rows but not ne11 * K / 256
+ * blocks of 304 bytes, keeps kq_gemv_q3k. mi355x_mul_mat_q8 (raw Q8_K rows) always runs kq_gemv_q3k.
+ * Returns the previous value, or MI355X_E_INVAL (and changes nothing) for any other. */
+#define MI355X_Q3K_PREFILL_AUTO 0
+#define MI355X_Q3K_PREFILL_GEMV 1
+#define MI355X_Q3K_PREFILL_MMQ 2
+int mi355x_q3k_prefill(int impl);
 size_t mi355x_mul_mat_workspace_size(int src0_type, int64_t ne00, int64_t ne01, int64_t ne11);
 /* The plan of the kq_gemv_q3k launch mi355x_mul_mat would issue for a packed Q3_K matrix of n_rows
  * rows of k elements against m columns (no launch, no device access): *ncol = columns per group
